@@ -2,6 +2,8 @@
 """Headline benchmark: hand-frames/s of the UmeTrack per-frame hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run)
+  python bench.py ... --full                               (also the roofline, exact-fp32, CPU and parity legs below)
+  python bench.py ... --dump-outputs DIR                   (the last timed step's records -> DIR/records.npy)
 
 One "step" = one pass of the whole hot path (fisheye->pinhole resample of every crop, backbone,
 fusion/temporal/regressor head, decode, forward kinematics) over one shard of synthetic frames:
@@ -11,7 +13,14 @@ seeded synthetic weights).  Inputs are resident in HBM before the timed region. 
 contiguously across ranks (weak scaling: --frames-per-gpu each) and the packed per-hand records are
 all-gathered over RCCL at the end of every step.
 
-Extra JSON objects: `roofline` (the implicit-GEMM convolution kernel, hipEvent-timed per launch in a
+A plain run sets up, warms up, times the K steps and prints the result line; everything else is behind --full.
+--dump-outputs DIR writes what the timed path returned in its last step, the [hand-frames, 123] float32 records
+(pose record | 21 keypoints in mm, pipeline.HotPath.step), as DIR/records.npy; above 64 MB a fixed seeded sample of
+rows, with their row numbers in DIR/records_rows.npy.  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
+Extra JSON objects, with --full only: `exact_fp32_mode` / `split_f16_check` (the same K steps with the exact-fp32
+convolutions, and the records against that mode's), `roofline` (the implicit-GEMM convolution kernel, hipEvent-timed per launch in a
 separate profiling pass on the launch stream) and `cpu_baseline` (the CPU oracle's restatement of the
 same path on a bounded sample, rank 0, N=1 only).  The same checker leg also drives all 369 label frames of
 recording_00 as one sequence (temporal memory engaged) through the drop-in HandTracker and the oracle and
@@ -32,6 +41,7 @@ import torch  # noqa: E402
 
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_F16_MFMA_TFLOPS = 2500.0      # MI355X_MICROARCH.md: dense fp16/bf16 MFMA; the split kernels spend 3 fp16 MFMA flops per flop
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: all files together
 
 
 def main():
@@ -61,6 +71,12 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the step's launches from one captured hipGraph")
     ap.add_argument("--cropgen-in-step", action="store_true",
                     help="also regenerate the crop cameras from the label poses inside every step (SURVEY 8 f1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs besides the headline figure: exact-fp32 mode and split check, rooflines, "
+                         "CPU baseline, recording_00 parity (each still subject to its own --no-* / 0 option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records ([hand-frames, 123] float32) to DIR/records.npy "
+                         "(above 64 MB: a fixed seeded row sample, row numbers in DIR/records_rows.npy)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -166,6 +182,17 @@ def main():
     dt, out = timed_run()
     hot.check()            # deferred index checks of every step above
     assert out.shape == (s_local * world, pipeline.RECORD)
+    if args.dump_outputs and rank == 0:
+        # before any later leg reuses the record buffer; above DUMP_MAX_BYTES a fixed seeded sample of rows (ascending),
+        # whose row numbers go to records_rows.npy
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        recs = out.detach().float()
+        max_rows = DUMP_MAX_BYTES // (recs.shape[1] * 4 + 8)
+        if recs.shape[0] > max_rows:
+            rows = np.sort(np.random.default_rng(0).choice(recs.shape[0], size=max_rows, replace=False))
+            recs = recs[torch.from_numpy(rows).to(recs.device)]
+            np.save(os.path.join(args.dump_outputs, "records_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "records.npy"), recs.cpu().numpy())
     finite = bool(torch.isfinite(out).all().item())
     if planner is not None and not bool(planner.ok.item()):
         raise SystemExit("crop-camera generation inside the step produced a candidate without two views")
@@ -177,7 +204,7 @@ def main():
     # split-fp16 mode: the same K steps timed with the exact-fp32 convolutions (every rank, same barriers), and the records
     # of the timed workload against that mode's on the same batch
     split_check, fp32_mode = None, None
-    if args.conv != "fp32" and not args.no_fp32_mode:
+    if args.full and args.conv != "fp32" and not args.no_fp32_mode:
         rec_split = hot.step(batch).clone()
         eng.set_conv_arithmetic("fp32")
         dt32, _ = timed_run()
@@ -196,7 +223,7 @@ def main():
     roofline = None
     # (split arithmetic requested; with the roofline pass: requested AND its launches were seen)
     split_kind = args.conv != "fp32"
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # separate profiling pass: hipEvents around every conv_igemm launch on the launch stream
         eng.profile_begin()
         n_prof = 2
@@ -259,7 +286,7 @@ def main():
                          "avg_launch_ms": round(ms32 / max(l32, 1), 5)}
 
     cpu, batched = None, None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         from oracle import checks
         # the GPU box gives one GPU a 16-CPU share although os.cpu_count() reports the whole host
         threads = min(os.cpu_count() or 1, 16)
@@ -273,7 +300,7 @@ def main():
                          f"oracle resample+network+FK, {r['seconds']:.1f} s"}
 
     parity = None
-    if rank == 0 and world == 1 and args.parity_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.parity_frames > 0:
         from oracle import checks      # checker leg, like cpu_baseline above: never inside the timed region
         eng.close()
         r = checks.run_recording00(sd, str(device), known=known, n_frames=args.parity_frames)

@@ -15,6 +15,7 @@ regenerated + expected outputs) under tests/golden/:
   torch_data.npz                        reference lib.batched_dataset.data_transform crops + matrices (f2)
   metrics.npz                           reference load_eval._compute_metrics / metric_utils outputs (f4)
   *.torch.idx / *.torch.bin             files from the product's writer, verified readable by the reference's TorchIdx (f3)
+  dropin_loader_rows.npz                what the reference's loader yields from them through the drop-in lib/ (8 b)
 and the label data the bench/tests drive the path with:
   absolutetrack_amd/data/recording_00_labels.npz   (from sample_data/recording_00.json)
 
@@ -321,6 +322,38 @@ def export_idxbin():
     np.savez_compressed(os.path.join(GOLD, "idxbin_offsets.npz"), **offs)
 
 
+# ----------------------------------------------------------------------------- drop-in loader chain (SURVEY 8 b)
+def export_dropin_loader_rows():
+    """The rows the reference's own loader chain (find_dataset -> AsyncToIterableDataset), running on top of this
+    repo's served lib.data_utils.{fs,idxbinfile} (repo first on PYTHONPATH, the reference behind it), yields from the
+    seq_mono / seq_labels fixtures: dropin_loader_rows.npz (n, mono<i>, lab<i> = msgpack of the labels).
+    The reference's Sampler passes an argument to torch.utils.data.Sampler.__init__ that this torch no longer
+    accepts, so a plain index range stands in."""
+    import shutil
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        leaf = os.path.join(tmp, "torch_data", "real", "testing")
+        os.makedirs(leaf)
+        for field, src in (("mono", "seq_mono"), ("labels", "seq_labels")):
+            for ext in (".torch.idx", ".torch.bin"):
+                shutil.copy(os.path.join(GOLD, src + ext), os.path.join(leaf, field + ext))
+        code = f"""
+import numpy as np, msgpack
+import lib.data_utils.fs as fs, lib.data_utils.idxbinfile as ib
+assert fs.__file__.startswith({REPO!r}) and ib.__file__.startswith({REPO!r})
+from lib.data_utils.async_dataset import AsyncToIterableDataset, find_dataset
+from lib.data_utils.split import Split
+d = find_dataset([{os.path.join(tmp, "torch_data", "real")!r}], ["mono", "labels"])[Split.TEST]
+rows = list(AsyncToIterableDataset(d, range(len(d)), max_prefetch=4))
+np.savez_compressed({os.path.join(GOLD, "dropin_loader_rows.npz")!r}, n=len(rows),
+                    **{{f"mono{{i}}": np.asarray(r["mono"]) for i, r in enumerate(rows)}},
+                    **{{f"lab{{i}}": np.frombuffer(msgpack.packb(r["labels"]), np.uint8) for i, r in enumerate(rows)}})
+"""
+        subprocess.run([sys.executable, "-c", code], check=True, cwd=tmp,
+                       env=dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, REF])))
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(8)
@@ -331,6 +364,7 @@ def main():
     export_torch_data()
     export_metrics()
     export_idxbin()
+    export_dropin_loader_rows()
     np.savez_compressed(os.path.join(GOLD, "model_known.npz"), **run_model_scenario(True))
     np.savez_compressed(os.path.join(GOLD, "model_unknown.npz"), **run_model_scenario(False))
     for f in sorted(os.listdir(GOLD)):

@@ -11,9 +11,9 @@ CONV=${CONV:-split_f16}
 O=$R/gpurun_out/profiles_r04_$CONV
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 python3 $R/bench.py --conv $CONV > $O/bench_stdout.log 2>$O/bench_stderr.log || exit 1
+timeout -k 10 400 python3 $R/bench.py --full --conv $CONV > $O/bench_stdout.log 2>$O/bench_stderr.log || exit 1
 tail -1 $O/bench_stdout.log > $O/bench_line.json
-rm -rf /tmp/prof_s && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o run --output-format csv -- python3 $R/bench.py --conv $CONV --no-fp32-mode --steps 5 --warmup 1 --parity-frames 0 --cpu-frames 0 > $O/bench_under_rocprof.log 2>&1 || exit 1
+rm -rf /tmp/prof_s && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o run --output-format csv -- python3 $R/bench.py --full --conv $CONV --no-fp32-mode --steps 5 --warmup 1 --parity-frames 0 --cpu-frames 0 > $O/bench_under_rocprof.log 2>&1 || exit 1
 grep -o "{\"metric.*" $O/bench_under_rocprof.log | tail -1 > $O/bench_under_rocprof.json
 cp /tmp/prof_s/run_kernel_stats.csv $O/bench_kernel_stats.csv
 python3 $R/tools/layer_profile.py /tmp/prof_s/run_kernel_trace.csv 4096 4096 > $O/bench_conv_layers.txt 2>&1 || exit 1
