@@ -25,6 +25,7 @@ EXPORTS = (
     "ut_set_index_checks", "ut_poll_status", "ut_warp_backbone", "ut_set_latency_mode", "ut_set_conv_arithmetic",
     "ut_set_backbone_lanes", "ut_status_snapshot", "ut_warp_map", "ut_set_block_fusion", "ut_set_resident_weights",
     "ut_canonical_backbone_weights", "ut_set_split_scale", "ut_calibrate_split", "ut_get_split_calibration",
+    "ut_gen_crop_cameras_from_window_points",
 )
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
@@ -79,6 +80,9 @@ def load_library() -> ctypes.CDLL:
     lib.ut_gen_crop_cameras.restype = i32
     lib.ut_gen_crop_cameras.argtypes = [vp, vp, vp, f32p, f32p, i32, f32p, f32p, vp, vp, i32, i32, i32, i32, i32, i32,
                                         i32, ctypes.c_double, vp, f32p, f32p, vp, vp, vp, f32p, vp]
+    lib.ut_gen_crop_cameras_from_window_points.restype = i32
+    lib.ut_gen_crop_cameras_from_window_points.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, ctypes.c_double, vp,
+                                                           f32p, f32p, vp, vp, vp, vp]
     lib.ut_gen_crop_matrices.restype = i32
     lib.ut_gen_crop_matrices.argtypes = [vp, f32p, f32p, f32p, vp, i32, i32, i32, i32, ctypes.c_double, f32p, f32p, f32p,
                                          vp, vp]
@@ -264,6 +268,51 @@ def gen_crop_cameras(cam_params: torch.Tensor, camera_angles: torch.Tensor, hand
                                      _ptr(out["n_views"]), _ptr(out["status"]), _ptr(out.get("landmarks")), _stream(d))
     if rc != 0:
         raise RuntimeError(f"ut_gen_crop_cameras failed ({rc}): {lib.ut_last_error(None).decode()}")
+    return out
+
+
+def gen_crop_cameras_from_window_points(cam_params: torch.Tensor, keypoints: torch.Tensor, src_row: torch.Tensor,
+                                        hand_idx: torch.Tensor, crop_size: int = arch.CROP,
+                                        focal_multiplier: float = 0.8, check_indices: bool = True
+                                        ) -> Dict[str, torch.Tensor]:
+    """ut_gen_crop_cameras_from_window_points: crop cameras of n hand candidates placed from 21 window keypoints per
+    view (lib/tracker/tracker.py:111-219), one launch.  cam_params [R,32] f64, keypoints [n,V,21,2] (window px),
+    src_row [n,V] (row of cam_params, -1 = not seen in that view), hand_idx [n].  Returns crop_params [n,V,24] f64,
+    intrinsics [n,V,3,3], extrinsics [n,V,4,4], cam_index [n,V] i32 (the src_row of each filled slot, -1 after),
+    n_views [n] i32, status [n] i32.  All tensors on one HIP device; no CPU fallback."""
+    lib = load_library()
+    d = keypoints.device
+    if d.type != "cuda":
+        raise NativeLibraryError("gen_crop_cameras_from_window_points needs tensors on a HIP device (no CPU fallback)")
+    if keypoints.dim() != 4 or tuple(keypoints.shape[2:]) != (arch.N_LANDMARKS, 2):
+        raise ValueError("keypoints must be [n, views, 21, 2]")
+    n, v = keypoints.shape[:2]
+    cam_params = _need(cam_params, torch.float64, d, "cam_params").reshape(-1, 32)
+    keypoints = _need(keypoints, torch.float64, d, "keypoints")
+    src_row = _need(src_row, torch.int32, d, "src_row")
+    hand_idx = _need(hand_idx, torch.int64, d, "hand_idx").reshape(-1)
+    if tuple(src_row.shape) != (n, v) or hand_idx.shape[0] != n:
+        raise ValueError("gen_crop_cameras_from_window_points: keypoints, src_row and hand_idx disagree on n / views")
+    # (reads the indices back: pass check_indices=False when the same tensors were validated before; the C entry
+    # checks them again before it launches and then fails with UT_E_INVALID instead)
+    if check_indices and n:
+        if int(src_row.min()) < -1 or int(src_row.max()) >= cam_params.shape[0]:
+            raise ValueError("gen_crop_cameras_from_window_points: src_row points past cam_params")
+        if bool(((hand_idx != 0) & (hand_idx != 1)).any()):
+            raise ValueError("gen_crop_cameras_from_window_points: hand_idx must be 0 or 1")
+    out = {"crop_params": torch.empty(n, v, 24, dtype=torch.float64, device=d),
+           "intrinsics": torch.empty(n, v, 3, 3, dtype=torch.float32, device=d),
+           "extrinsics": torch.empty(n, v, 4, 4, dtype=torch.float32, device=d),
+           "cam_index": torch.empty(n, v, dtype=torch.int32, device=d),
+           "n_views": torch.empty(n, dtype=torch.int32, device=d),
+           "status": torch.empty(n, dtype=torch.int32, device=d)}
+    with torch.cuda.device(d):
+        rc = lib.ut_gen_crop_cameras_from_window_points(
+            None, _ptr(cam_params), cam_params.shape[0], _ptr(keypoints), _ptr(src_row), _ptr(hand_idx), n, v,
+            crop_size, ctypes.c_double(focal_multiplier), _ptr(out["crop_params"]), _ptr(out["intrinsics"]),
+            _ptr(out["extrinsics"]), _ptr(out["cam_index"]), _ptr(out["n_views"]), _ptr(out["status"]), _stream(d))
+    if rc != 0:
+        raise RuntimeError(f"ut_gen_crop_cameras_from_window_points failed ({rc}): {lib.ut_last_error(None).decode()}")
     return out
 
 

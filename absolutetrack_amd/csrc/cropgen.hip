@@ -95,13 +95,19 @@ __device__ inline void fit_begin(const double* c2w0, const double* center, doubl
 
 // one bounding point through the new world->eye: largest |x/z|, |y/z| so far and the "behind the camera" flag
 // (crop.py:15-28); max is exact, so the points may be visited in any order (or by different lanes)
-__device__ inline void fit_point(const double* w2e, const float* pt, double& max_ndc, bool& bad) {
-  const double px = (double)pt[0], py = (double)pt[1], pz = (double)pt[2];
+__device__ inline void fit_point(const double* w2e, const double* pt, double& max_ndc, bool& bad) {
+  const double px = pt[0], py = pt[1], pz = pt[2];
   const double ex = w2e[0] * px + w2e[1] * py + w2e[2] * pz + w2e[3];
   const double ey = w2e[4] * px + w2e[5] * py + w2e[6] * pz + w2e[7];
   const double ez = w2e[8] * px + w2e[9] * py + w2e[10] * pz + w2e[11];
   if (ez < 0.0001) bad = true;
   max_ndc = fmax(max_ndc, fmax(fabs(ex / ez), fabs(ey / ez)));
+}
+
+// fp32 points (FK output) go through the same arithmetic after an exact widening
+__device__ inline void fit_point(const double* w2e, const float* pt, double& max_ndc, bool& bad) {
+  const double p[3] = {(double)pt[0], (double)pt[1], (double)pt[2]};
+  fit_point(w2e, p, max_ndc, bad);
 }
 
 __device__ inline void fit_end(double max_ndc, bool bad, int crop_size, double focal_multiplier, CropFit& o) {
@@ -120,6 +126,24 @@ __device__ inline void fit_crop_camera(const double* c2w0, const float* pts, int
   bool bad = false;
   for (int q = 0; q < n_pts; ++q) fit_point(o.w2e, pts + 3 * q, max_ndc, bad);
   fit_end(max_ndc, bad, crop_size, focal_multiplier, o);
+}
+
+// one view's outputs: the crop_params row of ut_warp_crops, K, and the network's world->eye (tracker.py:333-337)
+__device__ inline void write_crop_view(const CropFit& fit, double* cp, float* kk, float* ex) {
+  const double focal = fit.focal, cxy = fit.cxy;
+  const double* c2w = fit.c2w;
+  cp[0] = focal; cp[1] = focal; cp[2] = cxy; cp[3] = cxy;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) cp[4 + 3 * i + j] = c2w[4 * i + j];
+    cp[13 + i] = c2w[4 * i + 3];
+  }
+  for (int i = 16; i < 24; ++i) cp[i] = 0.0;
+  kk[0] = (float)focal; kk[1] = 0.f; kk[2] = (float)cxy; kk[3] = 0.f; kk[4] = (float)focal; kk[5] = (float)cxy;
+  kk[6] = 0.f; kk[7] = 0.f; kk[8] = 1.f;
+  // extrinsics = inv(crop camera_to_world) with the translation in metres (tracker.py:335-337)
+  double ext[16];
+  inv4(c2w, ext);
+  for (int i = 0; i < 16; ++i) ex[i] = (float)((i % 4 == 3 && i < 12) ? ext[i] * 0.001 : ext[i]);
 }
 
 // middle of the bounding box, (pts.min + pts.max) / 2.0 (crop.py:60): in fp32 like numpy on float32 points
@@ -306,24 +330,9 @@ __global__ __launch_bounds__(64) void cropgen_kernel(CropGenArgs g) {
     for (int k = 0; k < 16; ++k) fit.w2e[k] = s_w2e[lane][k];
     fit_end(my_ndc, my_bad, g.crop_size, g.focal_multiplier, fit);
     if (fit.bad) my_status = 1;
-    const double focal = fit.focal, cxy = fit.cxy;
-    const double* c2w = fit.c2w;
     // ---- outputs
-    double* cp = g.crop_params + ((size_t)s * g.max_views + lane) * 24;
-    cp[0] = focal; cp[1] = focal; cp[2] = cxy; cp[3] = cxy;
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) cp[4 + 3 * i + j] = c2w[4 * i + j];
-      cp[13 + i] = c2w[4 * i + 3];
-    }
-    for (int i = 16; i < 24; ++i) cp[i] = 0.0;
-    float* kk = g.intrinsics + ((size_t)s * g.max_views + lane) * 9;
-    kk[0] = (float)focal; kk[1] = 0.f; kk[2] = (float)cxy; kk[3] = 0.f; kk[4] = (float)focal; kk[5] = (float)cxy;
-    kk[6] = 0.f; kk[7] = 0.f; kk[8] = 1.f;
-    // extrinsics = inv(crop camera_to_world) with the translation in metres (tracker.py:335-337)
-    double ext[16];
-    inv4(c2w, ext);
-    float* ex = g.extrinsics + ((size_t)s * g.max_views + lane) * 16;
-    for (int i = 0; i < 16; ++i) ex[i] = (float)((i % 4 == 3 && i < 12) ? ext[i] * 0.001 : ext[i]);
+    const size_t slot = (size_t)s * g.max_views + lane;
+    write_crop_view(fit, g.crop_params + slot * 24, g.intrinsics + slot * 9, g.extrinsics + slot * 16);
     g.cam_index[(size_t)s * g.max_views + lane] = s_sel[lane];
   } else if (lane < g.max_views) {
     g.cam_index[(size_t)s * g.max_views + lane] = -1;
@@ -335,6 +344,141 @@ __global__ __launch_bounds__(64) void cropgen_kernel(CropGenArgs g) {
     g.n_views[s] = n_views;
     g.status[s] = my_status;
   }
+}
+
+// Label-free crop placement (lib/tracker/tracker.py:111-219, the live demo's path): 21 window keypoints of a hand seen
+// by a Fisheye62 camera -> one crop camera.  Per (hand, view), in the reference's order of operations:
+//   q = (w - c) / f; radial-only five-step fixed point of Fisheye62.undistort (lib/common/camera.py:146-181; not the
+//   inverse of evaluate: p1 / p2 are ignored); arctan unprojection (u s, v s, cos r), s = np.sinc(r / pi)
+//   (camera.py:88-94); eye_to_world; bounding-box centre; look-at with camera angle 0; x-mirror for hand 1; focal fit
+//   on the 21 points (crop.py:15-28); camera_to_world = inv(new world->eye).
+// All fp64 like numpy.  The elementwise steps are written without fused multiply-adds (numpy rounds every operation);
+// what remains different from the host is the last bit of sin / cos / pow and the summation order of the 3x3
+// products numpy hands to BLAS.
+// One wave per candidate: lane v*21+k unprojects keypoint k of view v; the centre and the max-|ndc| reductions are
+// wave min / max (exact in any order); lane v (a valid view) aims and finishes view v.
+constexpr int WP_MAX_VIEWS = 3;   // 3 x 21 (view, keypoint) pairs fill a wave
+
+__device__ inline double wave_min(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off));
+  return x;
+}
+
+__device__ inline double wave_max(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off));
+  return x;
+}
+
+// window px -> world point through a cam_params row (Fisheye62CameraModel.window_to_eye, then eye_to_world)
+__device__ inline void window_to_world_d(const double* cam, const double* w, double* out) {
+#pragma clang fp contract(off)
+  const double qx = (w[0] - cam[2]) / cam[0], qy = (w[1] - cam[3]) / cam[1];
+  const double k1 = cam[4], k2 = cam[5], k3 = cam[6], k4 = cam[7], k5 = cam[10], k6 = cam[11];
+  double x = qx, y = qy;
+  for (int it = 0; it < 5; ++it) {          // camera.py:167-179
+    const double r2 = x * x + y * y;
+    const double rad = 1 + k1 * r2 + k2 * (r2 * r2) + k3 * pow(r2, 3.0) + k4 * pow(r2, 4.0) + k5 * pow(r2, 5.0) +
+                       k6 * pow(r2, 6.0);
+    x = qx / rad;
+    y = qy / rad;
+  }
+  const double r = sqrt(x * x + y * y);
+  const double xs = r / 3.141592653589793;                      // np.sinc(r / pi) = sin(y) / y, y = pi * x
+  const double ys = 3.141592653589793 * (xs == 0.0 ? 1.0e-20 : xs);
+  const double s = sin(ys) / ys;
+  const double e[3] = {x * s, y * s, cos(r)};
+  const double* rc = cam + 12;
+  const double* tc = cam + 21;
+  for (int i = 0; i < 3; ++i) out[i] = (rc[3 * i] * e[0] + rc[3 * i + 1] * e[1] + rc[3 * i + 2] * e[2]) + tc[i];
+}
+
+__global__ __launch_bounds__(64) void cropgen_window_kernel(CropGenWindowArgs g) {
+  const int s = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int v_me = lane / 21, k_me = lane - 21 * v_me;
+  __shared__ double s_w2e[WP_MAX_VIEWS][16];
+  __shared__ double s_center[WP_MAX_VIEWS][3];
+  const int32_t* rows = g.src_row + (size_t)s * g.max_views;
+  const bool mine = v_me < g.max_views && rows[v_me] >= 0;      // this lane holds a keypoint of a seen view
+  double pt[3] = {0.0, 0.0, 0.0};
+  if (mine) {
+    const double* cam = g.cam_params + (size_t)rows[v_me] * 32;
+    const double* w = g.keypoints + (((size_t)s * g.max_views + v_me) * 21 + k_me) * 2;
+    window_to_world_d(cam, w, pt);
+  }
+  // ---- bounding-box centre per view, (min + max) / 2 (tracker.py:135-137)
+  for (int v = 0; v < g.max_views; ++v) {
+    if (rows[v] < 0) continue;                                   // uniform across the wave
+    const bool in_v = mine && v_me == v;
+    for (int d = 0; d < 3; ++d) {
+      const double lo = wave_min(in_v ? pt[d] : INFINITY), hi = wave_max(in_v ? pt[d] : -INFINITY);
+      if (lane == 0) s_center[v][d] = (lo + hi) / 2;
+    }
+  }
+  __syncthreads();
+  // ---- look-at per view (camera angle 0) and the mirror of hand 1 (tracker.py:139-148)
+  const bool right = g.hand_idx[s] == 1;
+  if (lane < g.max_views && rows[lane] >= 0) {
+    const double* cam = g.cam_params + (size_t)rows[lane] * 32;
+    const double* rc = cam + 12;
+    const double* tc = cam + 21;
+    const double c2w0[16] = {rc[0], rc[1], rc[2], tc[0], rc[3], rc[4], rc[5], tc[1], rc[6], rc[7], rc[8], tc[2], 0, 0, 0, 1};
+    fit_begin(c2w0, s_center[lane], 0.0, right, s_w2e[lane]);
+  }
+  __syncthreads();
+  // ---- largest |ndc| of the 21 points per view and the "behind the camera" flag (tracker.py:150-153, crop.py:15-28)
+  double my_ndc = 0.0;       // of the view lane v finishes
+  bool my_bad = false;
+  for (int v = 0; v < g.max_views; ++v) {
+    if (rows[v] < 0) continue;
+    double m = 0.0;
+    bool bad = false;
+    if (mine && v_me == v) fit_point(s_w2e[v], pt, m, bad);
+    int badi = bad ? 1 : 0;
+    m = wave_max(m);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) badi |= __shfl_xor(badi, off);
+    if (lane == v) { my_ndc = m; my_bad = badi != 0; }
+  }
+  // ---- outputs: slots filled front to back in input order
+  int my_status = 0;
+  if (lane < g.max_views) {
+    int slot = 0, n_views = 0;
+    for (int v = 0; v < g.max_views; ++v) {
+      if (rows[v] < 0) continue;
+      if (v < lane) ++slot;
+      ++n_views;
+    }
+    if (rows[lane] >= 0) {
+      CropFit fit;
+      for (int k = 0; k < 16; ++k) fit.w2e[k] = s_w2e[lane][k];
+      fit_end(my_ndc, my_bad, g.crop_size, g.focal_multiplier, fit);
+      if (fit.bad) my_status = 1;
+      const size_t o = (size_t)s * g.max_views + slot;
+      write_crop_view(fit, g.crop_params + o * 24, g.intrinsics + o * 9, g.extrinsics + o * 16);
+      g.cam_index[o] = rows[lane];
+    }
+    if (lane >= n_views) {                                       // unused slots: -1 and zeros, like cropgen_kernel
+      const size_t o = (size_t)s * g.max_views + lane;
+      g.cam_index[o] = -1;
+      for (int i = 0; i < 24; ++i) g.crop_params[o * 24 + i] = 0.0;
+      for (int i = 0; i < 9; ++i) g.intrinsics[o * 9 + i] = 0.f;
+      for (int i = 0; i < 16; ++i) g.extrinsics[o * 16 + i] = 0.f;
+    }
+    if (lane == 0) g.n_views[s] = n_views;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) my_status |= __shfl_xor(my_status, off);
+  if (lane == 0) g.status[s] = my_status;
+}
+
+hipError_t launch_cropgen_window(const CropGenWindowArgs& g, hipStream_t s) {
+  if (g.n <= 0) return hipSuccess;
+  if (g.max_views < 1 || g.max_views > WP_MAX_VIEWS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cropgen_window_kernel, dim3(g.n), dim3(64), 0, s, g);
+  return hipGetLastError();
 }
 
 // torch_data path: _gen_crop_matrices of lib/batched_dataset/data_transform.py:147-212

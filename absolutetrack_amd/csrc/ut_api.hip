@@ -1467,6 +1467,36 @@ int ut_gen_crop_cameras(ut_handle h, const double* cam_params, const double* cam
   return UT_OK;
 }
 
+int ut_gen_crop_cameras_from_window_points(ut_handle h, const double* cam_params, int n_cam_rows, const double* keypoints,
+                                           const int32_t* src_row, const int64_t* hand_idx, int n, int max_views,
+                                           int crop_size, double focal_multiplier, double* crop_params, float* intrinsics,
+                                           float* extrinsics, int32_t* cam_index, int32_t* n_views, int32_t* status,
+                                           void* stream) {
+  if (n == 0) return UT_OK;
+  if (!cam_params || !keypoints || !src_row || !hand_idx || !crop_params || !intrinsics || !extrinsics || !cam_index ||
+      !n_views || !status || n < 0 || n_cam_rows <= 0 || max_views < 1 || max_views > 3 || crop_size <= 1)
+    return fail(h, UT_E_INVALID, "ut_gen_crop_cameras_from_window_points: bad argument");
+  ON_DEVICE_IF(h);
+  // the index arrays are read back and checked before anything is launched: a bad row is reported, never read
+  std::vector<int32_t> rows((size_t)n * max_views);
+  std::vector<int64_t> hands((size_t)n);
+  HIPCHK(h, hipMemcpyAsync(rows.data(), src_row, rows.size() * sizeof(int32_t), hipMemcpyDefault, (hipStream_t)stream));
+  HIPCHK(h, hipMemcpyAsync(hands.data(), hand_idx, hands.size() * sizeof(int64_t), hipMemcpyDefault, (hipStream_t)stream));
+  HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
+  for (int32_t r : rows)
+    if (r < -1 || r >= n_cam_rows)
+      return fail(h, UT_E_INVALID, "ut_gen_crop_cameras_from_window_points: src_row outside [-1, n_cam_rows)");
+  for (int64_t x : hands)
+    if (x != 0 && x != 1) return fail(h, UT_E_INVALID, "ut_gen_crop_cameras_from_window_points: hand_idx not 0 or 1");
+  ut::CropGenWindowArgs g{};
+  g.cam_params = cam_params; g.keypoints = keypoints; g.src_row = src_row; g.hand_idx = hand_idx;
+  g.n = n; g.max_views = max_views; g.crop_size = crop_size; g.focal_multiplier = focal_multiplier;
+  g.crop_params = crop_params; g.intrinsics = intrinsics; g.extrinsics = extrinsics; g.cam_index = cam_index;
+  g.n_views = n_views; g.status = status;
+  HIPCHK(h, ut::launch_cropgen_window(g, (hipStream_t)stream));
+  return UT_OK;
+}
+
 int ut_gen_crop_matrices(ut_handle h, const float* orig_extrinsics, const float* orig_intrinsics, const float* crop_points,
                          const int64_t* hand_idx, int n_frames, int n_views, int n_pts, int crop_size,
                          double focal_multiplier, float* extrinsics_xf, float* new_intrinsics, float* resample_xf,

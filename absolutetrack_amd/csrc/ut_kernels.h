@@ -260,6 +260,23 @@ struct CropGenArgs {
 };
 hipError_t launch_cropgen(const CropGenArgs& g, hipStream_t s);
 
+// label-free crop cameras from 21 window keypoints per (hand, view) (lib/tracker/tracker.py:111-219)
+struct CropGenWindowArgs {
+  const double* cam_params;     // [n_cam_rows,32] Fisheye62 source camera rows (layout of ut_warp_crops)
+  const double* keypoints;      // [n,max_views,21,2] window px
+  const int32_t* src_row;       // [n,max_views] row of cam_params, -1 = not seen in that view (checked by the caller)
+  const int64_t* hand_idx;      // [n] 0 / 1 (1 = x-mirrored crop)
+  int n, max_views, crop_size;
+  double focal_multiplier;
+  double* crop_params;          // [n,max_views,24]
+  float* intrinsics;            // [n,max_views,3,3]
+  float* extrinsics;            // [n,max_views,4,4]
+  int32_t* cam_index;           // [n,max_views] src_row of the view in that slot (-1 = unused slot)
+  int32_t* n_views;             // [n]
+  int32_t* status;              // [n] 0 ok, 1 = "Unable to create crop camera"
+};
+hipError_t launch_cropgen_window(const CropGenWindowArgs& g, hipStream_t s);
+
 // torch_data path: crop matrices per (frame, view) and the pinhole->pinhole homography resampler.
 struct CropMatArgs {
   const float* orig_extrinsics;  // [n_frames*n_views,4,4] world->eye

@@ -177,6 +177,31 @@ def crop_plan_on_device(lab: Dict[str, np.ndarray], hand_model: HandModel, frame
             "hand_idx": hand_idx[keep]}
 
 
+def crop_plan_from_window_points(cam_params, keypoints, src_row, hand_idx, device,
+                                 opts: Optional[HandTrackerOpts] = None) -> Dict[str, torch.Tensor]:
+    """Crop plan of hand candidates placed from 2-D keypoints (lib/tracker/tracker.py:111-219, the live demo's path)
+    with ONE ut_gen_crop_cameras_from_window_points launch.  cam_params [R,32] source camera rows; keypoints
+    [n,V,21,2] window px; src_row [n,V] row of cam_params (= of the source image stack) per view, -1 where the hand
+    is not seen, e.g. frame * n_cams + cam; hand_idx [n].  numpy arrays or tensors.  Returns device tensors with the
+    keys and row order of crop_plan_on_device: hands without a view are dropped, a candidate the reference would
+    raise on ("Unable to create crop camera") raises here as well."""
+    opts = opts or HandTrackerOpts()
+    dev = torch.device(device)
+    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
+    cam_params, hand_idx = t(cam_params).double(), t(hand_idx).long()
+    g = _native.gen_crop_cameras_from_window_points(cam_params, t(keypoints), t(src_row), hand_idx, crop_size=arch.CROP,
+                                                    focal_multiplier=opts.hand_ratio_in_crop)
+    if bool((g["status"] != 0).any()):
+        raise ValueError("Unable to create crop camera")
+    nv = g["n_views"].long()
+    keep = nv > 0
+    used = g["cam_index"] >= 0                                           # [n,V], view slots are filled front to back
+    ends = torch.cumsum(nv, 0)
+    return {"cam_params": cam_params, "crop_params": g["crop_params"][used], "src_index": g["cam_index"][used],
+            "intrinsics": g["intrinsics"][used], "extrinsics": g["extrinsics"][used],
+            "sample_range": torch.stack([ends - nv, ends], 1)[keep], "hand_idx": hand_idx[keep]}
+
+
 class DeviceCropPlanner:
     """Row f1 inside the step: the label poses of a frame block stay on the GPU and every call regenerates the
     crop cameras with one ut_gen_crop_cameras launch and no host round trip, like the reference's per-frame loop

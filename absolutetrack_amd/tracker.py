@@ -8,6 +8,7 @@ packing of kernel argument rows, dict bookkeeping.  The heavy steps run natively
   * the network                                        -> ut_backbone + ut_fuse_temporal_regress
 """
 import contextlib
+import ctypes
 import logging
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Tuple
@@ -129,6 +130,54 @@ def gen_crop_cameras_from_pose(cameras, camera_angles, hand_model, hand_pose, ha
         if len(out) == max_view_num:
             break
     return out
+
+
+def crop_camera_from_window_points(camera: CameraModel, window_hand_pose: np.ndarray, hand_idx: int, input_size,
+                                   hand_ratio_in_crop: float) -> PinholePlaneCameraModel:
+    """One (hand, camera) of HandTracker.gen_crop_cameras_from_stereo_camera_with_window_hand_pose
+    (lib/tracker/tracker.py:128-176): unproject the 21 window keypoints through the camera's own window_to_eye (for
+    Fisheye62 the radial-only five-step fixed point, lib/common/camera.py:146-181), aim a crop camera at their
+    bounding-box centre (camera angle 0, x-mirrored for hand 1) and fit its focal length to them.  Raises
+    ValueError("Unable to create crop camera", ...) where the reference does (lib/common/crop.py:25-26)."""
+    world_to_eye = np.linalg.inv(camera.camera_to_world_xf)
+    world = camera.eye_to_world(camera.window_to_eye(np.asarray(window_hand_pose)[:, :2]))
+    center = (world.min(axis=0) + world.max(axis=0)) / 2
+    new_world_to_eye = geometry.make_look_at_matrix(world_to_eye, center, 0)
+    if hand_idx == 1:
+        mirrorx = np.eye(4, dtype=np.float32)
+        mirrorx[0, 0] = -1
+        new_world_to_eye = mirrorx @ new_world_to_eye
+    fx_fy, cx_cy = geometry.gen_intrinsics_from_bounding_pts(geometry.transform3(new_world_to_eye, world),
+                                                             input_size[0], input_size[1])
+    return PinholePlaneCameraModel(width=input_size[0], height=input_size[1], f=hand_ratio_in_crop * fx_fy, c=cx_cy,
+                                   distort_coeffs=[], camera_to_world_xf=np.linalg.inv(new_world_to_eye))
+
+
+def gen_crop_cameras_from_window_points(camera_left: CameraModel, camera_right: CameraModel,
+                                        window_hand_pose_left: Dict[int, np.ndarray],
+                                        window_hand_pose_right: Dict[int, np.ndarray], input_size,
+                                        hand_ratio_in_crop: float) -> Dict[int, Dict[int, PinholePlaneCameraModel]]:
+    """Host path of gen_crop_cameras_from_stereo_camera_with_window_hand_pose (lib/tracker/tracker.py:111-219), any
+    camera model: the left dict's hands in insertion order with view key 0, then the right dict's views as key 1 (a
+    hand seen only on the right is appended)."""
+    out: Dict[int, Dict[int, PinholePlaneCameraModel]] = {}
+    for view, camera, hands in ((0, camera_left, window_hand_pose_left), (1, camera_right, window_hand_pose_right)):
+        for hand_idx, pose in hands.items():
+            cam = crop_camera_from_window_points(camera, pose, hand_idx, input_size, hand_ratio_in_crop)
+            out.setdefault(hand_idx, {})[view] = cam
+    return out
+
+
+def _crop_camera_from_row(row: np.ndarray, k: np.ndarray, ext: np.ndarray, size: int) -> PinholePlaneCameraModel:
+    """A crop camera as a crop-camera kernel returned it (crop_params row, K, world->eye in metres)."""
+    t = np.eye(4)
+    t[:3, :3] = row[4:13].reshape(3, 3)
+    t[:3, 3] = row[13:16]
+    cam = PinholePlaneCameraModel(width=size, height=size, f=(row[0], row[1]), c=(row[2], row[3]), distort_coeffs=[],
+                                  camera_to_world_xf=t)
+    # what _make_inputs needs of this camera, as the kernel computed it (row, K, world->eye in metres)
+    cam._ut_net = (row, k, ext)
+    return cam
 
 
 # ----------------------------------------------------------------------------- tracker.py
@@ -265,6 +314,7 @@ class HandTracker:
         self._valid_tracking_history = np.zeros(2, dtype=bool)
         self._remap_mode = _native.UT_REMAP_CV2_FIXED
         self._crop_stage: Optional[_Stage] = None       # staging of gen_crop_cameras (one upload, one read-back)
+        self._window_stage: Optional[_Stage] = None     # staging of gen_crop_cameras_from_stereo_camera_with_window_hand_pose
         self._frame_stage: Optional[_Stage] = None      # staging of track_frame
         self._frame_stage_key = None
         self._limits_dev = None                         # (joint_limits tensor identity, device copy)
@@ -365,18 +415,79 @@ class HandTracker:
             _landmark_memo.put(hand_model, hand_idx, pose.joint_angles, pose.wrist_xform, o["landmarks"][i])
             per_hand = {}
             for k in range(int(o["n_views"][i])):
-                row = o["crop"][i, k].copy()
-                t = np.eye(4)
-                t[:3, :3] = row[4:13].reshape(3, 3)
-                t[:3, 3] = row[13:16]
-                cam = PinholePlaneCameraModel(width=size, height=size, f=(row[0], row[1]), c=(row[2], row[3]),
-                                              distort_coeffs=[], camera_to_world_xf=t)
-                # what _make_inputs needs of this camera, as the kernel computed it (row, K, world->eye in metres)
-                cam._ut_net = (row, o["k"][i, k].copy(), o["ext"][i, k].copy())
-                per_hand[int(o["cam_index"][i, k])] = cam
+                per_hand[int(o["cam_index"][i, k])] = _crop_camera_from_row(
+                    o["crop"][i, k].copy(), o["k"][i, k].copy(), o["ext"][i, k].copy(), size)
             if per_hand and len(per_hand) >= min_num_crops:
                 crop_cameras[hand_idx] = per_hand
         return crop_cameras
+
+    def gen_crop_cameras_from_stereo_camera_with_window_hand_pose(
+            self, camera_left: CameraModel, camera_right: CameraModel, window_hand_pose_left: Dict[int, np.ndarray],
+            window_hand_pose_right: Dict[int, np.ndarray]) -> Dict[int, Dict[int, PinholePlaneCameraModel]]:
+        """Crop cameras from 2-D hand keypoints of a stereo pair (lib/tracker/tracker.py:111-219, the live demo's
+        path): window_hand_pose_* map a hand index to its 21 window keypoints [21, >=2] (only [:, :2] is read).
+        Returns {hand: {0: left crop camera, 1: right crop camera}} in the reference's key order.  Fisheye62 cameras
+        on a HIP device: every hand of both cameras in one ut_gen_crop_cameras_from_window_points launch (one staged
+        upload, one read-back); anything else runs the host path.  Raises ValueError("Unable to create crop
+        camera") where the reference raises."""
+        left, right = window_hand_pose_left or {}, window_hand_pose_right or {}
+        hands = list(left) + [h for h in right if h not in left]
+        if hands and self._device == "cuda" and self._window_cropgen_ok(camera_left, camera_right, left, right, hands):
+            return self._gen_crop_cameras_from_window_batched(camera_left, camera_right, left, right, hands)
+        return gen_crop_cameras_from_window_points(camera_left, camera_right, left, right, self._input_size,
+                                                   self._hand_ratio_in_crop)
+
+    def _window_cropgen_ok(self, camera_left, camera_right, left, right, hands) -> bool:
+        """The kernel's configuration: Fisheye62 cameras, square crops, hands 0 / 1, 21 keypoints per hand."""
+        return (self._input_size[0] == self._input_size[1] and len(hands) <= NUM_HANDS
+                and all(isinstance(c, geometry.Fisheye62CameraModel) for c in (camera_left, camera_right))
+                and all(h in (0, 1) for h in hands)
+                and all(np.ndim(p) == 2 and np.shape(p)[0] == 21 and np.shape(p)[1] >= 2
+                        for d in (left, right) for p in d.values()))
+
+    def _gen_crop_cameras_from_window_batched(self, camera_left, camera_right, left, right, hands):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        v = MAX_VIEW_NUM
+        st = self._window_stage
+        if st is None or st.dev != dev:
+            st = self._window_stage = _Stage(
+                dev, [("cam", np.float64, (2, 32)), ("kp", np.float64, (NUM_HANDS, v, 21, 2)),
+                      ("src_row", np.int32, (NUM_HANDS, v)), ("hand", np.int64, (NUM_HANDS,))],
+                [("crop", np.float64, (NUM_HANDS, v, 24)), ("k", np.float32, (NUM_HANDS, v, 9)),
+                 ("ext", np.float32, (NUM_HANDS, v, 16)), ("cam_index", np.int32, (NUM_HANDS, v)),
+                 ("n_views", np.int32, (NUM_HANDS,)), ("status", np.int32, (NUM_HANDS,))])
+        a = st.np_in
+        a["cam"][0] = geometry.pack_camera_model(camera_left)
+        a["cam"][1] = geometry.pack_camera_model(camera_right)
+        for i, h in enumerate(hands):
+            a["hand"][i] = h
+            for view, d in enumerate((left, right)):
+                if h in d:
+                    a["kp"][i, view] = np.asarray(d[h])[:, :2]
+                    a["src_row"][i, view] = view
+                else:
+                    a["src_row"][i, view] = -1
+        st.upload()
+        ti, to = st.t_in, st.t_out
+        n = len(hands)
+        lib = _native.load_library()
+        with torch.cuda.device(dev):
+            rc = lib.ut_gen_crop_cameras_from_window_points(
+                None, _native._ptr(ti["cam"]), 2, _native._ptr(ti["kp"]), _native._ptr(ti["src_row"]),
+                _native._ptr(ti["hand"]), n, v, int(self._input_size[0]), ctypes.c_double(self._hand_ratio_in_crop),
+                _native._ptr(to["crop"]), _native._ptr(to["k"]), _native._ptr(to["ext"]), _native._ptr(to["cam_index"]),
+                _native._ptr(to["n_views"]), _native._ptr(to["status"]), _native._stream(dev))
+        if rc != 0:
+            raise RuntimeError(f"ut_gen_crop_cameras_from_window_points failed ({rc}): {lib.ut_last_error(None).decode()}")
+        st.download()                                                         # one read-back
+        o = st.np_out
+        if (o["status"][:n] != 0).any():
+            raise ValueError("Unable to create crop camera")
+        size = int(self._input_size[0])
+        return {h: {int(o["cam_index"][i, k]): _crop_camera_from_row(o["crop"][i, k].copy(), o["k"][i, k].copy(),
+                                                                     o["ext"][i, k].copy(), size)
+                    for k in range(int(o["n_views"][i]))}
+                for i, h in enumerate(hands)}
 
     # ------------------------------------------------------------------ network inputs
     def _make_inputs(self, sample: InputFrame, hand_model_mm: Optional[HandModel], crop_cameras):
@@ -541,6 +652,14 @@ class HandTracker:
 
     def track_frame(self, sample: InputFrame, hand_model: HandModel, crop_cameras) -> TrackingResult:
         return self._run(sample, hand_model, crop_cameras, calibrate=False)
+
+    def track_frame_analysis(self, sample: InputFrame, hand_model: HandModel, crop_cameras,
+                             gt_tracking: Optional[Dict[int, SingleHandPose]]) -> TrackingResult:
+        """lib/tracker/tracker.py:416-604, the live demo's call: the body is track_frame's (the same warp with the
+        depth check, the same TrackingResult, the same validity-history update), so is this one.  gt_tracking is
+        accepted and ignored, as in the reference.  The reference also shows every crop with cv2.imshow /
+        cv2.waitKey(1); that GUI side effect is not reproduced (OpenCV's GUI is not a dependency here)."""
+        return self.track_frame(sample, hand_model, crop_cameras)
 
     def track_frame_and_calibrate_scale(self, sample: InputFrame, crop_cameras) -> TrackingResult:
         return self._run(sample, None, crop_cameras, calibrate=True)

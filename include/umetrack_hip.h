@@ -297,6 +297,33 @@ int ut_gen_crop_cameras(ut_handle h, const double* cam_params, const double* cam
                         int32_t* cam_index, int32_t* n_views, int32_t* status, float* landmarks,
                         void* stream);
 
+/* HandTracker.gen_crop_cameras_from_stereo_camera_with_window_hand_pose for a batch of hand candidates in one
+ * launch: the label-free crop placement of the live demo (lib/tracker/tracker.py:111-219, per (hand, camera)
+ * :128-176): window keypoints -> (w - c) / f -> the radial-only five-step fixed point of
+ * Fisheye62CameraModel.undistort (lib/common/camera.py:146-181) -> arctan unprojection (camera.py:88-94) ->
+ * eye_to_world -> bounding-box centre -> make_look_at_matrix(inv(camera_to_world), centre, 0)
+ * (lib/common/affine.py:47-76) -> x-mirror for hand_idx 1 -> gen_intrinsics_from_bounding_pts on the 21 points
+ * (lib/common/crop.py:15-28), f *= focal_multiplier, c = (crop_size - 1) / 2; plus the network camera inputs of
+ * lib/tracker/tracker.py:333-337.  fp64 throughout, as in the reference.
+ *  cam_params f64 [n_cam_rows,32]  Fisheye62 source cameras, rows as for ut_warp_crops
+ *  keypoints  f64 [n,max_views,21,2] window pixels
+ *  src_row    i32 [n,max_views]  row of cam_params per view, -1 = the hand is not seen in that view
+ *  hand_idx   i64 [n]            0 or 1 (1 = x-mirrored crop); 1 <= max_views <= 3
+ *  Outputs, as for ut_gen_crop_cameras (padded to max_views, view slots filled front to back in input order):
+ *  crop_params f64 [n,max_views,24], intrinsics f32 [n,max_views,3,3], extrinsics f32 [n,max_views,4,4]
+ *  (world->eye, translation in metres), cam_index i32 [n,max_views] (the src_row of the slot's view, -1 = unused),
+ *  n_views i32 [n], status i32 [n] (1 where the reference raises "Unable to create crop camera": a point with
+ *  z < 1e-4 or a focal below 5 before the multiplier, lib/common/crop.py:25-26).
+ *  src_row and hand_idx are read back and checked before the launch (one stream synchronisation): a row outside
+ *  [-1, n_cam_rows) or a hand other than 0 / 1 gives UT_E_INVALID and nothing is written.
+ *  Stateless: h may be NULL. */
+int ut_gen_crop_cameras_from_window_points(ut_handle h, const double* cam_params, int n_cam_rows,
+                                           const double* keypoints, const int32_t* src_row,
+                                           const int64_t* hand_idx, int n, int max_views, int crop_size,
+                                           double focal_multiplier, double* crop_params, float* intrinsics,
+                                           float* extrinsics, int32_t* cam_index, int32_t* n_views,
+                                           int32_t* status, void* stream);
+
 /* torch_data path, lib/batched_dataset/data_transform.py:147-212 (_gen_crop_matrices) for every
  * (frame, view) of a batch in one launch.
  *  orig_extrinsics f32 [n_frames*n_views,4,4] world->eye of the (pinhole) source cameras

@@ -1,0 +1,262 @@
+"""GPU tests of the label-free crop placement (ut_gen_crop_cameras_from_window_points; lib/tracker/tracker.py:111-219
+and :416-604, the reference's live demo path): the kernel against the goldens the reference's own method wrote
+(tests/golden/window_pose_rec00.npz), the demo's two per-frame calls through the drop-in `lib` against track_frame and
+the CPU oracle, the batched plan against the per-frame method and HotPath against the oracle, and the C entry's
+argument checks.
+
+Tolerances (realistic cases): the kernel runs the reference's fp64 chain; sin / cos / pow differ from the host's libm
+in the last bit and numpy's 3x3 products go through BLAS in another summation order; on these well-conditioned cases
+that leaves differences of a few ulps, far inside the 1e-9 bound.  Adversarial cases (the fixed point diverges) compare only the raise
+decision: their values are ill-conditioned."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from absolutetrack_amd import _native, geometry, pipeline, synth
+from oracle import checks, ref_fk, ref_model
+from window_pose_cases import label_keypoints, load_cases
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ANGLE_TOL_RAD, KEYPOINT_TOL_MM = 1e-4, 1e-3
+UT_E_INVALID = -1
+
+
+class _StubModel:
+    def to(self, device):
+        return self
+
+    def getInputImageSizes(self):
+        return (96, 96)
+
+
+@pytest.fixture(scope="module")
+def cases(golden_dir):
+    return load_cases(golden_dir)
+
+
+@pytest.fixture(scope="module")
+def labels():
+    return pipeline.load_labels()
+
+
+@pytest.fixture(scope="module")
+def hand_model(labels):
+    return pipeline.hand_model_from_labels(labels)
+
+
+def _oracle_hm(labels):
+    return {k[3:]: v for k, v in labels.items() if k.startswith("hm.")}
+
+
+def _call(trk, case):
+    return trk.gen_crop_cameras_from_stereo_camera_with_window_hand_pose(
+        camera_left=case["cams"][0], camera_right=case["cams"][1], window_hand_pose_left=case["left"],
+        window_hand_pose_right=case["right"])
+
+
+def test_kernel_matches_reference_goldens(cases):
+    from lib.tracker.tracker import HandTracker, HandTrackerOpts
+    trk = HandTracker(_StubModel(), HandTrackerOpts())
+    assert trk._device == "cuda"
+    n = 0
+    for case in (c for c in cases if c["real"]):
+        got = _call(trk, case)
+        assert list(got) == list(case["expected"])
+        for h, per_hand in case["expected"].items():
+            assert list(got[h]) == list(per_hand)
+            for v, (f, c, T) in per_hand.items():
+                cam = got[h][v]
+                assert hasattr(cam, "_ut_net")                       # the kernel's path, not the host fallback
+                np.testing.assert_allclose(cam.f, f, rtol=1e-9, atol=0)
+                assert tuple(cam.c) == tuple(c)
+                np.testing.assert_allclose(cam.camera_to_world_xf[:3, :3], T[:3, :3], rtol=0, atol=1e-9)
+                np.testing.assert_allclose(cam.camera_to_world_xf[:3, 3], T[:3, 3], rtol=1e-9, atol=0)
+                # the network inputs the kernel emitted are the host formulas' on its own camera
+                from absolutetrack_amd.tracker import network_camera_inputs
+                k, ext = network_camera_inputs(cam)
+                np.testing.assert_allclose(cam._ut_net[1].reshape(3, 3), k, rtol=1e-7)
+                np.testing.assert_allclose(cam._ut_net[2].reshape(4, 4), ext, rtol=1e-6, atol=1e-7)
+                n += 1
+    assert n > 100
+
+
+def test_kernel_raises_exactly_where_the_reference_raises(cases):
+    from lib.tracker.tracker import HandTracker, HandTrackerOpts
+    trk = HandTracker(_StubModel(), HandTrackerOpts())
+    adv = [c for c in cases if not c["real"]]
+    for case in adv:
+        if case["raises"]:
+            with pytest.raises(ValueError, match="Unable to create crop camera"):
+                _call(trk, case)
+        else:
+            got = _call(trk, case)
+            assert list(got) == list(case["expected"])
+            assert all(list(got[h]) == list(case["expected"][h]) for h in got)
+
+
+def _demo_frames(labels, hm_np, frame_ids, pair, seed):
+    """Per frame: (left camera, right camera, left dict, right dict) like MediaPipe feeds the demo."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for fi in frame_ids:
+        cams = pipeline.cameras_for_frame(labels, fi)
+        d = [{}, {}]
+        for h in (0, 1):
+            for v, ci in enumerate(pair):
+                kp = label_keypoints(labels, hm_np, fi, h, cams[ci], rng)
+                if kp is not None:
+                    d[v][h] = kp
+        out.append((cams[pair[0]], cams[pair[1]], d[0], d[1]))
+    return out
+
+
+def test_demo_flow_equals_track_frame_and_the_oracle(labels, hand_model):
+    """demo/ume_tracker.py:157-188 through the drop-in `lib`: a two-view InputFrame (left = view 0, right = view 1,
+    camera_angle 0), keypoint dicts keyed by hand, then track_frame_analysis(..., None).  Five consecutive frames with
+    the temporal memory engaged, one with a hand missing, one without hands."""
+    from lib.models.umetrack_model import UmeTrackModel
+    from lib.tracker.tracker import HandTracker, HandTrackerOpts, InputFrame, ViewData
+    sd = synth.synthetic_state_dict(0)
+    demo = HandTracker(UmeTrackModel(sd), HandTrackerOpts())
+    plain = HandTracker(UmeTrackModel(sd), HandTrackerOpts())
+    om = ref_model.OracleModel(sd)
+    hm_np = _oracle_hm(labels)
+    imgs = synth.synthetic_frames(5, seed=21)
+    frames = _demo_frames(labels, hm_np, range(200, 205), (1, 2), seed=3)
+    for step, (cam_l, cam_r, left, right) in enumerate(frames):
+        if step == 3:                                   # hand 1 not detected in this frame
+            left, right = {h: v for h, v in left.items() if h != 1}, {h: v for h, v in right.items() if h != 1}
+        if step == 4:                                   # no hands
+            left, right = {}, {}
+        sample = InputFrame(views=[ViewData(image=imgs[step, 1].copy(), camera=cam_l, camera_angle=0),
+                                   ViewData(image=imgs[step, 2].copy(), camera=cam_r, camera_angle=0)])
+        crop_cameras = demo.gen_crop_cameras_from_stereo_camera_with_window_hand_pose(
+            camera_left=cam_l, camera_right=cam_r, window_hand_pose_left=left, window_hand_pose_right=right)
+        if step < 3:
+            assert list(crop_cameras) == [0, 1] and all(list(v) == [0, 1] for v in crop_cameras.values())
+        fd = desc = skel = None
+        if crop_cameras:
+            fd, desc, skel = demo._make_inputs(sample, hand_model, crop_cameras)
+        res = demo.track_frame_analysis(sample, hand_model, crop_cameras, None)
+        ref = plain.track_frame(sample, hand_model, crop_cameras)
+        assert list(res.hand_poses) == list(ref.hand_poses) and res.num_views == ref.num_views
+        assert res.predicted_scales == ref.predicted_scales == {}
+        for h in res.hand_poses:
+            assert np.array_equal(res.hand_poses[h].joint_angles, ref.hand_poses[h].joint_angles)
+            assert np.array_equal(res.hand_poses[h].wrist_xform, ref.hand_poses[h].wrist_xform)
+        assert np.array_equal(demo._valid_tracking_history, plain._valid_tracking_history)
+        if not crop_cameras:
+            assert res.hand_poses == {} and not demo._valid_tracking_history.any()
+            continue
+        o = om.forward(fd.left_images.cpu(), fd.intrinsics.cpu(), fd.extrinsics_xf.cpu(), desc.sample_range.cpu(),
+                       desc.memory_idx.cpu(), desc.use_memory.cpu(), desc.hand_idx.cpu(),
+                       skel.joint_rotation_axes.cpu(), skel.joint_rest_positions.cpu(), True)
+        for i, h in enumerate(desc.hand_idx.tolist()):
+            pose = res.hand_poses[h]
+            assert np.abs(pose.joint_angles - o["joint_angles"][i].numpy()).max() < ANGLE_TOL_RAD
+            want_xf = o["wrist_xfs"][i].numpy().copy()
+            want_xf[:3, 3] *= 1000.0
+            assert np.abs(pose.wrist_xform[:3, 3] - want_xf[:3, 3]).max() < KEYPOINT_TOL_MM
+            xf = want_xf.copy()
+            if h == 1:
+                xf[:, 0] *= -1
+            mine = pose.wrist_xform.copy()
+            if h == 1:
+                mine[:, 0] *= -1
+            got_kp = ref_fk.skin_landmarks(hm_np, pose.joint_angles, mine)
+            want_kp = ref_fk.skin_landmarks(hm_np, o["joint_angles"][i].numpy(), xf)
+            assert np.abs(got_kp - want_kp).max() < KEYPOINT_TOL_MM
+
+
+def _window_candidates(labels, frame_ids, pair=(0, 1), seed=5):
+    """Flat keypoint candidates of the label frames (rows frame * 4 + camera of the label camera stack)."""
+    hm_np = _oracle_hm(labels)
+    frames = _demo_frames(labels, hm_np, frame_ids, pair, seed)
+    n_cams = labels["cameras"].shape[0]
+    c = pipeline.label_candidates(labels, frame_ids)
+    kps, rows, hands = [], [], []
+    for fo, (_, _, left, right) in enumerate(frames):
+        order = list(left) + [h for h in right if h not in left]
+        for h in order:
+            kp = np.zeros((2, 21, 2))
+            row = [-1, -1]
+            for v, d in enumerate((left, right)):
+                if h in d:
+                    kp[v] = d[h]
+                    row[v] = fo * n_cams + pair[v]
+            kps.append(kp)
+            rows.append(row)
+            hands.append(h)
+    return (c["cam_params"], np.stack(kps), np.asarray(rows, np.int32), np.asarray(hands, np.int64), frames)
+
+
+def test_batched_plan_equals_the_per_frame_method(labels):
+    from lib.tracker.tracker import HandTracker, HandTrackerOpts
+    frame_ids = list(range(labels["joint_angles"].shape[0]))
+    cam_params, kp, rows, hands, frames = _window_candidates(labels, frame_ids)
+    assert len(hands) == 738
+    plan = pipeline.crop_plan_from_window_points(cam_params, kp, rows, hands, DEV)
+    plan = {k: v.cpu().numpy() for k, v in plan.items()}
+    trk = HandTracker(_StubModel(), HandTrackerOpts())
+    n = s = 0
+    for fo, (cam_l, cam_r, left, right) in enumerate(frames):
+        cc = trk.gen_crop_cameras_from_stereo_camera_with_window_hand_pose(cam_l, cam_r, left, right)
+        for h, per_hand in cc.items():
+            assert plan["hand_idx"][s] == h and tuple(plan["sample_range"][s]) == (n, n + len(per_hand))
+            s += 1
+            for v, cam in per_hand.items():
+                assert np.array_equal(plan["crop_params"][n], geometry.pack_crop_camera(cam.f, cam.c,
+                                                                                        cam.camera_to_world_xf))
+                assert plan["src_index"][n] == fo * 4 + (0, 1)[v]
+                assert np.array_equal(plan["intrinsics"][n], cam._ut_net[1].reshape(3, 3))
+                assert np.array_equal(plan["extrinsics"][n], cam._ut_net[2].reshape(4, 4))
+                n += 1
+    assert n == plan["crop_params"].shape[0] and s == 738
+    assert plan["sample_range"].shape == (738, 2)
+
+
+@pytest.mark.parametrize("conv", ["fp32", "split_f16"])
+def test_hot_path_on_a_keypoint_plan_matches_the_oracle(labels, conv):
+    torch.set_num_threads(min(torch.get_num_threads(), 16))
+    sd = synth.synthetic_state_dict(0)
+    frame_ids = list(range(40, 56))
+    cam_params, kp, rows, hands, _ = _window_candidates(labels, frame_ids)
+    plan = pipeline.crop_plan_from_window_points(cam_params, kp, rows, hands, DEV)
+    plan = {k: v.cpu().numpy() for k, v in plan.items()}
+    imgs = synth.synthetic_frames(len(frame_ids), seed=7)
+    rec, crops = checks._gpu_records(sd, plan, imgs, DEV, conv, _native.UT_REMAP_CV2_FIXED)
+    ref = checks.oracle_frames(sd, labels, _oracle_hm(labels), frame_ids, imgs, True, plan=plan)
+    assert rec.shape[0] == plan["sample_range"].shape[0] == 32
+    assert np.array_equal(crops, ref["crops"])
+    assert np.abs(rec[:, :22] - ref["joint_angles"]).max() < ANGLE_TOL_RAD
+    assert np.abs(rec[:, 60:].reshape(-1, 21, 3) - ref["keypoints_mm"]).max() < KEYPOINT_TOL_MM
+
+
+def test_c_entry_rejects_bad_arguments_and_writes_nothing():
+    lib = _native.load_library()
+    p = _native._ptr
+    cam = torch.zeros(2, 32, dtype=torch.float64, device=DEV)
+    kp = torch.zeros(1, 2, 21, 2, dtype=torch.float64, device=DEV)
+    out = {"crop": torch.full((1, 2, 24), 7.0, dtype=torch.float64, device=DEV),
+           "k": torch.full((1, 2, 9), 7.0, device=DEV), "ext": torch.full((1, 2, 16), 7.0, device=DEV),
+           "ci": torch.full((1, 2), 7, dtype=torch.int32, device=DEV), "nv": torch.full((1,), 7, dtype=torch.int32, device=DEV),
+           "st": torch.full((1,), 7, dtype=torch.int32, device=DEV)}
+
+    def call(rows, hand, kp_ptr=None):
+        r = torch.tensor(rows, dtype=torch.int32, device=DEV).reshape(1, 2)
+        h = torch.tensor([hand], dtype=torch.int64, device=DEV)
+        rc = lib.ut_gen_crop_cameras_from_window_points(
+            None, p(cam), 2, p(kp) if kp_ptr is None else kp_ptr, p(r), p(h), 1, 2, 96, ctypes.c_double(0.8),
+            p(out["crop"]), p(out["k"]), p(out["ext"]), p(out["ci"]), p(out["nv"]), p(out["st"]), _native._stream(DEV))
+        torch.cuda.synchronize()
+        return rc, lib.ut_last_error(None).decode()
+
+    for rows, hand, kp_ptr in (([0, 2], 0, None), ([-2, 0], 0, None), ([0, 1], 2, None), ([0, 1], -1, None),
+                               ([0, 1], 0, 0)):
+        rc, msg = call(rows, hand, kp_ptr)
+        assert rc == UT_E_INVALID and "ut_gen_crop_cameras_from_window_points" in msg, (rows, hand, rc, msg)
+        for k, t in out.items():
+            assert bool((t == 7).all()), k
