@@ -8,8 +8,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ut_kernels.h"
@@ -69,17 +71,17 @@ struct ut_context {
   // layer4, projection) runs over up to PHASE_B_MAX crops at once so that the small late maps still fill the
   // chip with workgroups.
   int chunk = kDefaultChunk;
-  int ws_crops = 0;       // phase-A capacity (crops)
+  size_t ws_crops = 0;    // phase-A capacity (crops)
   float *bufX = nullptr, *bufH = nullptr, *bufY = nullptr, *bufD = nullptr;
   // fused resample -> backbone: the crops between the two kernels (u8 grey levels, or fp32 in UT_REMAP_FLOAT mode)
-  size_t crops_ws_bytes = 0;
-  void* crops_ws = nullptr;
-  int wsb_crops = 0;      // phase-B capacity (crops)
+  size_t crops_ws_floats = 0;
+  float* crops_ws = nullptr;
+  size_t wsb_crops = 0;   // phase-B capacity (crops)
   float *bufL2 = nullptr, *bufP = nullptr, *bufQ = nullptr, *bufBH = nullptr, *bufBD = nullptr;
   // head workspace
-  int ws_samples = 0;
+  size_t ws_samples = 0;
   ut::HeadBuffers hb{};
-  int ws_skel = 0;
+  size_t ws_skel = 0;
   // temporal state
   int slots_cap = 0, slots_used = 0;
   float *mem = nullptr, *prev_ext = nullptr;
@@ -204,13 +206,18 @@ const char* status_message(int bits) {
   return "index check: failed";
 }
 
-// Read the status words back (synchronises the stream), clear the sticky word when it holds an error.
-int read_status(ut_handle h, int* dev, int* host, hipStream_t s, int* sticky, int* call) {
+// Read the status words back into `host` (synchronises the stream) and fail with "<what>: <message>" when the sticky word
+// holds an error; a non-zero sticky word is cleared.  host[1] keeps the per-call word for the caller.
+int check_status(ut_handle h, int* dev, int* host, hipStream_t s, const char* what) {
   HIPCHK(h, hipMemcpyAsync(host, dev, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  *sticky = host[0];
-  *call = host[1];
-  if (*sticky) HIPCHK(h, hipMemsetAsync(dev, 0, sizeof(int), s));
+  const int sticky = host[0];
+  if (sticky) HIPCHK(h, hipMemsetAsync(dev, 0, sizeof(int), s));
+  if (sticky & ut::UT_STATUS_ERRORS) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", what, status_message(sticky));
+    return fail(h, UT_E_INVALID, buf);
+  }
   return UT_OK;
 }
 
@@ -534,63 +541,39 @@ void dev_free(ut_handle h, void* p) {
   (void)hipFree(p);
 }
 
-int ensure_backbone_ws(ut_handle h, int crops) {
-  if (crops <= h->ws_crops) return UT_OK;
+// Regrow a set of workspace buffers to n units each (`bufs`: a buffer and its floats per unit) when *cap < n.  Launches in
+// flight may still use the old buffers, hence the synchronise; *cap stays 0 until every allocation has succeeded.
+int regrow(ut_handle h, size_t* cap, size_t n, std::initializer_list<std::pair<float**, size_t>> bufs) {
+  if (n <= *cap) return UT_OK;
   HIPCHK(h, hipDeviceSynchronize());
-  dev_free(h, h->bufX); dev_free(h, h->bufH); dev_free(h, h->bufY); dev_free(h, h->bufD);
-  h->bufX = h->bufH = h->bufY = h->bufD = nullptr;
-  h->ws_crops = 0;
-  const size_t big = (size_t)crops * 48 * 48 * 32, small = (size_t)crops * 24 * 24 * 64;
+  for (auto& b : bufs) { dev_free(h, *b.first); *b.first = nullptr; }
+  *cap = 0;
   int rc;
-  if ((rc = dev_alloc(h, &h->bufX, big)) || (rc = dev_alloc(h, &h->bufH, big)) ||
-      (rc = dev_alloc(h, &h->bufY, big)) || (rc = dev_alloc(h, &h->bufD, small)))
-    return rc;
-  h->ws_crops = crops;
+  for (auto& b : bufs)
+    if ((rc = dev_alloc(h, b.first, n * b.second))) return rc;
+  *cap = n;
   return UT_OK;
+}
+
+int ensure_backbone_ws(ut_handle h, int crops) {
+  const size_t big = 48 * 48 * 32, small = 24 * 24 * 64;
+  return regrow(h, &h->ws_crops, crops, {{&h->bufX, big}, {&h->bufH, big}, {&h->bufY, big}, {&h->bufD, small}});
 }
 
 constexpr int PHASE_B_MAX = 8192;    // its input, the 24x24x64 map (147 KB per crop), must stay under 2^31 bytes: < 14563 crops
 
 int ensure_phase_b_ws(ut_handle h, int crops) {
-  if (crops <= h->wsb_crops) return UT_OK;
-  HIPCHK(h, hipDeviceSynchronize());
-  float** ptrs[] = {&h->bufL2, &h->bufP, &h->bufQ, &h->bufBH, &h->bufBD};
-  for (auto pp : ptrs) { dev_free(h, *pp); *pp = nullptr; }
-  h->wsb_crops = 0;
-  const size_t l2 = (size_t)crops * 24 * 24 * 64, l3 = (size_t)crops * 12 * 12 * 128;
-  int rc;
-  if ((rc = dev_alloc(h, &h->bufL2, l2)) || (rc = dev_alloc(h, &h->bufP, l3)) || (rc = dev_alloc(h, &h->bufQ, l3)) ||
-      (rc = dev_alloc(h, &h->bufBH, l3)) || (rc = dev_alloc(h, &h->bufBD, l3)))
-    return rc;
-  h->wsb_crops = crops;
-  return UT_OK;
+  const size_t l2 = 24 * 24 * 64, l3 = 12 * 12 * 128;
+  return regrow(h, &h->wsb_crops, crops, {{&h->bufL2, l2}, {&h->bufP, l3}, {&h->bufQ, l3}, {&h->bufBH, l3}, {&h->bufBD, l3}});
 }
 
 int ensure_head_ws(ut_handle h, int samples, int n_skel) {
-  int rc;
-  if (samples > h->ws_samples) {
-    HIPCHK(h, hipDeviceSynchronize());
-    float** ptrs[] = {&h->hb.cat144, &h->hb.f108, &h->hb.f72a, &h->hb.f72b, &h->hb.fused, &h->hb.t92a,
-                      &h->hb.t92b, &h->hb.regin, &h->hb.rega, &h->hb.regb};
-    const int ch[] = {144, 108, 72, 72, 72, 92, 92, kRegSplitCh, kRegSplitCh, kRegSplitCh};
-    for (int i = 0; i < 10; ++i) {
-      dev_free(h, *ptrs[i]);
-      *ptrs[i] = nullptr;
-    }
-    h->ws_samples = 0;
-    for (int i = 0; i < 10; ++i)
-      if ((rc = dev_alloc(h, ptrs[i], (size_t)samples * 36 * ch[i]))) return rc;
-    h->ws_samples = samples;
-  }
-  if (n_skel > h->ws_skel) {
-    HIPCHK(h, hipDeviceSynchronize());
-    dev_free(h, h->hb.skel);
-    h->hb.skel = nullptr;
-    h->ws_skel = 0;
-    if ((rc = dev_alloc(h, &h->hb.skel, (size_t)n_skel * 36 * 4))) return rc;
-    h->ws_skel = n_skel;
-  }
-  return UT_OK;
+  ut::HeadBuffers& b = h->hb;
+  const size_t r = 36 * kRegSplitCh;
+  int rc = regrow(h, &h->ws_samples, samples, {{&b.cat144, 36 * 144}, {&b.f108, 36 * 108}, {&b.f72a, 36 * 72}, {&b.f72b, 36 * 72},
+                                                {&b.fused, 36 * 72}, {&b.t92a, 36 * 92}, {&b.t92b, 36 * 92}, {&b.regin, r},
+                                                {&b.rega, r}, {&b.regb, r}});
+  return rc ? rc : regrow(h, &h->ws_skel, n_skel, {{&b.skel, 36 * 4}});
 }
 
 int ensure_slots(ut_handle h, int slots, hipStream_t s) {
@@ -629,12 +612,15 @@ int begin_call(ut_handle h, hipStream_t s) {
   return UT_OK;
 }
 
-// the next launch's index into the per-launch words
-int next_launch_word(ut_handle h, hipStream_t s, int* idx) {
-  if (h->counter_next >= kMaxCounters) {   // recycle: stream order puts the memset behind the earlier launches
+// the next launch's index into the per-launch words; *recycled (optional): taking it zeroed the words, so every max word an
+// earlier launch of the call left is stale
+int next_launch_word(ut_handle h, hipStream_t s, int* idx, bool* recycled = nullptr) {
+  const bool full = h->counter_next >= kMaxCounters;
+  if (full) {   // recycle: stream order puts the memset behind the earlier launches
     int rc0 = begin_call(h, s);
     if (rc0) return rc0;
   }
+  if (recycled) *recycled = full;
   *idx = h->counter_next++;
   return UT_OK;
 }
@@ -650,9 +636,25 @@ ScaleRef scale_for(ut_handle h, int tid, const unsigned* producer_word) {
   else { r.word = h->calib + tid; r.obs = producer_word; }
   return r;
 }
-// calibration pass: fold the producer's word of tensor `tid` into its calibrated word
-int note_calibration(ut_handle h, int tid, const unsigned* producer_word, hipStream_t s) {
-  if (h->calibrating && producer_word && tid >= 0 && tid < kScaleTensors) HIPCHK(h, ut::launch_merge_max(h->calib + tid, producer_word, s));
+// One convolution launch (`launch()` enqueues kernel `what`).  A calibration pass first folds the producer's word of the
+// input tensor `in_tid` into its calibrated word; while the handle profiles, two events time the launch, kept with its flops
+// and kind (ProfEvent).  (A calibration pass never profiles: calibrate_split turns profiling off.)
+template <class Launch>
+int bracket_launch(ut_handle h, hipStream_t s, int in_tid, const unsigned* in_max, double flops, int kind, const char* what,
+                   Launch launch) {
+  if (h->calibrating && in_max && in_tid >= 0 && in_tid < kScaleTensors) HIPCHK(h, ut::launch_merge_max(h->calib + in_tid, in_max, s));
+  ProfEvent pe{nullptr, nullptr, flops, kind};
+  if (h->profiling) {
+    HIPCHK(h, hipEventCreateWithFlags(&pe.a, hipEventDisableSystemFence));   // timing only: no system-scope flush per kernel
+    HIPCHK(h, hipEventCreateWithFlags(&pe.b, hipEventDisableSystemFence));
+    HIPCHK(h, hipEventRecord(pe.a, s));
+  }
+  const hipError_t e = launch();
+  if (e != hipSuccess) return fail(h, UT_E_HIP, what, e);
+  if (h->profiling) {
+    HIPCHK(h, hipEventRecord(pe.b, s));
+    h->prof.push_back(pe);
+  }
   return UT_OK;
 }
 
@@ -673,12 +675,10 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
   c.relu = relu; c.out_nchw = nchw;
   c.device = h->device; c.num_cu = h->num_cu; { static const int kMask[7] = {15, 0, 14, 9, 12, 13, 8}; c.no_resident = kMask[h->resident_weights]; }      // (ut_kernels.h::ConvLaunch::no_resident)
   int word = 0;
-  {
-    const unsigned gen = h->word_gen;
-    int rc0 = next_launch_word(h, s, &word);
-    if (rc0) return rc0;
-    if (gen != h->word_gen) in_max = nullptr;      // recycled in mid-call: the producer's word has just been zeroed
-  }
+  bool recycled = false;
+  int rc = next_launch_word(h, s, &word, &recycled);
+  if (rc) return rc;
+  if (recycled) in_max = nullptr;      // recycled in mid-call: the producer's word has just been zeroed
   c.tile_counter = h->counters + word;
   // Latency mode: a convolution of a few crops has far fewer 64x64 tiles than the chip has CUs and every workgroup
   // walks all of K alone (a layer-4 conv of 4 crops: 12 tiles x 72 chunks).  Cut K into S equal chunk ranges (S the
@@ -702,13 +702,6 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
                                        relu ? 1 : 0, s));
     return UT_OK;
   }
-  ProfEvent pe{};
-  if (h->profiling) {
-    HIPCHK(h, hipEventCreateWithFlags(&pe.a, hipEventDisableSystemFence));   // timing only: no system-scope flush per kernel
-    HIPCHK(h, hipEventCreateWithFlags(&pe.b, hipEventDisableSystemFence));
-    pe.flops = cw.flops_per_pixel * (double)n_img * c.Ho * c.Wo;
-    HIPCHK(h, hipEventRecord(pe.a, s));
-  }
   // split-fp16 arithmetic: decided once per backbone call (run_backbone), for every eligible layer of the call whose
   // producer left a max word; everything else - the head, and every launch in latency mode - stays on the fp32 instruction
   const ScaleRef sr = scale_for(h, in_tid, in_max);
@@ -717,20 +710,15 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
   c.status = h->status;
   c.in_max = sr.word;
   c.in_obs = sr.obs;
-  pe.kind = c.w_split && (ut::conv_split_applicable(c) || ut::conv_patch_applicable(c)) ? 1 : 0;
-  if (pe.kind) {
+  const int kind = c.w_split && (ut::conv_split_applicable(c) || ut::conv_patch_applicable(c)) ? 1 : 0;
+  if (kind) {
     c.out_max = h->counters + kMaxCounters + word;
     if (out_max) *out_max = c.out_max;
-    int rc1 = note_calibration(h, in_tid, in_max, s);
-    if (rc1) return rc1;
   }
-  if (c.w_split && ut::conv_split_applicable(c)) HIPCHK(h, ut::launch_conv_split(c, s));
-  else HIPCHK(h, ut::launch_conv_igemm(c, s));
-  if (h->profiling) {
-    HIPCHK(h, hipEventRecord(pe.b, s));
-    h->prof.push_back(pe);
-  }
-  return UT_OK;
+  const bool split = c.w_split && ut::conv_split_applicable(c);
+  return bracket_launch(h, s, kind ? in_tid : -1, in_max, cw.flops_per_pixel * (double)n_img * c.Ho * c.Wo, kind,
+                        split ? "launch_conv_split" : "launch_conv_igemm",
+                        [&] { return split ? ut::launch_conv_split(c, s) : ut::launch_conv_igemm(c, s); });
 }
 
 // relu(bn2(conv2(relu(bn1(conv1 x)))) + (downsample(x) | x))   lib/models/backbone_resnet.py:56-72
@@ -758,26 +746,15 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
     bl.in_max = xs.word; bl.in_obs = xs.obs; bl.status = h->status;
     bl.n_img = n_img; bl.H = H; bl.W = W; bl.device = h->device; bl.num_cu = h->num_cu;
     if (ut::conv_block32_applicable((bl.tile_counter = h->counters, bl))) {
-      const unsigned gen = h->word_gen;
       int word = 0;
-      if ((rc = next_launch_word(h, s, &word))) return rc;
-      if (gen == h->word_gen) {          // (never a recycle here: the block's words were reserved above)
-        if ((rc = note_calibration(h, x_tid, x_max, s))) return rc;
+      bool recycled = false;
+      if ((rc = next_launch_word(h, s, &word, &recycled))) return rc;
+      if (!recycled) {          // (never a recycle here: the block's words were reserved above)
         bl.tile_counter = h->counters + word;
         bl.out_max = h->counters + kMaxCounters + word;
-        ProfEvent pe{};
-        if (h->profiling) {
-          HIPCHK(h, hipEventCreateWithFlags(&pe.a, hipEventDisableSystemFence));
-          HIPCHK(h, hipEventCreateWithFlags(&pe.b, hipEventDisableSystemFence));
-          pe.flops = (b.conv1.flops_per_pixel + b.conv2.flops_per_pixel) * (double)n_img * H * W;
-          pe.kind = 1;
-          HIPCHK(h, hipEventRecord(pe.a, s));
-        }
-        HIPCHK(h, ut::launch_conv_block32(bl, s));
-        if (h->profiling) {
-          HIPCHK(h, hipEventRecord(pe.b, s));
-          h->prof.push_back(pe);
-        }
+        const double flops = (b.conv1.flops_per_pixel + b.conv2.flops_per_pixel) * (double)n_img * H * W;
+        if ((rc = bracket_launch(h, s, x_tid, x_max, flops, 1, "launch_conv_block32", [&] { return ut::launch_conv_block32(bl, s); })))
+          return rc;
         if (y_max) *y_max = bl.out_max;
         return UT_OK;
       }
@@ -793,25 +770,14 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
     sl.in_max = xs.word; sl.in_obs = xs.obs; sl.status = h->status;
     sl.n_img = n_img; sl.H = H; sl.W = W; sl.device = h->device; sl.num_cu = h->num_cu;
     if (ut::conv_c32s2_applicable(sl)) {
-      const unsigned gen = h->word_gen;
       int word = 0;
-      if ((rc = next_launch_word(h, s, &word))) return rc;
-      if (gen == h->word_gen) {
-        if ((rc = note_calibration(h, x_tid, x_max, s))) return rc;
+      bool recycled = false;
+      if ((rc = next_launch_word(h, s, &word, &recycled))) return rc;
+      if (!recycled) {
         sl.out1_max = h->counters + kMaxCounters + word;
-        ProfEvent pe{};
-        if (h->profiling) {
-          HIPCHK(h, hipEventCreateWithFlags(&pe.a, hipEventDisableSystemFence));
-          HIPCHK(h, hipEventCreateWithFlags(&pe.b, hipEventDisableSystemFence));
-          pe.flops = (b.conv1.flops_per_pixel + b.ds.flops_per_pixel) * (double)n_img * (H / 2) * (W / 2);
-          pe.kind = 1;
-          HIPCHK(h, hipEventRecord(pe.a, s));
-        }
-        HIPCHK(h, ut::launch_conv_c32s2(sl, s));
-        if (h->profiling) {
-          HIPCHK(h, hipEventRecord(pe.b, s));
-          h->prof.push_back(pe);
-        }
+        const double flops = (b.conv1.flops_per_pixel + b.ds.flops_per_pixel) * (double)n_img * (H / 2) * (W / 2);
+        if ((rc = bracket_launch(h, s, x_tid, x_max, flops, 1, "launch_conv_c32s2", [&] { return ut::launch_conv_c32s2(sl, s); })))
+          return rc;
         return run_conv(h, b.conv2, tmp, dsbuf, y, n_img, H / 2, W / 2, true, false, s, sl.out1_max, y_max, mid_tid);
       }
     }
@@ -825,6 +791,27 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
     res = dsbuf;
   }
   return run_conv(h, b.conv2, tmp, res, y, n_img, Ho, Wo, true, false, s, tmp_max, y_max, mid_tid);
+}
+
+// destroy the timing events of the launches profiled so far (the handle's device must be current)
+void prof_clear(ut_handle h) {
+  for (auto& pe : h->prof) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
+  h->prof.clear();
+}
+
+// end profiling: per kind (ProfEvent::kind), the summed times, launch counts and flops of the launches since ut_profile_begin
+int prof_reduce(ut_handle h, hipStream_t s, double ms[2], int64_t launches[2], double flops[2]) {
+  h->profiling = false;
+  HIPCHK(h, hipStreamSynchronize(s));
+  for (int k = 0; k < 2; ++k) { ms[k] = 0; launches[k] = 0; flops[k] = 0; }
+  for (auto& pe : h->prof) {
+    float t = 0;
+    HIPCHK(h, hipEventElapsedTime(&t, pe.a, pe.b));
+    const int k = pe.kind ? 1 : 0;
+    ms[k] += t; flops[k] += pe.flops; launches[k] += 1;
+  }
+  prof_clear(h);
+  return UT_OK;
 }
 
 }  // namespace
@@ -940,7 +927,7 @@ int ut_destroy(ut_handle h) {
     if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
   }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  for (auto& pe : h->prof) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
+  prof_clear(h);
   delete h;
   return UT_OK;
 }
@@ -962,15 +949,7 @@ int ut_reserve(ut_handle h, int max_crops, int max_samples, int max_slots) {
   if (cb > 0 && (rc = ensure_phase_b_ws(h, cb))) return rc;
   if (max_samples > 0 && (rc = ensure_head_ws(h, max_samples, max_samples))) return rc;
   if (max_slots > 0 && (rc = ensure_slots(h, max_slots, 0))) return rc;
-  const size_t crops_need = (size_t)(max_crops > 0 ? max_crops : 0) * 96 * 96 * sizeof(float);
-  if (crops_need > h->crops_ws_bytes) {
-    HIPCHK(h, hipDeviceSynchronize());
-    dev_free(h, h->crops_ws);
-    h->crops_ws = nullptr; h->crops_ws_bytes = 0;
-    float* pnew = nullptr;
-    if ((rc = dev_alloc(h, &pnew, crops_need / 4))) return rc;
-    h->crops_ws = pnew; h->crops_ws_bytes = crops_need;
-  }
+  if (max_crops > 0 && (rc = regrow(h, &h->crops_ws_floats, (size_t)max_crops * 96 * 96, {{&h->crops_ws, 1}}))) return rc;
   return UT_OK;
 }
 
@@ -995,16 +974,7 @@ int ut_warp_crops(ut_handle h, const uint8_t* src, int n_src_images, int src_h, 
   if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
   HIPCHK(h, ut::launch_warp(src, n_src_images, src_h, src_w, cam_params, crop_params, src_index, n_crops, remap_mode,
                             out, nullptr, st_dev, s));
-  if (mode == UT_CHECK_SYNC) {
-    int sticky = 0, call = 0, rc = read_status(h, st_dev, st_host, s, &sticky, &call);
-    if (rc) return rc;
-    if (sticky & ut::UT_STATUS_ERRORS) {
-      char buf[256];
-      snprintf(buf, sizeof buf, "ut_warp_crops: %s", status_message(sticky));
-      return fail(h, UT_E_INVALID, buf);
-    }
-  }
-  return UT_OK;
+  return mode == UT_CHECK_SYNC ? check_status(h, st_dev, st_host, s, "ut_warp_crops") : UT_OK;
 }
 
 extern "C" int ut_warp_map(const double* cam_params, const double* crop_params, const int32_t* src_index, int n_src_images,
@@ -1030,35 +1000,47 @@ static int run_stem(ut_handle h, const float* crops, const uint8_t* crops_u8, fl
   return UT_OK;
 }
 
-// stem .. projection over crops given as fp32 (crops) or as u8 grey levels (crops_u8)
-// One sub-batch of n crops (workspace slices starting at crop `off`) through stem .. projection on stream st.
-static int backbone_pass(ut_handle h, const float* crops, const uint8_t* crops_u8, int off, int n, float* feat,
-                         hipStream_t st) {
+// Crops c0 .. c0 + n - 1 of a call (fp32 `crops` or u8 `crops_u8`) through stem .. projection into their rows of `feat` on
+// stream s, in the workspace slices that start at crop `off`.
+static int backbone_pass(ut_handle h, const float* crops, const uint8_t* crops_u8, float* feat, int c0, int n, int off,
+                         int chunk, hipStream_t s) {
   int rc;
   const size_t a48 = (size_t)off * 48 * 48 * 32, a24 = (size_t)off * 24 * 24 * 64, a12 = (size_t)off * 12 * 12 * 128;
-  unsigned* xm = nullptr;            // max word of the running activation
-  if ((rc = run_stem(h, crops, crops_u8, h->bufX + a48, n, st, &xm))) return rc;
-  {
+  // the words of one pass (<= 2 x 22 + 16 launches) come from one zeroing, so that none of them is recycled while live
+  if (h->counter_next + 256 > kMaxCounters && (rc = begin_call(h, s))) return rc;
+  // ---- phase A: stem + layer1 (48x48x32) + layer2 (24x24x64), `chunk` crops per pass
+  unsigned* l2_max = nullptr;      // max word of bufL2: the passes' words merged when phase A took more than one pass
+  const unsigned l2_gen = h->word_gen;
+  for (int done = 0; done < n; done += chunk) {
+    const int m = n - done < chunk ? n - done : chunk;
+    const size_t first = (size_t)(c0 + done) * 96 * 96;
+    unsigned* xm = nullptr;
+    if ((rc = run_stem(h, crops ? crops + first : nullptr, crops_u8 ? crops_u8 + first : nullptr, h->bufX + a48, m, s, &xm))) return rc;
     float *x = h->bufX + a48, *y = h->bufY + a48;
     int hw = 48;
     for (int b = 0; b < 5; ++b) {
-      float* dst = b == 4 ? h->bufL2 + a24 : y;
-      if ((rc = run_block(h, h->bb[b], x, h->bufH + a48, h->bufD + a24, dst, n, hw, hw, st, xm, &xm, 2 * b, 2 * b + 1))) return rc;
+      float* dst = b == 4 ? h->bufL2 + a24 + (size_t)done * 24 * 24 * 64 : y;
+      if ((rc = run_block(h, h->bb[b], x, h->bufH + a48, h->bufD + a24, dst, m, hw, hw, s, xm, &xm, 2 * b, 2 * b + 1))) return rc;
       hw = (hw + 2 - 3) / h->bb[b].conv1.stride + 1;
       float* t = x; x = y; y = t;
     }
+    if (done == 0) l2_max = xm;
+    else if (l2_max && xm) HIPCHK(h, ut::launch_merge_max(l2_max, xm, s));
+    else l2_max = nullptr;
   }
+  // ---- phase B: layer3 (12x12x128) + layer4 (6x6x256) + projection over the whole sub-batch
   const float* x = h->bufL2 + a24;
   float *y = h->bufP + a12, *other = h->bufQ + a12;
   int hw = 24;
+  unsigned* xm = l2_gen == h->word_gen ? l2_max : nullptr;
   for (int b = 5; b < 12; ++b) {
-    if ((rc = run_block(h, h->bb[b], x, h->bufBH + a12, h->bufBD + a12, y, n, hw, hw, st, xm, &xm, 2 * b, 2 * b + 1))) return rc;
+    if ((rc = run_block(h, h->bb[b], x, h->bufBH + a12, h->bufBD + a12, y, n, hw, hw, s, xm, &xm, 2 * b, 2 * b + 1))) return rc;
     hw = (hw + 2 - 3) / h->bb[b].conv1.stride + 1;
     x = y;
     float* t = y; y = other; other = t;
   }
   // projection 256 -> 72, written NCHW like the reference (lib/models/model_utils.py:134)
-  return run_conv(h, h->proj, x, nullptr, feat, n, 6, 6, false, true, st);
+  return run_conv(h, h->proj, x, nullptr, feat + (size_t)c0 * 72 * 36, n, 6, 6, false, true, s);
 }
 
 // stem .. projection over crops given as fp32 (crops) or as u8 grey levels (crops_u8)
@@ -1090,10 +1072,7 @@ static int run_backbone(ut_handle h, const float* crops, const uint8_t* crops_u8
     for (int i = 0; i < 2; ++i) {
       const int off = i ? n0 : 0, n = i ? n_crops - n0 : n0;
       HIPCHK(h, hipStreamWaitEvent(h->lane_stream[i], h->ev_fork, 0));
-      const size_t first = (size_t)off * 96 * 96;
-      if ((rc = backbone_pass(h, crops ? crops + first : nullptr, crops_u8 ? crops_u8 + first : nullptr, off, n,
-                              feat + (size_t)off * 72 * 36, h->lane_stream[i])))
-        return rc;
+      if ((rc = backbone_pass(h, crops, crops_u8, feat, off, n, off, chunk, h->lane_stream[i]))) return rc;
       HIPCHK(h, hipEventRecord(h->ev_join[i], h->lane_stream[i]));
     }
     for (int i = 0; i < 2; ++i) HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[i], 0));
@@ -1101,42 +1080,7 @@ static int run_backbone(ut_handle h, const float* crops, const uint8_t* crops_u8
   }
   for (int base = 0; base < n_crops; base += pass_b) {
     const int nb = n_crops - base < pass_b ? n_crops - base : pass_b;
-    // ---- phase A: stem + layer1 (48x48x32) + layer2 (24x24x64), `chunk` crops per pass
-    // the words of one pass (<= 2 x 22 + 16 launches) come from one zeroing, so that none of them is recycled while live
-    if (h->counter_next + 256 > kMaxCounters && (rc = begin_call(h, s))) return rc;
-    unsigned* l2_max = nullptr;      // max word of bufL2: the passes' words merged when phase A took more than one pass
-    const unsigned l2_gen = h->word_gen;
-    int passes = 0;
-    for (int done = 0; done < nb; done += chunk, ++passes) {
-      const int n = nb - done < chunk ? nb - done : chunk;
-      const size_t first = (size_t)(base + done) * 96 * 96;
-      unsigned* xm = nullptr;
-      if ((rc = run_stem(h, crops ? crops + first : nullptr, crops_u8 ? crops_u8 + first : nullptr, h->bufX, n, s, &xm))) return rc;
-      float *x = h->bufX, *y = h->bufY;
-      int hw = 48;
-      for (int b = 0; b < 5; ++b) {
-        float* dst = b == 4 ? h->bufL2 + (size_t)done * 24 * 24 * 64 : y;
-        if ((rc = run_block(h, h->bb[b], x, h->bufH, h->bufD, dst, n, hw, hw, s, xm, &xm, 2 * b, 2 * b + 1))) return rc;
-        hw = (hw + 2 - 3) / h->bb[b].conv1.stride + 1;
-        float* t = x; x = y; y = t;
-      }
-      if (passes == 0) l2_max = xm;
-      else if (l2_max && xm) HIPCHK(h, ut::launch_merge_max(l2_max, xm, s));
-      else l2_max = nullptr;
-    }
-    // ---- phase B: layer3 (12x12x128) + layer4 (6x6x256) + projection over the whole pass
-    const float* x = h->bufL2;
-    float *y = h->bufP, *other = h->bufQ;
-    int hw = 24;
-    unsigned* xm = l2_gen == h->word_gen ? l2_max : nullptr;
-    for (int b = 5; b < 12; ++b) {
-      if ((rc = run_block(h, h->bb[b], x, h->bufBH, h->bufBD, y, nb, hw, hw, s, xm, &xm, 2 * b, 2 * b + 1))) return rc;
-      hw = (hw + 2 - 3) / h->bb[b].conv1.stride + 1;
-      x = y;
-      float* t = y; y = other; other = t;
-    }
-    // projection 256 -> 72, written NCHW like the reference (lib/models/model_utils.py:134)
-    if ((rc = run_conv(h, h->proj, x, nullptr, feat + (size_t)base * 72 * 36, nb, 6, 6, false, true, s))) return rc;
+    if ((rc = backbone_pass(h, crops, crops_u8, feat, base, nb, 0, chunk, s))) return rc;
   }
   return UT_OK;
 }
@@ -1193,33 +1137,46 @@ static int calibrate_head(ut_handle h, const float* feat, int n_crops, hipStream
 // Synchronous; the status words are left as they were (a calibration pass reports nothing: a non-finite activation ends up in
 // the calibrated word and is flagged by the calls that use it).
 static int calibrate_split(ut_handle h, const float* crops, int n, hipStream_t s) {
+  // The modes a calibration pass pins, put back on every way out.  Latency mode among them: it keeps every launch on the
+  // fp32 instruction without a max word, which would leave all the words at zero.
+  struct PinnedModes {
+    ut_handle h;
+    const int conv_arith, lanes;
+    const bool profiling, block_fusion, latency_mode;
+    explicit PinnedModes(ut_handle hh)
+        : h(hh), conv_arith(hh->conv_arith), lanes(hh->lanes), profiling(hh->profiling), block_fusion(hh->block_fusion),
+          latency_mode(hh->latency_mode) {
+      h->conv_arith = UT_CONV_SPLIT_F16_ALWAYS; h->lanes = 1; h->profiling = false; h->latency_mode = false; h->calibrating = true;
+    }
+    ~PinnedModes() {
+      h->conv_arith = conv_arith; h->lanes = lanes; h->profiling = profiling; h->block_fusion = block_fusion;
+      h->latency_mode = latency_mode; h->calibrating = false;
+    }
+  };
   float* feat = nullptr;
   int rc = dev_alloc(h, &feat, (size_t)n * 72 * 36);
   if (rc) return rc;
-  int saved[2] = {0, 0};
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipMemcpy(saved, h->status, sizeof saved, hipMemcpyDeviceToHost));
-  const int arith = h->conv_arith, lanes = h->lanes;
-  const bool prof = h->profiling;
-  h->conv_arith = UT_CONV_SPLIT_F16_ALWAYS; h->lanes = 1; h->profiling = false; h->calibrating = true;
-  const bool fusion = h->block_fusion;
-  rc = (int)ut::launch_zero_words(h->calib, 64, s) != 0 ? fail(h, UT_E_HIP, "launch_zero_words") : UT_OK;
-  // both launch forms of layer1 / layer2's entry: the separate-launch form (ut_set_block_fusion(h, 0)) has two tensors more
-  for (int form = 0; form < 2 && !rc; ++form) {
-    h->block_fusion = form == 0;
-    rc = run_backbone(h, crops, nullptr, n, feat, s);
-  }
-  h->block_fusion = fusion;
-  const bool with_head = n >= 2;
-  if (!rc && with_head) rc = calibrate_head(h, feat, n, s);
-  h->conv_arith = arith; h->lanes = lanes; h->profiling = prof; h->calibrating = false;
-  if (!rc) {
+  rc = [&]() -> int {
+    PinnedModes pinned(h);
+    int saved[2] = {0, 0}, r;
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipMemcpy(saved, h->status, sizeof saved, hipMemcpyDeviceToHost));
+    h->calibrated = h->head_calibrated = false;      // until the words are whole again
+    HIPCHK(h, ut::launch_zero_words(h->calib, 64, s));
+    // both launch forms of layer1 / layer2's entry: the separate-launch form (ut_set_block_fusion(h, 0)) has two tensors more
+    for (int form = 0; form < 2; ++form) {
+      h->block_fusion = form == 0;
+      if ((r = run_backbone(h, crops, nullptr, n, feat, s))) return r;
+    }
+    const bool with_head = n >= 2;
+    if (with_head && (r = calibrate_head(h, feat, n, s))) return r;
     HIPCHK(h, ut::launch_raise_words(h->calib, kScaleTensors, kCalibHeadroom, s));
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipMemcpy(h->status, saved, sizeof saved, hipMemcpyHostToDevice));
     h->calibrated = true;
     h->head_calibrated = with_head;
-  }
+    return UT_OK;
+  }();
   (void)hipStreamSynchronize(s);
   dev_free(h, feat);
   return rc;
@@ -1280,29 +1237,12 @@ int ut_warp_backbone(ut_handle h, const uint8_t* src, int n_src_images, int src_
   ON_DEVICE_OF(h);
   hipStream_t s = (hipStream_t)stream;
   const bool u8 = remap_mode == UT_REMAP_CV2_FIXED;
-  const size_t need = (size_t)n_crops * 96 * 96 * (u8 ? 1 : sizeof(float));
-  if (need > h->crops_ws_bytes) {
-    HIPCHK(h, hipDeviceSynchronize());
-    dev_free(h, h->crops_ws);
-    h->crops_ws = nullptr; h->crops_ws_bytes = 0;
-    float* pnew = nullptr;
-    int rc0 = dev_alloc(h, &pnew, (need + 3) / 4);
-    if (rc0) return rc0;
-    h->crops_ws = pnew; h->crops_ws_bytes = need;
-  }
+  int rc = regrow(h, &h->crops_ws_floats, (size_t)n_crops * 96 * 96 / (u8 ? sizeof(float) : 1), {{&h->crops_ws, 1}});
+  if (rc) return rc;
   HIPCHK(h, ut::launch_warp(src, n_src_images, src_h, src_w, cam_params, crop_params, src_index, n_crops, remap_mode,
-                            u8 ? nullptr : (float*)h->crops_ws, u8 ? (uint8_t*)h->crops_ws : nullptr, h->status, s));
-  if (h->check_mode == UT_CHECK_SYNC) {
-    int sticky = 0, call = 0, rc = read_status(h, h->status, h->status_host, s, &sticky, &call);
-    if (rc) return rc;
-    if (sticky & ut::UT_STATUS_ERRORS) {
-      char buf[256];
-      snprintf(buf, sizeof buf, "ut_warp_backbone: %s", status_message(sticky));
-      return fail(h, UT_E_INVALID, buf);
-    }
-  }
-  return run_backbone(h, u8 ? nullptr : (const float*)h->crops_ws, u8 ? (const uint8_t*)h->crops_ws : nullptr, n_crops,
-                      feat, s);
+                            u8 ? nullptr : h->crops_ws, u8 ? (uint8_t*)h->crops_ws : nullptr, h->status, s));
+  if (h->check_mode == UT_CHECK_SYNC && (rc = check_status(h, h->status, h->status_host, s, "ut_warp_backbone"))) return rc;
+  return run_backbone(h, u8 ? nullptr : h->crops_ws, u8 ? (const uint8_t*)h->crops_ws : nullptr, n_crops, feat, s);
 }
 
 // The head behind the index checks: FTL, fusion, temporal block, regressor, decode (a.mem / a.prev_ext: the temporal state it
@@ -1392,14 +1332,8 @@ int ut_fuse_temporal_regress(ut_handle h, const float* feat, const float* intrin
   HIPCHK(h, ut::launch_zero_words(h->slot_seen, (size_t)n_slots, s));
   HIPCHK(h, ut::launch_validate_desc(a, s));
   if (h->check_mode == UT_CHECK_SYNC) {
-    int sticky = 0, call = 0;
-    if ((rc = read_status(h, h->status, h->status_host, s, &sticky, &call))) return rc;
-    if (sticky & ut::UT_STATUS_ERRORS) {
-      char buf[256];
-      snprintf(buf, sizeof buf, "ut_fuse_temporal_regress: %s", status_message(sticky));
-      return fail(h, UT_E_INVALID, buf);
-    }
-    if (call & a.call_error_mask)   // lib/models/umetrack_model.py:224-229
+    if ((rc = check_status(h, h->status, h->status_host, s, "ut_fuse_temporal_regress"))) return rc;
+    if (h->status_host[1] & a.call_error_mask)   // lib/models/umetrack_model.py:224-229
       return fail(h, UT_E_UNSUPPORTED, "Unsupported: found single-view samples when calibration scale");
   }
   if (n_slots > h->slots_used) h->slots_used = n_slots;
@@ -1590,14 +1524,7 @@ int ut_set_index_checks(ut_handle h, int mode) {
 int ut_poll_status(ut_handle h, void* stream) {
   if (!h) return UT_E_INVALID;
   ON_DEVICE_OF(h);
-  int sticky = 0, call = 0, rc = read_status(h, h->status, h->status_host, (hipStream_t)stream, &sticky, &call);
-  if (rc) return rc;
-  if (sticky & ut::UT_STATUS_ERRORS) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "reported late (deferred checks): %s", status_message(sticky));
-    return fail(h, UT_E_INVALID, buf);
-  }
-  return UT_OK;
+  return check_status(h, h->status, h->status_host, (hipStream_t)stream, "reported late (deferred checks)");
 }
 
 int ut_status_snapshot(ut_handle h, int32_t* dst, void* stream) {
@@ -1610,8 +1537,8 @@ int ut_status_snapshot(ut_handle h, int32_t* dst, void* stream) {
 int ut_profile_begin(ut_handle h, void* stream) {
   if (!h) return UT_E_INVALID;
   (void)stream;
-  for (auto& pe : h->prof) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
-  h->prof.clear();
+  ON_DEVICE_OF(h);
+  prof_clear(h);
   h->profiling = true;
   return UT_OK;
 }
@@ -1619,37 +1546,20 @@ int ut_profile_begin(ut_handle h, void* stream) {
 int ut_profile_end(ut_handle h, void* stream, double* conv_ms_total, int64_t* conv_launches, double* conv_flops_total) {
   if (!h) return UT_E_INVALID;
   ON_DEVICE_OF(h);
-  h->profiling = false;
-  HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-  double ms = 0, fl = 0;
-  for (auto& pe : h->prof) {
-    float t = 0;
-    HIPCHK(h, hipEventElapsedTime(&t, pe.a, pe.b));
-    ms += t; fl += pe.flops;
-  }
-  if (conv_ms_total) *conv_ms_total = ms;
-  if (conv_launches) *conv_launches = (int64_t)h->prof.size();
-  if (conv_flops_total) *conv_flops_total = fl;
-  for (auto& pe : h->prof) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
-  h->prof.clear();
+  double ms[2], fl[2];
+  int64_t n[2];
+  int rc = prof_reduce(h, (hipStream_t)stream, ms, n, fl);
+  if (rc) return rc;
+  if (conv_ms_total) *conv_ms_total = ms[0] + ms[1];
+  if (conv_launches) *conv_launches = n[0] + n[1];
+  if (conv_flops_total) *conv_flops_total = fl[0] + fl[1];
   return UT_OK;
 }
 
 int ut_profile_end_by_kind(ut_handle h, void* stream, double* ms2, int64_t* launches2, double* flops2) {
   if (!h || !ms2 || !launches2 || !flops2) return UT_E_INVALID;
   ON_DEVICE_OF(h);
-  h->profiling = false;
-  HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
-  for (int k = 0; k < 2; ++k) { ms2[k] = 0; launches2[k] = 0; flops2[k] = 0; }
-  for (auto& pe : h->prof) {
-    float t = 0;
-    HIPCHK(h, hipEventElapsedTime(&t, pe.a, pe.b));
-    const int k = pe.kind ? 1 : 0;
-    ms2[k] += t; flops2[k] += pe.flops; launches2[k] += 1;
-  }
-  for (auto& pe : h->prof) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
-  h->prof.clear();
-  return UT_OK;
+  return prof_reduce(h, (hipStream_t)stream, ms2, launches2, flops2);
 }
 
 }  // extern "C"

@@ -760,6 +760,25 @@ def test_split_f16_calibrated_scales_batch_independence_and_range_guard(engine):
         other.close()
 
 
+def test_split_f16_calibration_does_not_depend_on_latency_mode():
+    """A handle that selects the split-fp16 arithmetic while in latency mode calibrates on the batched dispatch all the same
+    (csrc/ut_api.hip::calibrate_split pins latency mode off for the pass): the same words, bit for bit, as a handle that was
+    never in latency mode, and none of them left at zero (but word 24: that tensor feeds only the projection, an fp32 launch)."""
+    a = _native.HipEngine(synth.synthetic_state_dict(0), DEV)
+    b = _native.HipEngine(synth.synthetic_state_dict(0), DEV)
+    try:
+        a.set_latency_mode(True)
+        a.set_conv_arithmetic("split_f16_always")
+        a.set_latency_mode(False)
+        b.set_conv_arithmetic("split_f16_always")
+        cal = a.split_calibration()
+        assert np.array_equal(cal.view(np.uint32), b.split_calibration().view(np.uint32))
+        assert (cal[:24] > 0).all() and cal[24] == 0 and (cal[25:] > 0).all()
+    finally:
+        a.close()
+        b.close()
+
+
 def _head_inputs(engine, n_samples=3, seed=2):
     n = 2 * n_samples
     g = torch.Generator(device=DEV)
