@@ -231,3 +231,63 @@ def channel_rescaled_state_dict(sd: Dict[str, np.ndarray], spread: int, seed: in
                 mul(pre + f"{l}.{b}.bn1.bias", down, 0)
                 mul(pre + f"{l}.{b}.conv2.weight", up, 1)
     return out
+
+
+_BB0 = "_feature_extractor._image_backbone.0._layers."
+
+
+def zero_bias_state_dict(sd: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """`sd` with every additive term of the backbone removed: each BatchNorm's running_mean and bias, the stem convolution's
+    bias and the projection's bias set to 0.  Every backbone tensor is then positively homogeneous in the crops
+    (conv, scale, ReLU and max-pool all commute with c > 0): backbone(c x crops) == c x backbone(crops), exactly for c = 2^j in
+    fp64 - so one fp64 run gives the reference at every scale, and scaling the crops scales every activation tensor by the
+    same factor relative to its calibrated word."""
+    out = dict(sd)
+    for k, v in sd.items():
+        if not k.startswith("_feature_extractor._image_backbone."):
+            continue
+        if k.endswith(".running_mean") or (k.endswith(".bias") and v.ndim == 1):
+            out[k] = np.zeros_like(v)
+    return out
+
+
+def layer1_worst_case_state_dict(sd: Dict[str, np.ndarray], row_significand: float = 1.93) -> Dict[str, np.ndarray]:
+    """A zero-bias network (zero_bias_state_dict) on which a constant crop drives each of layer1's fused intermediates
+    relu(bn1(conv1 x)) to the L1 bound max|x| x max_c sum_k |w1[c][k]| that conv_block32.hip sizes its scale from:
+      - every stem channel has the same all-positive 3x3 weights and the same BatchNorm: a constant crop gives one value on every
+        channel at every interior pixel, and that value is the stem output's maximum;
+      - in both blocks of layer1 every row of conv1 is the same all-positive row, its folded L1 sum with significand
+        `row_significand` (near 2, so that the bound's power of two sits at the top of its octave); every row of conv2 is the same
+        all-positive row, scaled so that bn2(conv2(.)) returns the block's input at interior pixels: a block doubles a constant
+        input, and the intermediate's rounding reaches the block's output at half weight;
+      - layer2's entry (conv1 and shortcut weights x 2^-6, bn1 / shortcut BatchNorm biases 0.5) lets every later tensor grow far
+        slower than the crops' brightness, so that only the stem's and layer1's tensors approach their calibrated range."""
+    out = zero_bias_state_dict(sd)
+
+    def bn_gain(p):
+        return float(out[p + ".weight"][0]) / math.sqrt(float(out[p + ".running_var"][0]) + arch.BN_EPS)
+
+    def same_rows(key, bn):
+        w = np.repeat(np.abs(out[key][:1]).astype(np.float64), out[key].shape[0], 0)
+        for f in ("weight", "running_var"):
+            v = out[bn + "." + f]
+            out[bn + "." + f] = np.full_like(v, v[0])
+        return w, bn_gain(bn)
+
+    w, _ = same_rows(_BB0 + "0.0.weight", _BB0 + "0.1")
+    out[_BB0 + "0.0.weight"] = w.astype(np.float32)
+    for b in (0, 1):
+        p = _BB0 + f"1.{b}"
+        w1, g1 = same_rows(p + ".conv1.weight", p + ".bn1")
+        l1 = g1 * w1[0].sum()
+        w1 *= row_significand / (l1 / 2.0 ** math.floor(math.log2(l1)))
+        out[p + ".conv1.weight"] = w1.astype(np.float32)
+        l1 = g1 * out[p + ".conv1.weight"][0].astype(np.float64).sum()
+        w2, g2 = same_rows(p + ".conv2.weight", p + ".bn2")
+        out[p + ".conv2.weight"] = (w2 / (l1 * g2 * w2[0].sum())).astype(np.float32)
+    p = _BB0 + "2.0."
+    for k in ("conv1.weight", "downsample.0.weight"):
+        out[p + k] = (out[p + k] * np.float32(2.0 ** -6)).astype(np.float32)
+    for k in ("bn1.bias", "downsample.1.bias"):
+        out[p + k] = np.full_like(out[p + k], 0.5)
+    return out

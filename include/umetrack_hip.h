@@ -119,7 +119,12 @@ int ut_set_backbone_lanes(ut_handle h, int lanes);
  *                      - inside a packed tensor, a value more than 2^18 below the scale word (a weight that far below its layer's
  *                        largest) loses its second piece: it keeps an absolute error of 2^-40 of the scale word, where fp32
  *                        would keep 2^-24 of the value.  After canonicalisation such values belong to channels (weights) whose
- *                        contribution to the layer's output is below fp32's own rounding of that output;
+ *                        contribution to the layer's output is below fp32's own rounding of that output.  The same holds for
+ *                        activations against their CALIBRATED word (UT_SPLIT_SCALE_CALIBRATED): a call whose inputs are far dimmer
+ *                        than the calibration set gets an ABSOLUTE error, about the one a call at 2^-7 of the calibration maximum
+ *                        gets (~4e-9 of the calibration set's largest output; 2^-12 with ut_set_block_fusion(h, 0): the fused
+ *                        layer1 block scales its intermediate by an L1 bound, not by a calibrated word), not a relative one.
+ *                        UT_SPLIT_SCALE_DYNAMIC, ut_calibrate_split on representative crops, or UT_CONV_FP32 avoid it;
  *                      - an infinity or a NaN has no scale, and (calibrated scales) an activation of 32 x the calibration maximum
  *                        or more would saturate the first piece: both set a sticky status bit that the next status read
  *                        (ut_poll_status, or any call that reads the index checks in UT_CHECK_SYNC mode) returns as

@@ -1,4 +1,5 @@
-"""Oracle (TEST INFRASTRUCTURE ONLY): fp32 CPU restatement of the UmeTrack network.
+"""Oracle (TEST INFRASTRUCTURE ONLY): CPU restatement of the UmeTrack network, in the dtype of its inputs (fp32 as the
+reference runs it; fp64 from a `.double()` state dict and fp64 inputs, the high-precision yardstick of the split-fp16 tests).
 
 Follows, stage by stage (reference file:line):
   backbone            lib/models/model_utils.py:107-138, lib/models/backbone_resnet.py:56-72,75-165
@@ -10,7 +11,7 @@ Follows, stage by stage (reference file:line):
   regressor + decode  lib/models/regressor.py:76-121,163-186, lib/models/model_utils.py:17-54
   world transform     lib/models/umetrack_model.py:77-97,188-242
 Weights are a plain dict keyed like the reference state_dict.  torch is used only
-for its CPU fp32 conv / batch_norm / svd / inverse - the same ATen the reference
+for its CPU conv / batch_norm / svd / inverse - the same ATen the reference
 calls - so the restatement is an op-for-op functional pipeline, not a module tree.
 """
 from typing import Dict, Optional
@@ -113,8 +114,8 @@ class TemporalState:
     def step(self, sd, img_feat, cur_ext, memory_idx, use_memory) -> torch.Tensor:
         need = int(memory_idx.max()) + 1
         if len(self.mem) < need:                                        # temporal.py:101-125
-            mem = torch.zeros(need, arch.MEM_CH, arch.FEAT_HW, arch.FEAT_HW)
-            ext = torch.zeros(need, 4, 4)
+            mem = torch.zeros(need, arch.MEM_CH, arch.FEAT_HW, arch.FEAT_HW, dtype=img_feat.dtype)
+            ext = torch.zeros(need, 4, 4, dtype=img_feat.dtype)
             if len(self.mem):
                 mem[: len(self.mem)] = self.mem
                 ext[: len(self.prev_ext)] = self.prev_ext
@@ -146,13 +147,13 @@ def skeleton_features(sd, axes, rest) -> torch.Tensor:
     return F.relu(_bn(sd, "_skeleton_enc._layers.2", x))
 
 
-def rigid_source_points() -> torch.Tensor:
+def rigid_source_points(dtype=torch.float32) -> torch.Tensor:
     # regressor.py:19-47: 7 fixed points, non-zero ones rescaled to norm 0.1
     pts = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1],
                     [-1, -1, 0], [-1, 0, -1], [0, -1, -1]], dtype=np.float64)
     nrm = np.linalg.norm(pts, axis=1, keepdims=True)
     pts = np.where(nrm > 0, pts / np.maximum(nrm, 1e-30) * 0.1, pts)
-    return torch.from_numpy(pts).float()
+    return torch.from_numpy(pts).to(dtype)
 
 
 def procrustes(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
@@ -162,9 +163,9 @@ def procrustes(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     h = (src - mu_s[:, None]).transpose(1, 2) @ (dst - mu_d[:, None])
     u, _s, vh = torch.linalg.svd(h)
     v = vh.transpose(1, 2)
-    w = torch.eye(3).repeat(n, 1, 1)
+    w = torch.eye(3, dtype=src.dtype).repeat(n, 1, 1)
     w[:, 2, 2] = torch.det(v @ u.transpose(1, 2))
-    xf = torch.eye(4).repeat(n, 1, 1)
+    xf = torch.eye(4, dtype=src.dtype).repeat(n, 1, 1)
     xf[:, :3, :3] = v @ w @ u.transpose(1, 2)
     xf[:, :3, 3] = mu_d - (xf[:, :3, :3] @ mu_s[..., None])[..., 0]
     return xf
@@ -180,9 +181,9 @@ def regress(sd, name: str, x: torch.Tensor) -> Dict[str, torch.Tensor]:
     sl = arch.REG_K_SLICES if name == "_regressor_k" else arch.REG_U_SLICES
     out = {"raw": raw}
     a, b = sl["joint_angles"]
-    out["joint_angles"] = torch.cat([raw[:, a:b], torch.zeros(raw.shape[0], 2)], 1)   # regressor.py:76-85
+    out["joint_angles"] = torch.cat([raw[:, a:b], torch.zeros(raw.shape[0], 2, dtype=raw.dtype)], 1)   # regressor.py:76-85
     a, b = sl["wrist_xfs"]
-    src = rigid_source_points()[None].expand(raw.shape[0], -1, -1)
+    src = rigid_source_points(raw.dtype)[None].expand(raw.shape[0], -1, -1)
     out["wrist_xfs"] = procrustes(src, raw[:, a:b].reshape(raw.shape[0], -1, 3))    # regressor.py:88-104
     if "skel_scales" in sl:
         a, b = sl["skel_scales"]
