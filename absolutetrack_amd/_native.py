@@ -25,12 +25,13 @@ EXPORTS = (
     "ut_set_index_checks", "ut_poll_status", "ut_warp_backbone", "ut_set_latency_mode", "ut_set_conv_arithmetic",
     "ut_set_backbone_lanes", "ut_status_snapshot", "ut_warp_map", "ut_set_block_fusion", "ut_set_resident_weights",
     "ut_canonical_backbone_weights", "ut_set_split_scale", "ut_calibrate_split", "ut_get_split_calibration",
-    "ut_gen_crop_cameras_from_window_points",
+    "ut_gen_crop_cameras_from_window_points", "ut_get_split_adaptations",
 )
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
 UT_CHECK_SYNC, UT_CHECK_DEFERRED = 0, 1
+SPLIT_SCALE_MODES = {"calibrated": 0, "dynamic": 1, "adaptive": 2}      # UT_SPLIT_SCALE_*
 
 _lib = None
 
@@ -122,6 +123,8 @@ def load_library() -> ctypes.CDLL:
     lib.ut_calibrate_split.argtypes = [vp, vp, i32, vp]
     lib.ut_get_split_calibration.restype = i32
     lib.ut_get_split_calibration.argtypes = [vp, vp]
+    lib.ut_get_split_adaptations.restype = i32
+    lib.ut_get_split_adaptations.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), i32, vp]
     lib.ut_canonical_backbone_weights.restype = i32
     lib.ut_canonical_backbone_weights.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     _lib = lib
@@ -441,6 +444,7 @@ class HipEngine:
         self._h = h
         self.deferred_checks = False      # mirrors of the handle's modes (the C ABI has setters only)
         self.latency_mode = False
+        self.split_scale = "calibrated"
 
     def close(self):
         if getattr(self, "_h", None):
@@ -474,16 +478,19 @@ class HipEngine:
         self.deferred_checks = bool(deferred)
 
     @contextlib.contextmanager
-    def modes(self, deferred_checks: Optional[bool] = None, latency: Optional[bool] = None):
-        """Switch the handle's check / latency mode for the calls inside the `with` block and put back what was set
-        before: a handle shared by a per-frame HandTracker (latency mode, deferred checks) and a batched HotPath keeps
-        each user's settings out of the other's calls."""
-        prev = (self.deferred_checks, self.latency_mode)
+    def modes(self, deferred_checks: Optional[bool] = None, latency: Optional[bool] = None,
+              split_scale: Optional[str] = None):
+        """Switch the handle's check / latency / split-scale mode for the calls inside the `with` block and put back what
+        was set before: a handle shared by a per-frame HandTracker (latency mode, deferred checks) and a batched HotPath
+        keeps each user's settings out of the other's calls, and a HotPath user can scope e.g. split_scale="adaptive"."""
+        prev = (self.deferred_checks, self.latency_mode, self.split_scale)
         try:
             if deferred_checks is not None and deferred_checks != prev[0]:
                 self.set_index_checks(deferred_checks)
             if latency is not None and latency != prev[1]:
                 self.set_latency_mode(latency)
+            if split_scale is not None and split_scale != prev[2]:
+                self.set_split_scale(split_scale)
             yield self
         finally:
             if self._h:
@@ -491,6 +498,8 @@ class HipEngine:
                     self.set_index_checks(prev[0])
                 if self.latency_mode != prev[1]:
                     self.set_latency_mode(prev[1])
+                if self.split_scale != prev[2]:
+                    self.set_split_scale(prev[2])
 
     def status_snapshot(self, out: torch.Tensor):
         """Stream-ordered copy of the two device status words (sticky errors, this call's bits) into `out` (int32 [2] on
@@ -530,8 +539,21 @@ class HipEngine:
         """Split-fp16 mode: "calibrated" (default) - one fixed power-of-two activation scale per backbone tensor and handle (a
         crop's bits do not depend on its batch, lane count or sharding; inputs beyond 32 x the calibration maximum are reported
         by poll_status as FloatingPointError) - or "dynamic": each launch scales by the largest magnitude its producer stored in
-        this call."""
-        self._check(self.lib.ut_set_split_scale(self._h, {"calibrated": 0, "dynamic": 1}[mode]), "ut_set_split_scale")
+        this call - or "adaptive": calibrated, but a launch whose input lies outside the calibrated band (32 x the calibration
+        maximum or more, or non-zero and below 2^-7 of it) runs exactly as in "dynamic" mode instead of raising or losing
+        precision, and counts in split_adaptations().  In band its bits are the "calibrated" mode's.  The decision is per
+        LAUNCH, made on the device: one dim crop in a normal batch stays in band (and keeps the calibrated floor).  Only an
+        infinity or a NaN still raises."""
+        self._check(self.lib.ut_set_split_scale(self._h, SPLIT_SCALE_MODES[mode]), "ut_set_split_scale")
+        self.split_scale = mode
+
+    def split_adaptations(self, reset: bool = False) -> int:
+        """Split launches that adapted ("adaptive" split scale: input out of the calibrated band) since the counter was last
+        reset; one count per launch, both lanes included.  Synchronises the current stream; reset=True zeroes the counter."""
+        n = ctypes.c_uint32(0)
+        self._check(self.lib.ut_get_split_adaptations(self._h, ctypes.byref(n), int(bool(reset)), _stream(self.device)),
+                    "ut_get_split_adaptations")
+        return int(n.value)
 
     def calibrate_split(self, crops: Optional[torch.Tensor] = None):
         """Take the calibrated activation scales from `crops` ([n,96,96] fp32 on the device; None: the built-in synthetic set,

@@ -17,7 +17,8 @@
 //
 // Activation scale of the intermediate.  The split needs a power of two that brings the intermediate under 2^15 BEFORE any
 // of it exists, so it cannot be the producer's max word.  It is a bound instead: |relu(bn1(conv1 x))| <= max|x| * max_c sum_k
-// |w1[c][k]| + max|b1| (host: the row sums of the folded weights; device: max|x| - the input's max word with dynamic scales,
+// |w1[c][k]| + max|b1| (host: the row sums of the folded weights; device: max|x| - the input's max word with dynamic scales
+// and in a launch that adapted (ut_kernels.h::split_act_scale),
 // the largest input split_act_scale admits against a calibrated word, 2^16 / x_scale).  The bound is
 // loose by the usual gap between an L1 and a random-sign sum (tens), which costs nothing: a value keeps its full 22 bits
 // down to 2^-18 of the bound and an absolute 2^-40 of the bound below.  Same bits for every tiling and batch.
@@ -123,14 +124,15 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
   // ---- scales: input (from the producer's max word), intermediate (a bound, see the header)
   float x_scale = 1.f, x_unscale = 1.f, i_scale = 1.f, i_unscale = 1.f;
   {
-    bool ok;
-    split_act_scale(p.in_max, p.in_obs, x_scale, x_unscale, ok);
-    if (!ok && tid == 0 && blockIdx.x == 0 && p.status) atomicOr(p.status, UT_SPLIT_RANGE);
+    bool ok, adapted;
+    const unsigned x_bits = split_act_scale(p.in_max, p.in_obs, p.split_adaptive, x_scale, x_unscale, ok, adapted);
+    split_scale_report(ok, adapted, p.status, p.adapt_count);
     // calibrated word (in_obs set): the guard admits inputs up to 2^16 x x_unscale (2 .. 4 x the word), so the bound is taken
-    // there, not at the word - else an admitted input near the L1 worst case pushes the intermediate past fp16's range
+    // there, not at the word - else an admitted input near the L1 worst case pushes the intermediate past fp16's range.  A
+    // dynamic word, or an adapted launch's (in_obs, as in dynamic mode), is the input's own maximum
     const float xmax = !ok ? 0.f
-                       : p.in_obs ? 65536.f * x_unscale
-                                  : __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)*p.in_max));
+                       : p.in_obs && !adapted ? 65536.f * x_unscale
+                                              : __uint_as_float(x_bits);
     b_pow2_for(xmax * p.wsum1 + p.bmax1, i_scale, i_unscale);
   }
   const float acc1_scale = x_scale / p.unscale_w1, acc1_unscale = p.unscale_w1 * x_unscale;     // powers of two

@@ -112,9 +112,9 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
   float x_scale = 1.f, x_unscale = 1.f;      // SPLIT: power-of-two activation scale and its inverse
   if constexpr (SPLIT) {
     if (p.in_max) {
-      bool ok;
-      split_act_scale(p.in_max, p.in_obs, x_scale, x_unscale, ok);
-      if (!ok && tid == 0 && blockIdx.x == 0 && p.status) atomicOr(p.status, UT_SPLIT_RANGE);
+      bool ok, adapted;
+      split_act_scale(p.in_max, p.in_obs, p.split_adaptive, x_scale, x_unscale, ok, adapted);
+      split_scale_report(ok, adapted, p.status, p.adapt_count);
     }
   }
   auto convert_patch = [&](int buf) {

@@ -178,9 +178,9 @@ __global__ __launch_bounds__(512, 1) void conv_split_kernel(ConvLaunch p, int ti
   // power-of-two activation scale from the producer's max word, and the epilogue's factor 2^-(weight scale + activation scale)
   float x_scale = 1.f, x_unscale = 1.f;
   if (p.in_max) {
-    bool ok;
-    split_act_scale(p.in_max, p.in_obs, x_scale, x_unscale, ok);
-    if (!ok && tid == 0 && blockIdx.x == 0 && p.status) atomicOr(p.status, UT_SPLIT_RANGE);
+    bool ok, adapted;
+    split_act_scale(p.in_max, p.in_obs, p.split_adaptive, x_scale, x_unscale, ok, adapted);
+    split_scale_report(ok, adapted, p.status, p.adapt_count);
   }
   const float tot_unscale = p.split_unscale * x_unscale;
 

@@ -93,6 +93,8 @@ struct ut_context {
   // block b's output (b = 0 .. 11).  calib[t]: the bits of 2^kCalibHeadroom x the largest magnitude of tensor t over the
   // calibration crops (device words behind the per-launch words; never zeroed by begin_call).
   unsigned* calib = nullptr;
+  unsigned* adapt_count = nullptr;  // UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE: split launches that adapted (ut_get_split_adaptations; both
+                                    // lanes; the last of the 64 words at calib, so a calibration zeroes it)
   int scale_mode = UT_SPLIT_SCALE_CALIBRATED;
   bool calibrated = false;
   bool head_calibrated = false;     // ... including the regressor's tensors (needs at least two calibration crops)
@@ -197,7 +199,8 @@ int stateless_status(int* device_out, DevStatus* out) {
 const char* status_message(int bits) {
   if (bits & ut::UT_SPLIT_RANGE)
     return "range check: an activation entering a split-fp16 convolution is an infinity or a NaN, or lies beyond the calibrated range "
-           "of its layer (32 x the calibration maximum; ut_calibrate_split with representative crops, or UT_SPLIT_SCALE_DYNAMIC)";
+           "of its layer (32 x the calibration maximum; ut_calibrate_split with representative crops, UT_SPLIT_SCALE_DYNAMIC or "
+           "UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE)";
   if (bits & ut::UT_BAD_SRC_INDEX) return "index check: src_index outside [0, n_src_images)";
   if (bits & ut::UT_BAD_SAMPLE_RANGE) return "index check: sample_range rows must select 1 or 2 crops inside [0, n_crops]";
   if (bits & ut::UT_BAD_MEMORY_IDX) return "index check: memory_idx outside [0, n_slots)";
@@ -601,6 +604,7 @@ int ensure_slots(ut_handle h, int slots, hipStream_t s) {
 
 constexpr int kMaxCounters = 4096;
 constexpr int kScaleTensors = 33;      // 25 of the backbone; 25 .. 28 the known-skeleton regressor's input, inner tensors and first block's output, 29 .. 32 the other regressor's
+static_assert(kScaleTensors < 63, "the adaptation counter is the last of the 64 words at ut_context::calib");
 constexpr int kCalibHeadroom = 4;      // calibrated scale words hold 2^4 x the calibration maximum: inputs up to 32 x that maximum
                                        // (the scale leaves another factor 2 under fp16's 65504) are inside the split's range
 
@@ -626,14 +630,16 @@ int next_launch_word(ut_handle h, hipStream_t s, int* idx, bool* recycled = null
 }
 
 // The scale word a split-fp16 consumer of tensor `tid` reads, and the word it guards against: calibrated mode - the handle's
-// calibrated word, guarded by the word the producer left in this call (may be null); dynamic mode and calibration passes - the
-// producer's word itself (null: no scale, the launch stays on the fp32 instruction).
-struct ScaleRef { const unsigned* word = nullptr; const unsigned* obs = nullptr; };
+// calibrated word, guarded by the word the producer left in this call (may be null); adaptive mode - the same, and the consumer
+// takes the producer's word instead when it lies outside the calibrated band (ut_kernels.h::split_act_scale); dynamic mode and
+// calibration passes - the producer's word itself (null: no scale, the launch stays on the fp32 instruction).
+struct ScaleRef { const unsigned* word = nullptr; const unsigned* obs = nullptr; int adaptive = 0; unsigned* adapt_count = nullptr; };
 ScaleRef scale_for(ut_handle h, int tid, const unsigned* producer_word) {
   ScaleRef r;
   if (!h->call_split || h->latency_mode || tid < 0 || tid >= kScaleTensors) return r;
   if (h->calibrating || h->scale_mode == UT_SPLIT_SCALE_DYNAMIC) r.word = producer_word;
   else { r.word = h->calib + tid; r.obs = producer_word; }
+  if (!h->calibrating && h->scale_mode == UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE && r.obs) { r.adaptive = 1; r.adapt_count = h->adapt_count; }
   return r;
 }
 // One convolution launch (`launch()` enqueues kernel `what`).  A calibration pass first folds the producer's word of the
@@ -710,6 +716,8 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
   c.status = h->status;
   c.in_max = sr.word;
   c.in_obs = sr.obs;
+  c.split_adaptive = sr.adaptive;
+  c.adapt_count = sr.adapt_count;
   const int kind = c.w_split && (ut::conv_split_applicable(c) || ut::conv_patch_applicable(c)) ? 1 : 0;
   if (kind) {
     c.out_max = h->counters + kMaxCounters + word;
@@ -743,7 +751,7 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
     bl.unscale_w1 = b.conv1.split_unscale; bl.unscale_w2 = b.conv2.split_unscale;
     bl.bias1 = b.conv1.bias; bl.bias2 = b.conv2.bias;
     bl.wsum1 = b.conv1.wsum_rows; bl.bmax1 = b.conv1.bias_max;
-    bl.in_max = xs.word; bl.in_obs = xs.obs; bl.status = h->status;
+    bl.in_max = xs.word; bl.in_obs = xs.obs; bl.split_adaptive = xs.adaptive; bl.adapt_count = xs.adapt_count; bl.status = h->status;
     bl.n_img = n_img; bl.H = H; bl.W = W; bl.device = h->device; bl.num_cu = h->num_cu;
     if (ut::conv_block32_applicable((bl.tile_counter = h->counters, bl))) {
       int word = 0;
@@ -767,7 +775,7 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
     sl.in = x; sl.out1 = tmp; sl.out2 = dsbuf; sl.w1_split = b.conv1.w_split; sl.wd_split = b.ds.w_split;
     sl.unscale1 = b.conv1.split_unscale; sl.unscale_d = b.ds.split_unscale;
     sl.bias1 = b.conv1.bias; sl.bias_d = b.ds.bias;
-    sl.in_max = xs.word; sl.in_obs = xs.obs; sl.status = h->status;
+    sl.in_max = xs.word; sl.in_obs = xs.obs; sl.split_adaptive = xs.adaptive; sl.adapt_count = xs.adapt_count; sl.status = h->status;
     sl.n_img = n_img; sl.H = H; sl.W = W; sl.device = h->device; sl.num_cu = h->num_cu;
     if (ut::conv_c32s2_applicable(sl)) {
       int word = 0;
@@ -862,6 +870,7 @@ int ut_create(int device, const float* blob, size_t n_floats, ut_handle* out) {
   do {
     { float* cnt = nullptr; if ((rc = dev_alloc(h, &cnt, 2 * kMaxCounters + 64))) break; h->counters = (unsigned*)cnt;
       h->calib = h->counters + 2 * kMaxCounters;
+      h->adapt_count = h->calib + 63;      // behind the kScaleTensors words: zeroed with them by a calibration
       hipError_t e1 = hipMemset(h->calib, 0, 64 * sizeof(unsigned));
       if (e1 != hipSuccess) { rc = fail(h, UT_E_HIP, "calibration words", e1); break; } }
     { float* st = nullptr; if ((rc = dev_alloc(h, &st, 2))) break; h->status = (int*)st;
@@ -1203,10 +1212,26 @@ int ut_calibrate_split(ut_handle h, const float* crops, int n_crops, void* strea
 }
 
 int ut_set_split_scale(ut_handle h, int mode) {
-  if (!h || (mode != UT_SPLIT_SCALE_CALIBRATED && mode != UT_SPLIT_SCALE_DYNAMIC)) return fail(h, UT_E_INVALID, "ut_set_split_scale: bad argument");
+  if (!h || (mode != UT_SPLIT_SCALE_CALIBRATED && mode != UT_SPLIT_SCALE_DYNAMIC && mode != UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE))
+    return fail(h, UT_E_INVALID, "ut_set_split_scale: bad argument");
   ON_DEVICE_OF(h);
   h->scale_mode = mode;
-  if (mode == UT_SPLIT_SCALE_CALIBRATED && h->conv_arith != UT_CONV_FP32 && !h->calibrated) return calibrate_builtin(h);
+  if (mode != UT_SPLIT_SCALE_DYNAMIC && h->conv_arith != UT_CONV_FP32 && !h->calibrated) return calibrate_builtin(h);
+  return UT_OK;
+}
+
+int ut_get_split_adaptations(ut_handle h, uint32_t* out, int reset, void* stream) {
+  if (!h || !out) return fail(h, UT_E_INVALID, "ut_get_split_adaptations: null argument");
+  ON_DEVICE_OF(h);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned n = 0;
+  HIPCHK(h, hipMemcpyAsync(&n, h->adapt_count, sizeof n, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  *out = n;
+  if (reset) {
+    HIPCHK(h, ut::launch_zero_words(h->adapt_count, 1, s));      // a kernel, not a memset node: see launch_zero_words
+    HIPCHK(h, hipStreamSynchronize(s));
+  }
   return UT_OK;
 }
 
@@ -1481,7 +1506,7 @@ int ut_set_backbone_lanes(ut_handle h, int lanes) {
 int ut_set_conv_arithmetic(ut_handle h, int mode) {
   if (!h || (mode != UT_CONV_FP32 && mode != UT_CONV_SPLIT_F16 && mode != UT_CONV_SPLIT_F16_ALWAYS)) return fail(h, UT_E_INVALID, "ut_set_conv_arithmetic: bad argument");
   h->conv_arith = mode;
-  if (mode != UT_CONV_FP32 && h->scale_mode == UT_SPLIT_SCALE_CALIBRATED && !h->calibrated) {
+  if (mode != UT_CONV_FP32 && h->scale_mode != UT_SPLIT_SCALE_DYNAMIC && !h->calibrated) {
     ON_DEVICE_OF(h);
     return calibrate_builtin(h);
   }

@@ -23,6 +23,9 @@ struct ConvLaunch {
                             // left in this call (publish_abs_max)
   const unsigned* in_obs;   // optional, with a calibrated in_max: the word the producer left in THIS call - an input beyond the
                             // calibrated range sets UT_SPLIT_RANGE
+  int split_adaptive;       // with in_obs (UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE): an input outside the calibrated band takes its
+                            // scale from in_obs instead (see split_act_scale) and counts one in *adapt_count
+  unsigned* adapt_count;    // device word of the handle: launches that adapted (never null when split_adaptive is set)
   unsigned* out_max;        // optional device word (zero before the launch): receives the bits of max |out|
   const float* bias;   // [cout_pad]
   const float* res;    // optional residual, same layout as out
@@ -64,8 +67,10 @@ struct Stride2Launch {
   float unscale1, unscale_d;      // 1 / (their weight scales)
   const float* bias1;
   const float* bias_d;
-  const unsigned* in_max;   // scale word of `in` (see ConvLaunch::in_max / in_obs)
+  const unsigned* in_max;   // scale word of `in` (see ConvLaunch::in_max / in_obs / split_adaptive / adapt_count)
   const unsigned* in_obs;
+  int split_adaptive;
+  unsigned* adapt_count;
   unsigned* out1_max;       // device word (zero before the launch): receives the bits of max |out1|
   int* status;
   int n_img, H, W;
@@ -94,8 +99,10 @@ struct BlockLaunch {
   const float* bias2;
   float wsum1;              // max over output channels of sum_k |w1| (folded): bounds the intermediate with max|in| and bmax1
   float bmax1;              // max |bias1|
-  const unsigned* in_max;   // scale word of `in` (never null; see ConvLaunch::in_max / in_obs)
+  const unsigned* in_max;   // scale word of `in` (never null; see ConvLaunch::in_max / in_obs / split_adaptive / adapt_count)
   const unsigned* in_obs;
+  int split_adaptive;
+  unsigned* adapt_count;
   unsigned* out_max;        // optional: receives the bits of max |out|
   int* status;
   unsigned* tile_counter;
@@ -181,17 +188,38 @@ __device__ __forceinline__ void publish_abs_max(unsigned* word, unsigned lane_bi
 // in_obs (optional): the largest magnitude the producer actually stored in this call, when in_max is a calibrated word: the
 // first piece of x * 2^k stays finite while x * 2^k < 2^16, i.e. while x's exponent is at most one above the word's;
 // beyond that (or a non-finite value) ok = false.
-__device__ __forceinline__ void split_act_scale(const unsigned* in_max, const unsigned* in_obs, float& scale, float& unscale, bool& ok) {
-  const unsigned bits = (unsigned)__builtin_amdgcn_readfirstlane((int)*in_max);
-  const int e = (int)(bits >> 23);
-  ok = e != 255;
-  int k = (bits == 0u || !ok) ? 0 : 141 - e;      // max in [2^(e-127), 2^(e-126)) -> times 2^k in [2^14, 2^15)
+// adaptive (with in_obs; UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE): a finite non-zero in_obs outside the calibrated band - beyond
+// that guard, or more than 11 binades below the word (under 2^-7 of the calibration maximum, the word being 2^4 x it) - is
+// taken as the scale word instead, exactly as a dynamic-scale launch takes its producer's word: adapted = true, ok = true.
+// A zero in_obs, an infinity or a NaN never adapts.  Every workgroup reads the same two words, so the choice is uniform over
+// the launch.  Returns the bits the scale was taken from.
+__device__ __forceinline__ unsigned split_act_scale(const unsigned* in_max, const unsigned* in_obs, bool adaptive, float& scale,
+                                                    float& unscale, bool& ok, bool& adapted) {
+  unsigned bits = (unsigned)__builtin_amdgcn_readfirstlane((int)*in_max);
+  const unsigned obs = in_obs ? (unsigned)__builtin_amdgcn_readfirstlane((int)*in_obs) : 0u;
+  const int eo = (int)(obs >> 23);
+  int e = (int)(bits >> 23);
+  int k = (bits == 0u || e == 255) ? 0 : 141 - e;  // max in [2^(e-127), 2^(e-126)) -> times 2^k in [2^14, 2^15)
   k = k > 100 ? 100 : k < -100 ? -100 : k;
+  adapted = adaptive && in_obs && obs != 0u && eo != 255 && (eo + k > 142 || eo + 11 < e);
+  if (adapted) {
+    bits = obs;
+    e = eo;
+    k = 141 - e;
+    k = k > 100 ? 100 : k < -100 ? -100 : k;
+  }
+  ok = e != 255;
   scale = __uint_as_float((unsigned)(127 + k) << 23);
   unscale = __uint_as_float((unsigned)(127 - k) << 23);
-  if (in_obs) {
-    const int eo = (int)((unsigned)__builtin_amdgcn_readfirstlane((int)*in_obs) >> 23);
-    if (eo == 255 || eo + k > 142) ok = false;      // 2^(eo - 127) * 2^k >= 2^16
+  if (in_obs && !adapted && (eo == 255 || eo + k > 142)) ok = false;      // 2^(eo - 127) * 2^k >= 2^16
+  return bits;
+}
+
+// block 0's first thread reports the launch: UT_SPLIT_RANGE when !ok, one count in *adapt_count when it adapted
+__device__ __forceinline__ void split_scale_report(bool ok, bool adapted, int* status, unsigned* adapt_count) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (!ok && status) atomicOr(status, UT_SPLIT_RANGE);
+    if (adapted && adapt_count) atomicAdd(adapt_count, 1u);
   }
 }
 #endif

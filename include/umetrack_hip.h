@@ -98,8 +98,9 @@ int ut_status_snapshot(ut_handle h, int32_t* dst, void* stream);
 /* 1 (default) or 2: with 2, a ut_backbone / ut_warp_backbone call of >= 1024 crops that fits one workspace pass runs as
  * two half-batches on two internal streams (joined to the caller's stream before the call's work is visible to it), so
  * that the idle tail of one half's launches is filled by the other half's.  Same kernels on the same crops: results
- * are bit-identical (UT_CONV_FP32, and split-fp16 with calibrated scales; with UT_SPLIT_SCALE_DYNAMIC each half takes its own
- * scales).  Not applied between ut_profile_begin / ut_profile_end. */
+ * are bit-identical (UT_CONV_FP32, and split-fp16 with calibrated scales - adaptive ones too, while in band; with
+ * UT_SPLIT_SCALE_DYNAMIC, or an adaptive launch out of band, each half takes its own scales).  Not applied between
+ * ut_profile_begin / ut_profile_end. */
 int ut_set_backbone_lanes(ut_handle h, int lanes);
 
 /* Arithmetic of the 3x3 convolutions of the backbone (all 24 of them: layer1 .. layer4; lib/models/backbone_resnet.py:56-72).
@@ -124,11 +125,13 @@ int ut_set_backbone_lanes(ut_handle h, int lanes);
  *                        than the calibration set gets an ABSOLUTE error, about the one a call at 2^-7 of the calibration maximum
  *                        gets (~4e-9 of the calibration set's largest output; 2^-12 with ut_set_block_fusion(h, 0): the fused
  *                        layer1 block scales its intermediate by an L1 bound, not by a calibrated word), not a relative one.
- *                        UT_SPLIT_SCALE_DYNAMIC, ut_calibrate_split on representative crops, or UT_CONV_FP32 avoid it;
+ *                        UT_SPLIT_SCALE_DYNAMIC, UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE (for a whole launch that dim), ut_calibrate_split
+ *                        on representative crops, or UT_CONV_FP32 avoid it;
  *                      - an infinity or a NaN has no scale, and (calibrated scales) an activation of 32 x the calibration maximum
  *                        or more would saturate the first piece: both set a sticky status bit that the next status read
  *                        (ut_poll_status, or any call that reads the index checks in UT_CHECK_SYNC mode) returns as
- *                        UT_E_INVALID "range check: ...".  Results of that call are then not to be used.
+ *                        UT_E_INVALID "range check: ...".  Results of that call are then not to be used.  With
+ *                        UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE only an infinity or a NaN does.
  *                      Where a tensor's scale word comes from: ut_set_split_scale.
  *                      The mode is chosen once per ut_backbone / ut_warp_backbone call, for every 3x3 convolution of it:
  *                      split for calls of >= 2 x (compute units) crops (512 on MI355X: their 256-row tiles then fill the
@@ -152,9 +155,28 @@ int ut_set_conv_arithmetic(ut_handle h, int mode);
  *      largest magnitude its producer stored in THIS call with the calibrated word: an input of 32 x the calibration maximum or
  *      more is reported as "range check" (see UT_CONV_SPLIT_F16), never silently saturated.
  *  UT_SPLIT_SCALE_DYNAMIC  the scale word is the one the producing kernel left in this call (the largest magnitude over the
- *      launch): adapts to any input, but a crop's low-order bits then depend on its batch (at the 1e-7 level). */
-enum { UT_SPLIT_SCALE_CALIBRATED = 0, UT_SPLIT_SCALE_DYNAMIC = 1 };
+ *      launch): adapts to any input, but a crop's low-order bits then depend on its batch (at the 1e-7 level).
+ *  UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE  calibrated, but never refuses a finite input.  Every split launch compares the largest
+ *      magnitude its producer stored in this call (M) with its calibrated word (W = 2^4 x the calibration maximum), on the device,
+ *      from words every workgroup reads alike, so the choice is uniform over the launch, needs no host synchronisation and is
+ *      made again at every replay of a captured hipGraph:
+ *      - in band - M zero, or M at least 2^-7 of the calibration maximum (its exponent at most 11 below W's) and below the
+ *        calibrated guard (32 x the calibration maximum or more): the launch is bit-identical to UT_SPLIT_SCALE_CALIBRATED's,
+ *        with every batch, pass, lane and sharding independence of that mode;
+ *      - out of band, finite: the launch is bit-identical to UT_SPLIT_SCALE_DYNAMIC's on the same input (scale from M, no guard,
+ *        the fused layer1 block's intermediate bounded from M) and carries that mode's batch dependence (~1e-7); no status bit is
+ *        set, and the handle's adaptation counter (ut_get_split_adaptations) counts the launch once;
+ *      - an infinity or a NaN: "range check", as in every mode.
+ *      The unit is the LAUNCH, not the crop: a single dim crop inside a normal batch leaves the launch in band and keeps the
+ *      absolute error floor of UT_CONV_SPLIT_F16 for that crop.  Cost: a few scalar instructions per workgroup.  Calibration
+ *      passes run with dynamic scales in every mode; the built-in calibration runs when split mode meets an uncalibrated handle,
+ *      as for UT_SPLIT_SCALE_CALIBRATED. */
+enum { UT_SPLIT_SCALE_CALIBRATED = 0, UT_SPLIT_SCALE_DYNAMIC = 1, UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE = 2 };
 int ut_set_split_scale(ut_handle h, int mode);
+/* UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE: *out = the split launches that adapted since the counter was last zeroed (one device word
+ * per handle, both lanes count into it; zeroed by ut_create and by every calibration).  Synchronises `stream`; reset != 0 then zeroes the counter (stream
+ * ordered, by a kernel).  Not to be called while `stream` is being captured. */
+int ut_get_split_adaptations(ut_handle h, uint32_t* out, int reset, void* stream);
 /* Replace the calibrated scale words by those of `crops` (device fp32 [n_crops,96,96], the tensor ut_backbone takes;
  * n_crops == 0: the built-in set).  Synchronous; results of later split-mode calls change at the 1e-7 level with it. */
 int ut_calibrate_split(ut_handle h, const float* crops, int n_crops, void* stream);
