@@ -1,5 +1,5 @@
 // Small dense fp64 helpers shared by the head kernels; host+device so that they can be unit
-// tested (and sanitised) in a plain CPU build (tests/cpu_math_harness.cpp).
+// tested (and sanitised) in a plain CPU build (tests/test_head_math_host.py).
 #pragma once
 #include <math.h>
 #ifndef __HIPCC__
@@ -112,6 +112,10 @@ UT_HD inline void jacobi_eig3(double a[3][3], double v[3][3]) {
 // R = V diag(1,1,det(V U^T)) U^T for H = U S V^T (lib/models/model_utils.py:40-49).  Only the two
 // leading left singular vectors are needed: det * v3 u3^T does not depend on the sign of u3, so
 // u3 := u1 x u2 (det U = +1) and the sign is det V.
+// u_c = H v_c / s_c exists only while s_c is above the rounding noise of H v_c (~1e-16 s_1; collinear targets leave
+// s_2 = 4e-19, not 0).  Below kRankTol x s_1 the left basis is completed with a unit vector orthogonal to u1 instead -
+// any one gives a proper rotation with R u1 = v1, and the SVD itself defines no more there - and H = 0 (no u1 either)
+// returns the identity, as the reference's svd(0) = (I, 0, I) does.  Proper rotation for every finite H below ~1e150.
 UT_HD inline void kabsch_rotation(const double h[3][3], double r[3][3]) {
   double ata[3][3], v[3][3];
   for (int i = 0; i < 3; ++i)
@@ -136,7 +140,9 @@ UT_HD inline void kabsch_rotation(const double h[3][3], double r[3][3]) {
   }
   UT_CMPX(0, 1) UT_CMPX(0, 2) UT_CMPX(1, 2)
 #undef UT_CMPX
+  constexpr double kRankTol = 1e-12;
   double u[3][3];
+  double n1 = 0;      // |H v1|^2 = s_1^2
   for (int c = 0; c < 2; ++c) {
     double n2 = 0;
     for (int i = 0; i < 3; ++i) {
@@ -145,12 +151,27 @@ UT_HD inline void kabsch_rotation(const double h[3][3], double r[3][3]) {
       u[i][c] = s;
       n2 += s * s;
     }
-    if (c == 1) {   // re-orthogonalise against u1
+    if (c == 0) {
+      n1 = n2;
+      if (n1 == 0.0) {   // H = 0 (or below the underflow of its squares): nothing to align
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) r[i][j] = (i == j) ? 1.0 : 0.0;
+        return;
+      }
+    } else {   // re-orthogonalise against u1
       double d = u[0][0] * u[0][1] + u[1][0] * u[1][1] + u[2][0] * u[2][1];
       n2 = 0;
       for (int i = 0; i < 3; ++i) { u[i][1] -= d * u[i][0]; n2 += u[i][1] * u[i][1]; }
+      if (n2 <= kRankTol * kRankTol * n1) {
+        // rank 1: e_k - (e_k . u1) u1 for the axis k on which u1 is smallest (norm^2 = 1 - u1[k]^2 >= 2/3)
+        const double a0 = fabs(u[0][0]), a1 = fabs(u[1][0]), a2 = fabs(u[2][0]);
+        const int k = (a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2);
+        const double uk = (k == 0) ? u[0][0] : (k == 1 ? u[1][0] : u[2][0]);
+        n2 = 0;
+        for (int i = 0; i < 3; ++i) { u[i][1] = ((i == k) ? 1.0 : 0.0) - uk * u[i][0]; n2 += u[i][1] * u[i][1]; }
+      }
     }
-    double inv = n2 > 0 ? 1.0 / sqrt(n2) : 0.0;
+    double inv = 1.0 / sqrt(n2);
     for (int i = 0; i < 3; ++i) u[i][c] *= inv;
   }
   u[0][2] = u[1][0] * u[2][1] - u[2][0] * u[1][1];

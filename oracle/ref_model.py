@@ -177,7 +177,11 @@ def regress(sd, name: str, x: torch.Tensor) -> Dict[str, torch.Tensor]:
     x = _basic_block(sd, f"{p}.0", x, 1, False)
     x = _basic_block(sd, f"{p}.1", x, 1, False)
     x = F.conv2d(x, sd[f"{p}.2.weight"], sd[f"{p}.2.bias"])
-    raw = F.adaptive_avg_pool2d(x, 1).flatten(1)
+    return decode(name, F.adaptive_avg_pool2d(x, 1).flatten(1))
+
+
+def decode(name: str, raw: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The decoders of regress() on its raw outputs [n,d] alone (regressor.py:76-121), in raw's dtype."""
     sl = arch.REG_K_SLICES if name == "_regressor_k" else arch.REG_U_SLICES
     out = {"raw": raw}
     a, b = sl["joint_angles"]

@@ -13,15 +13,13 @@ import torch
 from absolutetrack_amd import _native, pipeline, synth
 from oracle import ref_model, scenarios
 
+from head_cases import ANGLE_TOL, FP32_TOL, METRE_TOL, RAW_TOL, decode_errors, head_oracle as _head_oracle
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 BAND_TOL = 3e-6          # relative error inside the calibrated band, 2^-7 .. the guard, every kernel selection (max seen 1.56e-6)
-FP32_TOL = 5e-6          # the exact-fp32 convolutions against fp64 (max seen 2.23e-6)
 FLOOR_F = 2.0 ** -7      # below this fraction of the calibration maximum the split's error is absolute (the header's floor)
-ANGLE_TOL = 1e-4         # rad
-METRE_TOL = 1e-6         # 1e-3 mm
-RAW_TOL = 1.3e-6         # split regressor's raw outputs, relative to the largest (max seen 3.3e-7)
 
 
 def _dev(a):
@@ -203,19 +201,6 @@ def test_split_layer1_worst_case_in_the_guarded_band(fusion):
         eng.close()
 
 
-def _head_oracle(sd64, feat, k, x, sr, mem_idx, use, hand, temporal, known, skel):
-    fused = ref_model.fuse_views(sd64, feat.double(), k.double(), x.double(), sr)
-    cam0 = x.double()[sr[:, 0]]
-    t = temporal.step(sd64, fused, cam0, mem_idx, use)
-    if known:
-        s = ref_model.skeleton_features(sd64, *skel).expand(t.shape[0], -1, -1, -1)
-        out = ref_model.regress(sd64, "_regressor_k", torch.cat([t, s], 1))
-    else:
-        out = ref_model.regress(sd64, "_regressor_u", t)
-    out["wrist_xfs"] = ref_model.wrist_to_world(hand, cam0, out["wrist_xfs"])
-    return out
-
-
 @pytest.mark.parametrize("known", [True, False])
 def test_split_headline_configuration_against_fp64(known):
     """The benchmark's configuration: UT_CONV_SPLIT_F16 with calibrated scales, 2048 crops = 1024 two-view samples (split
@@ -223,8 +208,11 @@ def test_split_headline_configuration_against_fp64(known):
     memory under moved extrinsics - with a real skeleton (recording_00's hand model, metres).  Profiling asserts that split
     launches ran in the backbone call and in the head call.  The head's outputs against the fp64 oracle head fed the GPU's own
     features, on all 1024 samples; the backbone against fp64 on 16 sampled crops; poll_status clean after every call (the head's
-    calibrated words cover real skeletons and warm memory).  Measured on the MI355X, both regress modes: backbone 1.15e-6; raw
-    3.3e-7 of its largest; joint angles 1.7e-6 rad; rotation entries 4.1e-7; translations 5.5e-8 m; memory 5.6e-7 of its largest."""
+    calibrated words cover real skeletons and warm memory).  Pose columns 38..59 (skeleton scale, sigmas) against the oracle's
+    float64 decode of the GPU's own raw, relative, bounded as in test_gpu_head_edges.py: 4 x the distance of the same decode in
+    fp32 torch, floor 4 fp32 ulp.  Measured on the MI355X, both regress modes: backbone 1.15e-6; raw 3.3e-7 of its largest;
+    joint angles 1.7e-6 rad; rotation entries 4.1e-7; translations 5.5e-8 m; memory 5.6e-7 of its largest; scale 7.2e-8,
+    sigmas 1.16e-7 (relative; allowed 4.8e-7, the 4 ulp floor)."""
     sd = synth.synthetic_state_dict(0)
     sd64 = _sd64(sd)
     n, s = 2048, 1024
@@ -275,6 +263,9 @@ def test_split_headline_configuration_against_fp64(known):
             errs[f"step{step}"] = e
             assert e["raw"] < RAW_TOL and e["angle"] < ANGLE_TOL and e["rot"] < 1e-5 and e["trans"] < METRE_TOL, e
             assert e["mem"] < BAND_TOL, e
+            dec = decode_errors(pose, raw, known, hand, torch.from_numpy(x)[sr[:, 0]])
+            e["decode"] = {g: dec[g] for g in ("scale", "sigmas") if g in dec}
+            assert all(v["ratio"] <= 1.0 for v in e["decode"].values()), e["decode"]
         print(f"\nheadline known={known}:", errs)
     finally:
         eng.close()
