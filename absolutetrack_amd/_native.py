@@ -26,6 +26,7 @@ EXPORTS = (
     "ut_set_backbone_lanes", "ut_status_snapshot", "ut_warp_map", "ut_set_block_fusion", "ut_set_resident_weights",
     "ut_canonical_backbone_weights", "ut_set_split_scale", "ut_calibrate_split", "ut_get_split_calibration",
     "ut_gen_crop_cameras_from_window_points", "ut_get_split_adaptations",
+    "ut_mesh_create", "ut_mesh_destroy", "ut_mesh_counts", "ut_skin_mesh",
 )
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
@@ -78,6 +79,14 @@ def load_library() -> ctypes.CDLL:
     lib.ut_get_memory.argtypes = [vp, f32p, f32p, i32, vp]
     lib.ut_fk.restype = i32
     lib.ut_fk.argtypes = [vp, f32p, i32, f32p, i32, f32p, i32, vp, ctypes.c_float, i32, f32p, vp]
+    lib.ut_mesh_create.restype = i32
+    lib.ut_mesh_create.argtypes = [vp, i32, vp, i32, vp, i32, ctypes.POINTER(vp)]
+    lib.ut_mesh_destroy.restype = i32
+    lib.ut_mesh_destroy.argtypes = [vp]
+    lib.ut_mesh_counts.restype = i32
+    lib.ut_mesh_counts.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.ut_skin_mesh.restype = i32
+    lib.ut_skin_mesh.argtypes = [vp, vp, f32p, i32, f32p, i32, f32p, i32, vp, ctypes.c_float, i32, f32p, f32p, vp]
     lib.ut_gen_crop_cameras.restype = i32
     lib.ut_gen_crop_cameras.argtypes = [vp, vp, vp, f32p, f32p, i32, f32p, f32p, vp, vp, i32, i32, i32, i32, i32, i32,
                                         i32, ctypes.c_double, vp, f32p, f32p, vp, vp, vp, f32p, vp]
@@ -221,6 +230,105 @@ def fk_stateless(hand_model: torch.Tensor, joint_angles: torch.Tensor, wrist_xf:
     if rc != 0:
         raise RuntimeError(f"ut_fk failed ({rc}): {lib.ut_last_error(None).decode()}")
     return out
+
+
+class Mesh:
+    """A hand mesh packed for ut_skin_mesh and resident on one HIP device (ut_mesh_create): sparse bone weights (at most
+    MESH_MAX_INFLUENCES per vertex) and the vertex -> triangle table of the normals.  vertices [V,3], triangles [T,3],
+    dense_bone_weights [V,17]: numpy arrays or tensors, read on the host.  Raises ValueError when the library refuses the
+    mesh (the message says which rule was broken); nothing is launched then.  Freed on close() / garbage collection."""
+
+    def __init__(self, vertices, triangles, dense_bone_weights, device="cuda"):
+        self._h = None
+        self.lib = load_library()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise NativeLibraryError("a Mesh lives on a HIP device (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+
+        def host(x, dtype, tail):
+            if isinstance(x, torch.Tensor):
+                x = x.detach().cpu().numpy()
+            x = np.ascontiguousarray(x, dtype)
+            if x.ndim != 2 or x.shape[1] != tail:
+                raise ValueError(f"expected an unbatched [*, {tail}] array, got {x.shape}")
+            return x
+        v, t, w = host(vertices, np.float32, 3), host(triangles, np.int32, 3), host(dense_bone_weights, np.float32, 17)
+        if w.shape[0] != v.shape[0]:
+            raise ValueError(f"{v.shape[0]} vertices but {w.shape[0]} rows of bone weights")
+        h = ctypes.c_void_p()
+        rc = self.lib.ut_mesh_create(v.ctypes.data, v.shape[0], t.ctypes.data, t.shape[0], w.ctypes.data, self.device.index,
+                                     ctypes.byref(h))
+        if rc != 0:
+            msg = f"ut_mesh_create failed ({rc}): {self.lib.ut_last_error(None).decode()}"
+            raise (ValueError if rc in (-1, -4) else RuntimeError)(msg)
+        self._h = h
+        self.n_vertices, self.n_triangles = v.shape[0], t.shape[0]
+
+    def counts(self) -> Tuple[int, int]:
+        nv, nt = ctypes.c_int(), ctypes.c_int()
+        rc = self.lib.ut_mesh_counts(self._h, ctypes.byref(nv), ctypes.byref(nt))
+        if rc != 0:
+            raise RuntimeError(f"ut_mesh_counts failed ({rc}): {self.lib.ut_last_error(None).decode()}")
+        return nv.value, nt.value
+
+    def close(self):
+        if self._h is not None:
+            self.lib.ut_mesh_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def skin_mesh(mesh: Mesh, hand_model: torch.Tensor, joint_angles: torch.Tensor, wrist_xf: torch.Tensor,
+              mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0, normals: bool = False, ja_stride: int = 22,
+              xf_stride: int = 16, n: Optional[int] = None, out: Optional[torch.Tensor] = None,
+              out_normals: Optional[torch.Tensor] = None, engine: Optional["HipEngine"] = None):
+    """ut_skin_mesh: vertices [n,V,3], or (vertices, normals) with normals=True.  hand_model [1|n,321] (ut_fk's blob);
+    joint_angles / wrist_xf either packed [n,22] / [n,4,4], or - with n given - views into a pose-record buffer with explicit
+    strides in floats, as for HipEngine.fk.  out / out_normals: preallocated fp32 [n,V,3] to write into.  All tensors on the
+    mesh's device; `engine` only lends its handle for error reporting (the kernel needs no network weights)."""
+    lib, d = mesh.lib, mesh.device
+    if mesh._h is None:
+        raise ValueError("the Mesh has been closed")
+    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
+    if n is None:
+        joint_angles = _need(joint_angles, torch.float32, d, "joint_angles").reshape(-1, 22)
+        wrist_xf = _need(wrist_xf, torch.float32, d, "wrist_xf").reshape(-1, 16)
+        n = joint_angles.shape[0]
+        if wrist_xf.shape[0] != n:
+            raise ValueError("joint_angles / wrist_xf batch mismatch")
+    elif joint_angles.device != d or wrist_xf.device != d or joint_angles.dtype != torch.float32 or wrist_xf.dtype != torch.float32:
+        raise ValueError(f"strided pose views must be fp32 on {d}")
+    if hand_model.shape[0] not in (1, n) and n:
+        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
+    if mirror is not None:
+        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
+        if mirror.shape[0] != n:
+            raise ValueError("mirror batch mismatch")
+    shape = (n, mesh.n_vertices, 3)
+
+    def buf(t, name):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=d)
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != d or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 {shape} tensor on {d}")
+        return t
+    out = buf(out, "out")
+    if normals or out_normals is not None:
+        out_normals = buf(out_normals, "out_normals")
+    h = engine._h if engine is not None else None
+    with torch.cuda.device(d):
+        rc = lib.ut_skin_mesh(h, mesh._h, _ptr(hand_model), hand_model.shape[0], _ptr(joint_angles), ja_stride, _ptr(wrist_xf),
+                              xf_stride, _ptr(mirror), ctypes.c_float(t_scale), n, _ptr(out), _ptr(out_normals), _stream(d))
+    if rc != 0:
+        raise RuntimeError(f"ut_skin_mesh failed ({rc}): {lib.ut_last_error(h).decode()}")
+    return (out, out_normals) if out_normals is not None else out
 
 
 def gen_crop_cameras(cam_params: torch.Tensor, camera_angles: torch.Tensor, hand_model: torch.Tensor,

@@ -26,52 +26,8 @@ __global__ __launch_bounds__(256) void fk_kernel(const float* __restrict__ hand_
   __shared__ float s_frame[FK_P][17][12];
   const int tid = threadIdx.x;
   const int base = blockIdx.x * FK_P;
-  // ---- phase 1: joint local transforms (20 per pose) and the wrist frames (slots 0, 1)
-  if (tid < FK_P * 20) {
-    const int pl = tid / 20, q = tid - pl * 20;
-    const int i = base + pl;
-    if (i < n) {
-      const float* hm = hand_model + (size_t)(n_models == 1 ? 0 : i) * 321;
-      const M34 l = joint_local(hm + 3 * q, hm + 66 + 3 * q, ja[(size_t)i * ja_stride + q]);
-#pragma unroll
-      for (int k = 0; k < 12; ++k) s_local[pl][q][k] = l.m[k];
-    }
-  } else if (tid < FK_P * 20 + FK_P) {
-    const int pl = tid - FK_P * 20;
-    const int i = base + pl;
-    if (i < n) {
-      const float* x = xf + (size_t)i * xf_stride;
-      M34 w;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) w.m[k] = x[k];
-      w.m[3] *= t_scale; w.m[7] *= t_scale; w.m[11] *= t_scale;
-      if (mirror && mirror[i] == 1) { w.m[0] = -w.m[0]; w.m[4] = -w.m[4]; w.m[8] = -w.m[8]; }
-#pragma unroll
-      for (int k = 0; k < 12; ++k) { s_frame[pl][0][k] = w.m[k]; s_frame[pl][1][k] = w.m[k]; }
-    }
-  }
-  __syncthreads();
-  // ---- phase 2: finger chains
-  if (tid < FK_P * 5) {
-    const int pl = tid / 5, f = tid - pl * 5;
-    if (base + pl < n) {
-      M34 t;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) t.m[k] = s_frame[pl][0][k];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        M34 l;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) l.m[k] = s_local[pl][4 * f + j][k];
-        t = mul34(t, l);
-        if (j >= 1) {
-#pragma unroll
-          for (int k = 0; k < 12; ++k) s_frame[pl][2 + 3 * f + (j - 1)][k] = t.m[k];
-        }
-      }
-    }
-  }
-  __syncthreads();
+  // ---- phases 1, 2: the skinning frames (ut_fk.h; mesh.hip builds its frames with the same code)
+  skinning_frames_lds<FK_P>(s_local, s_frame, hand_model, n_models, ja, ja_stride, xf, xf_stride, mirror, t_scale, n, base);
   // ---- phase 3: linear blend skinning, frames visited in ascending order like the dense reference sum
   if (tid < FK_P * 21) {
     const int pl = tid / 21, l = tid - pl * 21;

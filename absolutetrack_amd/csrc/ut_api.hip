@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -1400,6 +1401,134 @@ int ut_fk(ut_handle h, const float* hand_model, int n_models, const float* joint
   ON_DEVICE_IF(h);
   HIPCHK(h, ut::launch_fk(hand_model, n_models, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale, n, out,
                           (hipStream_t)stream));
+  return UT_OK;
+}
+
+struct ut_mesh {
+  int device = 0;
+  int n_vertices = 0, n_triangles = 0;
+  void* verts = nullptr;          // float4 [n_vertices][2], see launch_skin_mesh
+  uint32_t* csr_off = nullptr;    // [n_vertices + 1]
+  uint32_t* csr_ent = nullptr;    // [3 * n_triangles]
+};
+static_assert(UT_MESH_MAX_VERTICES == ut::MESH_MAX_VERTICES && UT_MESH_MAX_VERTICES <= 65536, "vertex cap");
+
+int ut_mesh_create(const float* vertices, int n_vertices, const int32_t* triangles, int n_triangles,
+                   const float* dense_bone_weights, int device, ut_mesh** out) {
+  if (out) *out = nullptr;
+  if (!out || !vertices || !dense_bone_weights || (!triangles && n_triangles != 0))
+    return fail(nullptr, UT_E_INVALID, "ut_mesh_create: null argument");
+  if (n_vertices <= 0) return fail(nullptr, UT_E_INVALID, "ut_mesh_create: the mesh has no vertices");
+  if (n_triangles < 0) return fail(nullptr, UT_E_INVALID, "ut_mesh_create: negative triangle count");
+  char msg[256];
+  if (n_vertices > UT_MESH_MAX_VERTICES) {
+    snprintf(msg, sizeof msg, "ut_mesh_create: %d vertices, more than UT_MESH_MAX_VERTICES (%d) that fit a workgroup's LDS",
+             n_vertices, UT_MESH_MAX_VERTICES);
+    return fail(nullptr, UT_E_UNSUPPORTED, msg);
+  }
+  if (n_triangles > (1 << 24)) return fail(nullptr, UT_E_UNSUPPORTED, "ut_mesh_create: more than 2^24 triangles");
+  // ---- pack on the host: (x, y, z, bones) | weights per vertex, slots in ascending bone order
+  const size_t nv = (size_t)n_vertices, nt = (size_t)n_triangles;
+  std::vector<float> packed(nv * 8, 0.f);
+  for (size_t v = 0; v < nv; ++v) {
+    float* p = &packed[v * 8];
+    for (int k = 0; k < 3; ++k) {
+      if (!std::isfinite(vertices[3 * v + k])) {
+        snprintf(msg, sizeof msg, "ut_mesh_create: vertex %zu has a coordinate that is not finite", v);
+        return fail(nullptr, UT_E_INVALID, msg);
+      }
+      p[k] = vertices[3 * v + k];
+    }
+    uint32_t bones = 0;
+    int slots = 0;
+    for (int f = 0; f < 17; ++f) {
+      const float w = dense_bone_weights[17 * v + f];
+      if (!std::isfinite(w)) {
+        snprintf(msg, sizeof msg, "ut_mesh_create: weight [%zu][%d] is not finite", v, f);
+        return fail(nullptr, UT_E_INVALID, msg);
+      }
+      if (w == 0.f) continue;
+      if (slots == UT_MESH_MAX_INFLUENCES) {
+        snprintf(msg, sizeof msg, "ut_mesh_create: vertex %zu has more than %d non-zero bone weights", v,
+                 UT_MESH_MAX_INFLUENCES);
+        return fail(nullptr, UT_E_UNSUPPORTED, msg);
+      }
+      bones |= (uint32_t)f << (8 * slots);
+      p[4 + slots] = w;
+      ++slots;
+    }
+    memcpy(&p[3], &bones, sizeof bones);
+  }
+  // ---- vertex -> incident triangles, ascending triangle order, each entry rotated so that the vertex comes first
+  std::vector<uint32_t> off(nv + 1, 0), ent(nt * 3 + 1, 0);
+  for (size_t t = 0; t < nt; ++t)
+    for (int k = 0; k < 3; ++k) {
+      const int32_t v = triangles[3 * t + k];
+      if (v < 0 || v >= n_vertices) {
+        snprintf(msg, sizeof msg, "ut_mesh_create: triangle %zu names vertex %d, outside [0, %d)", t, (int)v, n_vertices);
+        return fail(nullptr, UT_E_INVALID, msg);
+      }
+      ++off[(size_t)v + 1];
+    }
+  for (size_t v = 0; v < nv; ++v) off[v + 1] += off[v];
+  {
+    std::vector<uint32_t> fill(off.begin(), off.end() - 1);
+    for (size_t t = 0; t < nt; ++t)
+      for (int k = 0; k < 3; ++k) {
+        const uint32_t v = (uint32_t)triangles[3 * t + k];
+        const uint32_t a = (uint32_t)triangles[3 * t + (k + 1) % 3], b = (uint32_t)triangles[3 * t + (k + 2) % 3];
+        ent[fill[v]++] = a | (b << 16);
+      }
+  }
+  // ---- upload
+  DeviceScope scope(device);
+  if (scope.err != hipSuccess) return fail(nullptr, UT_E_HIP, "hipSetDevice", scope.err);
+  ut_mesh* m = new ut_mesh();
+  m->device = device; m->n_vertices = n_vertices; m->n_triangles = n_triangles;
+  hipError_t e = hipMalloc(&m->verts, packed.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->csr_off, off.size() * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->csr_ent, ent.size() * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpy(m->verts, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->csr_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->csr_ent, ent.data(), ent.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(m->verts); (void)hipFree(m->csr_off); (void)hipFree(m->csr_ent);
+    delete m;
+    return fail(nullptr, UT_E_HIP, "ut_mesh_create: upload", e);
+  }
+  *out = m;
+  return UT_OK;
+}
+
+int ut_mesh_destroy(ut_mesh* m) {
+  if (!m) return UT_OK;
+  DeviceScope scope(m->device);
+  (void)hipFree(m->verts); (void)hipFree(m->csr_off); (void)hipFree(m->csr_ent);
+  delete m;
+  return UT_OK;
+}
+
+int ut_mesh_counts(const ut_mesh* m, int* n_vertices, int* n_triangles) {
+  if (!m) return fail(nullptr, UT_E_INVALID, "ut_mesh_counts: null mesh");
+  if (n_vertices) *n_vertices = m->n_vertices;
+  if (n_triangles) *n_triangles = m->n_triangles;
+  return UT_OK;
+}
+
+int ut_skin_mesh(ut_handle h, const ut_mesh* mesh, const float* hand_model, int n_models, const float* joint_angles,
+                 int ja_stride, const float* wrist_xf, int xf_stride, const int64_t* mirror, float t_scale, int n,
+                 float* out_vertices, float* out_normals, void* stream) {
+  if (!mesh) return fail(h, UT_E_INVALID, "ut_skin_mesh: null mesh");
+  if (h && h->device != mesh->device) return fail(h, UT_E_INVALID, "ut_skin_mesh: the mesh lives on another device than the handle");
+  if (n == 0) return UT_OK;
+  if (!hand_model || !joint_angles || !wrist_xf || !out_vertices || n < 0 || (n_models != 1 && n_models != n) ||
+      ja_stride < 22 || xf_stride < 16)
+    return fail(h, UT_E_INVALID, "ut_skin_mesh: bad argument");
+  DeviceScope scope(mesh->device);
+  if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
+  HIPCHK(h, ut::launch_skin_mesh(hand_model, n_models, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale, n,
+                                 mesh->verts, mesh->csr_off, mesh->csr_ent, mesh->n_vertices, out_vertices, out_normals,
+                                 (hipStream_t)stream));
   return UT_OK;
 }
 

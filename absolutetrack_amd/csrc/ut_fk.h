@@ -51,6 +51,67 @@ __device__ inline M34 joint_local(const float* axis, const float* rest, float an
 }
 
 
+// The 17 skinning frames of P poses (base .. base + P - 1, those below n) into s_frame, by a workgroup of at least 21 * P
+// threads, operands through LDS so that no thread indexes a private array dynamically: (1) one thread per (pose, joint)
+// builds the joint's local transform (sin/cos) while one per pose writes the wrist frames (slots 0, 1: translation times
+// t_scale, column 0 negated where mirror[i] == 1), (2) one thread per (pose, finger) multiplies the chain wrist*L0*L1*L2*L3
+// and keeps the frames after 2, 3, 4 joints.  Ends on a barrier: every thread of the workgroup must call it, and may read
+// s_frame when it returns.  Shared by fk.hip (landmarks) and mesh.hip (mesh vertices): one arithmetic, one order.
+template <int P>
+__device__ inline void skinning_frames_lds(float (&s_local)[P][20][12], float (&s_frame)[P][17][12],
+                                           const float* __restrict__ hand_model, int n_models,
+                                           const float* __restrict__ ja, int ja_stride, const float* __restrict__ xf,
+                                           int xf_stride, const int64_t* __restrict__ mirror, float t_scale, int n,
+                                           int base) {
+  const int tid = threadIdx.x;
+  // ---- phase 1: joint local transforms (20 per pose) and the wrist frames (slots 0, 1)
+  if (tid < P * 20) {
+    const int pl = tid / 20, q = tid - pl * 20;
+    const int i = base + pl;
+    if (i < n) {
+      const float* hm = hand_model + (size_t)(n_models == 1 ? 0 : i) * 321;
+      const M34 l = joint_local(hm + 3 * q, hm + 66 + 3 * q, ja[(size_t)i * ja_stride + q]);
+#pragma unroll
+      for (int k = 0; k < 12; ++k) s_local[pl][q][k] = l.m[k];
+    }
+  } else if (tid < P * 20 + P) {
+    const int pl = tid - P * 20;
+    const int i = base + pl;
+    if (i < n) {
+      const float* x = xf + (size_t)i * xf_stride;
+      M34 w;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) w.m[k] = x[k];
+      w.m[3] *= t_scale; w.m[7] *= t_scale; w.m[11] *= t_scale;
+      if (mirror && mirror[i] == 1) { w.m[0] = -w.m[0]; w.m[4] = -w.m[4]; w.m[8] = -w.m[8]; }
+#pragma unroll
+      for (int k = 0; k < 12; ++k) { s_frame[pl][0][k] = w.m[k]; s_frame[pl][1][k] = w.m[k]; }
+    }
+  }
+  __syncthreads();
+  // ---- phase 2: finger chains
+  if (tid < P * 5) {
+    const int pl = tid / 5, f = tid - pl * 5;
+    if (base + pl < n) {
+      M34 t;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) t.m[k] = s_frame[pl][0][k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        M34 l;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) l.m[k] = s_local[pl][4 * f + j][k];
+        t = mul34(t, l);
+        if (j >= 1) {
+#pragma unroll
+          for (int k = 0; k < 12; ++k) s_frame[pl][2 + 3 * f + (j - 1)][k] = t.m[k];
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
 // 21 landmarks [63] of one pose.  hm: packed hand model (321 floats, see include/umetrack_hip.h); a: 22 joint
 // angles; wrist: root-to-world transform.
 __device__ inline void skin_landmarks_dev(const float* __restrict__ hm, const float* __restrict__ a, const M34& wrist,

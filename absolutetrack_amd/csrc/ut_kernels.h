@@ -266,6 +266,21 @@ hipError_t launch_fk(const float* hand_model, int n_models, const float* ja, int
                      const float* xf, int xf_stride, const int64_t* mirror, float t_scale, int n,
                      float* out, hipStream_t s);
 
+// Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
+//  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
+//           bone, unused slots weight 0 / bone 0
+//  csr_off  [nv + 1], csr_ent [3 * n_triangles]: per vertex its incident triangles in ascending triangle order, each entry the
+//           triangle's other two vertices in winding order, first | second << 16
+//  out_v [n,nv,3]; out_n [n,nv,3] or null (no normals).
+// The posed vertices of a pose stay in LDS until its normals are done: 12 nv bytes of dynamic LDS next to 4848 static ones.
+// MESH_MAX_VERTICES is what fits the 64 KB a workgroup gets without a per-device function attribute (65536 - 4848 = 60688
+// >= 12 * 5056); it also keeps a vertex index in 16 bits (csr_ent).  Public as UT_MESH_MAX_VERTICES.
+constexpr int MESH_MAX_VERTICES = 5056;
+hipError_t launch_skin_mesh(const float* hand_model, int n_models, const float* ja, int ja_stride, const float* xf,
+                            int xf_stride, const int64_t* mirror, float t_scale, int n, const void* verts,
+                            const uint32_t* csr_off, const uint32_t* csr_ent, int nv, float* out_v, float* out_n,
+                            hipStream_t s);
+
 // Batched crop-camera generation (cropgen.hip): one candidate = one (frame, hand) label pose.
 struct CropGenArgs {
   const double* cam_params;     // [n_frames*n_cams,32] source camera rows (layout of ut_warp_crops)

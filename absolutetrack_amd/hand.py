@@ -156,3 +156,63 @@ def skin_landmarks(hand_model: HandModel, joint_angles: torch.Tensor, wrist_tran
                                joint_angles.reshape(n, 22).to(dev, torch.float32),
                                wrist_transforms.reshape(n, 4, 4).to(dev, torch.float32))
     return out.reshape(lead + (21, 3)).to(src_device)
+
+
+_MESH_FIELDS = ("mesh_vertices", "mesh_triangles", "dense_bone_weights")
+_mesh_cache: list = []      # [(key, tensors kept alive, _native.Mesh)], most recent first
+
+
+def _mesh_tensors(hand_model: HandModel) -> tuple:
+    tensors = tuple(getattr(hand_model, f) for f in _MESH_FIELDS)
+    if any(t is None for t in tensors):
+        raise ValueError("the hand model carries no mesh (mesh_vertices, mesh_triangles and dense_bone_weights are needed)")
+    if any(t.dim() != 2 for t in tensors):
+        raise ValueError("mesh fields must be unbatched ([V,3], [T,3], [V,17]); got "
+                         + ", ".join(str(tuple(t.shape)) for t in tensors))
+    return tensors
+
+
+def device_mesh(hand_model: HandModel, dev: torch.device) -> "_native.Mesh":
+    """The model's mesh packed for csrc/mesh.hip (sparse weights, vertex -> triangle table) and resident on `dev`, cached
+    like device_blob: keyed on tensor identity + in-place version counters.  ValueError for a model without a mesh, for
+    batched mesh fields (one mesh per launch) and for a mesh the library refuses."""
+    tensors = _mesh_tensors(hand_model)
+    dev = torch.device(dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (str(dev),) + tuple((id(t), t._version) for t in tensors)
+    for i, (k, _keep, mesh) in enumerate(_mesh_cache):
+        if k == key:
+            if i:
+                _mesh_cache.insert(0, _mesh_cache.pop(i))
+            return mesh
+    mesh = _native.Mesh(*tensors, device=dev)
+    _mesh_cache.insert(0, (key, tensors, mesh))
+    del _mesh_cache[8:]
+    return mesh
+
+
+def skin_mesh(hand_model: HandModel, joint_angles: torch.Tensor, wrist_transforms: torch.Tensor, normals: bool = False,
+              mirror: Optional[torch.Tensor] = None):
+    """[...,22] joint angles + [...,4,4] wrist transforms -> the posed mesh [...,V,3], or (vertices, unit normals) with
+    normals=True: the reference's _skin_points (lib/common/hand_skinning.py:154-186) on mesh_vertices /
+    dense_bone_weights, on the HIP kernel csrc/mesh.hip (no CPU implementation).  Leading dims as for skin_landmarks;
+    the skeleton fields are unbatched or carry them, the mesh fields are unbatched.  mirror (optional, [...] of 0 / 1):
+    where 1, column 0 of the wrist transform is negated on the device - the right-hand convention of
+    lib/tracker/perspective_crop.py:48-49 - and the normals are kept pointing outwards."""
+    lead = tuple(joint_angles.shape[:-1])
+    n = int(np.prod(lead)) if lead else 1
+    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
+    if model_lead not in ((), lead):
+        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
+    _mesh_tensors(hand_model)                    # a model without a usable mesh is refused before a device is needed
+    src_device = joint_angles.device
+    dev = src_device if src_device.type == "cuda" else fk_device()
+    res = _native.skin_mesh(device_mesh(hand_model, dev), device_blob(hand_model, dev),
+                            joint_angles.reshape(n, 22).to(dev, torch.float32),
+                            wrist_transforms.reshape(n, 4, 4).to(dev, torch.float32),
+                            mirror=None if mirror is None else mirror.reshape(n).to(dev, torch.int64), normals=normals)
+    shape = lead + (hand_model.mesh_vertices.shape[0], 3)
+    if normals:
+        return res[0].reshape(shape).to(src_device), res[1].reshape(shape).to(src_device)
+    return res.reshape(shape).to(src_device)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native, arch, geometry
-from .hand import HandModel
+from .hand import HandModel, device_mesh
 from .tracker import (HandTrackerOpts, MAX_VIEW_NUM, SingleHandPose, gen_crop_cameras_from_pose,
                       network_camera_inputs)
 
@@ -270,9 +270,14 @@ class HotPath:
     it wherever the records are consumed - raises IndexError for it."""
 
     def __init__(self, engine: _native.HipEngine, hand_model_mm: HandModel, known_skeleton: bool = True,
-                 remap_mode: int = _native.UT_REMAP_CV2_FIXED, keep_crops: bool = False):
+                 remap_mode: int = _native.UT_REMAP_CV2_FIXED, keep_crops: bool = False, mesh: bool = False,
+                 mesh_normals: bool = False):
         """keep_crops: materialise the fp32 crop tensor (ut_warp_crops + ut_backbone, the crops are then in
-        `self.crops`) instead of the fused ut_warp_backbone, whose crops stay u8 in the engine's workspace."""
+        `self.crops`) instead of the fused ut_warp_backbone, whose crops stay u8 in the engine's workspace.
+        mesh: every step also poses the hand model's mesh (ut_skin_mesh on the step's pose records, read in place like
+        the FK reads them; right hands un-mirrored by hand_idx) into `self.mesh_vertices` [S,V,3] in mm, and with
+        mesh_normals the outward unit normals into `self.mesh_normals`.  Needs a hand model with a mesh; the returned
+        records are the same with and without it."""
         self.engine = engine
         self.keep_crops = keep_crops
         self.mode = _native.UT_MODE_KNOWN if known_skeleton else _native.UT_MODE_UNKNOWN
@@ -285,6 +290,11 @@ class HotPath:
         if known_skeleton:   # mm -> m (lib/tracker/tracker.py:361-367)
             self.skel = torch.stack([hand_model_mm.joint_rotation_axes.float(),
                                      hand_model_mm.joint_rest_positions.float() * 0.001])[None].contiguous().to(dev)
+        self.mesh = None
+        self.mesh_vertices = self.mesh_normals = None
+        self._mesh_normals_on = bool(mesh_normals)
+        if mesh or mesh_normals:
+            self.mesh = device_mesh(hand_model_mm, dev)
         self._bufs = None
 
     def _buffers(self, b: FrameBatch):
@@ -294,6 +304,10 @@ class HotPath:
             self._bufs = (key, torch.empty(b.n_crops if self.keep_crops else 0, arch.CROP, arch.CROP, device=dev),
                           torch.empty(b.n_crops, arch.FEAT_CH, arch.FEAT_HW, arch.FEAT_HW, device=dev),
                           torch.empty(b.n_samples, RECORD, device=dev))
+            if self.mesh is not None:
+                shape = (b.n_samples, self.mesh.n_vertices, 3)
+                self.mesh_vertices = torch.empty(shape, device=dev)
+                self.mesh_normals = torch.empty(shape, device=dev) if self._mesh_normals_on else None
             self.engine.reserve(b.n_crops, b.n_samples, b.n_slots)
         return self._bufs[1:]
 
@@ -314,6 +328,10 @@ class HotPath:
             # FK consumes the pose records in place (row stride 60): metres -> mm, right hands un-mirrored
             kp = eng.fk(self.hand_blob, pose, pose[:, 22:], mirror=b.hand_idx, t_scale=1000.0,
                         ja_stride=arch.POSE_REC, xf_stride=arch.POSE_REC, n=s, out=self._kp_buf(s))
+            if self.mesh is not None:
+                _native.skin_mesh(self.mesh, self.hand_blob, pose, pose[:, 22:], mirror=b.hand_idx, t_scale=1000.0,
+                                  ja_stride=arch.POSE_REC, xf_stride=arch.POSE_REC, n=s, out=self.mesh_vertices,
+                                  out_normals=self.mesh_normals, engine=eng)
         rec[:, : arch.POSE_REC].copy_(pose)
         rec[:, arch.POSE_REC:].copy_(kp.reshape(s, -1))
         return rec

@@ -18,7 +18,7 @@ import torch
 
 from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
-from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks
+from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
 
 logger = logging.getLogger(__name__)
@@ -70,6 +70,18 @@ def landmarks_from_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, h
     if hit is not None:
         return hit
     return skin_landmarks_np(hand_model, hand_pose.joint_angles, _left_handed(hand_pose.wrist_xform, hand_idx))
+
+
+def mesh_from_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, hand_idx: int, normals: bool = False):
+    """World-space mesh vertices [V,3] of a pose, or (vertices, unit normals) with normals=True: the mesh twin of
+    landmarks_from_hand_pose.  The hand model is a left hand: right hands get column 0 of the wrist transform negated, on
+    the device (the same values as _left_handed gives), so that the normals of both hands point outwards."""
+    res = skin_mesh(hand_model, torch.from_numpy(np.asarray(hand_pose.joint_angles)).float(),
+                    torch.from_numpy(np.asarray(hand_pose.wrist_xform)).float(), normals=normals,
+                    mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
+    if normals:
+        return res[0].cpu().numpy(), res[1].cpu().numpy()
+    return res.cpu().numpy()
 
 
 def _visible_counts(cameras: List[CameraModel], landmarks_world: np.ndarray) -> List[int]:

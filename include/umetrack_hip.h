@@ -296,6 +296,44 @@ int ut_fk(ut_handle h, const float* hand_model, int n_models, const float* joint
           int ja_stride, const float* wrist_xf, int xf_stride, const int64_t* mirror, float t_scale,
           int n, float* out, void* stream);
 
+/* The hand model's triangle mesh, posed: lib/common/hand_skinning.py:56-67,130-186 (_lbs, _get_skinned_vertices, _skin_points)
+ * with points = HandModel.mesh_vertices and skin_mat = HandModel.dense_bone_weights (lib/common/hand.py:59-61) - the function
+ * whose 21-point instance is skin_landmarks / ut_fk - plus per-vertex normals, which the reference has no code for.
+ *
+ * ut_mesh_create packs a mesh on the host and uploads it to `device` once.  All three arrays are HOST pointers:
+ *  vertices f32 [n_vertices,3] (any unit: the output is in the unit of vertices and of t_scale * translation),
+ *  triangles i32 [n_triangles,3] (n_triangles may be 0), dense_bone_weights f32 [n_vertices,17], one column per skinning
+ *  frame.  The weights are stored sparse, at most 4 non-zero per vertex, in ascending frame order (the order of the
+ *  reference's dense sum); the triangles as a vertex -> incident-triangle table in ascending triangle order.
+ * Refused, with nothing launched, and ut_last_error(NULL) naming the rule:
+ *  UT_E_INVALID      a null pointer, n_vertices <= 0, n_triangles < 0, a triangle index outside [0, n_vertices), a vertex
+ *                    coordinate or a weight that is not finite
+ *  UT_E_UNSUPPORTED  more than 4 non-zero weights on a vertex, n_vertices > UT_MESH_MAX_VERTICES (a pose's vertices stay
+ *                    in the workgroup's LDS), n_triangles > 2^24 */
+typedef struct ut_mesh ut_mesh;
+#define UT_MESH_MAX_VERTICES 5056
+#define UT_MESH_MAX_INFLUENCES 4
+int ut_mesh_create(const float* vertices, int n_vertices, const int32_t* triangles, int n_triangles,
+                   const float* dense_bone_weights, int device, ut_mesh** out);
+int ut_mesh_destroy(ut_mesh* mesh);
+int ut_mesh_counts(const ut_mesh* mesh, int* n_vertices, int* n_triangles);   /* either output may be NULL */
+
+/* Linear blend skinning of `mesh` for a batch of poses, one launch.
+ *  hand_model, n_models, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale, n: as for ut_fk - the 17 skinning
+ *  frames are built by the same code in the same order, so pose records are consumable in place, the translation is multiplied
+ *  by t_scale and column 0 of the wrist transform is negated where mirror[i] == 1.  Of hand_model only axes and rest
+ *  positions are read.
+ *  out_vertices f32 [n,n_vertices,3].
+ *  out_normals  f32 [n,n_vertices,3] or NULL: unit normals, normalise(sum over the vertex's triangles (v, a, b) of
+ *               cross(p[a] - p[v], p[b] - p[v])) - area weighted, pointing out of a mesh whose triangles are counter-clockwise
+ *               seen from outside; the sum is negated where mirror[i] == 1 (the reflection reverses the winding), so normals
+ *               point out of right hands too.  A vertex without a triangle, or with a zero sum, gets (0, 0, 0).
+ * A pose's result does not depend on the batch it is in.  Stream ordered, no allocation, no synchronisation: capturable.
+ * Runs on the mesh's device (and restores the caller's); h may be NULL, a handle of another device is UT_E_INVALID. */
+int ut_skin_mesh(ut_handle h, const ut_mesh* mesh, const float* hand_model, int n_models, const float* joint_angles,
+                 int ja_stride, const float* wrist_xf, int xf_stride, const int64_t* mirror, float t_scale, int n,
+                 float* out_vertices, float* out_normals, void* stream);
+
 /* HandTracker.gen_crop_cameras for a batch of (frame, hand) label poses in one launch
  * (lib/tracker/tracker.py:222-260 -> lib/tracker/perspective_crop.py:136-180 -> lib/common/crop.py:31-82,
  * lib/common/affine.py:34-76) plus the network camera inputs of lib/tracker/tracker.py:333-337.
