@@ -25,19 +25,11 @@
 //
 // MFMA operand roles, LDS row format and swizzles as in conv_patch.hip: weights = "A" (rows = output channel), pixels =
 // "B" (columns): a lane owns one pixel, accumulator register quads are 4 consecutive channels.
-#include <atomic>
-
 #include "ut_kernels.h"
+#include "ut_conv_dev.h"
 
 namespace ut {
 namespace {
-
-typedef float f32x16b __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2b __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8b __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2b __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) char lds_charb;
 
 constexpr int BT_Y = 12, BT_X = 16;                 // output tile
 constexpr int BI_W = BT_X + 2, BI_H = BT_Y + 2;     // intermediate (conv1 output) tile: 18 x 14 = 252 pixels
@@ -57,61 +49,13 @@ constexpr int BP_DIV = (65536 + BP_W - 1) / BP_W;   // r / 20 == (r * BP_DIV) >>
 constexpr int BI_DIV = (65536 + BI_W - 1) / BI_W;   // q / 18 == (q * BI_DIV) >> 16 for q < 256
 constexpr unsigned B_OOB = 0xFFFFFF00u;
 
-__device__ __forceinline__ void b_dma(u32x4b rsrc, unsigned lds_addr, unsigned voffset) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voffset), "s"(lds_addr), "s"(rsrc)
-      : "memory");
-}
-__device__ __forceinline__ u32x4b b_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4b r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
-__device__ __forceinline__ void b_split(float a, float b, unsigned& p0, unsigned& p1) {
-  const f16x2b h = __builtin_bit_cast(f16x2b, __builtin_amdgcn_cvt_pkrtz(a, b));
-  const float ra = a - (float)h[0], rb = b - (float)h[1];
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-// the two pieces of a * s and b * s for a power of two s: the products are exact, so fma(a, s, -h) is the same remainder as
-// (a * s) - h, in one instruction that also converts h (v_fma_mix_f32)
-__device__ __forceinline__ void b_split_scaled(float a, float b, float s, unsigned& p0, unsigned& p1) {
-  const f16x2b h = __builtin_bit_cast(f16x2b, __builtin_amdgcn_cvt_pkrtz(a * s, b * s));
-  const float ra = __builtin_fmaf(a, s, -(float)h[0]), rb = __builtin_fmaf(b, s, -(float)h[1]);
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-// 2^k with max * 2^k in [2^14, 2^15) for a positive finite `max` (1 for 0), and its inverse
-__device__ __forceinline__ void b_pow2_for(float mx, float& scale, float& unscale) {
-  const unsigned bits = __float_as_uint(mx);
-  const int e = (int)(bits >> 23) & 0xFF;
-  int k = (bits << 1) == 0u || e == 255 ? 0 : 141 - e;
-  k = k > 100 ? 100 : k < -100 ? -100 : k;
-  scale = __uint_as_float((unsigned)(127 + k) << 23);
-  unscale = __uint_as_float((unsigned)(127 - k) << 23);
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch p, int tiles_x, int tiles_per_img, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const unsigned smem_addr = (unsigned)(unsigned long)(lds_charb*)smem;
+  const unsigned smem_addr = (unsigned)(unsigned long)(lds_char*)smem;
   constexpr int W1_OFF = 0, W2_OFF = B_W_BYTES, R_OFF = 2 * B_W_BYTES, SLOT_OFF = R_OFF + 2 * B_R_BYTES;
-  auto slot_write = [&](int idx, int v) {
-    asm volatile("ds_write_b32 %0, %1" ::"v"(smem_addr + (unsigned)(SLOT_OFF + 4 * idx)), "v"(v) : "memory");
-  };
-  auto slot_read = [&](int idx) {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(smem_addr + (unsigned)(SLOT_OFF + 4 * idx)) : "memory");
-    return __builtin_amdgcn_readfirstlane(v);
-  };
+  auto slot_addr = [&](int idx) { return smem_addr + (unsigned)(SLOT_OFF + 4 * idx); };      // tile-queue hand-over words
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -133,20 +77,23 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
     const float xmax = !ok ? 0.f
                        : p.in_obs && !adapted ? 65536.f * x_unscale
                                               : __uint_as_float(x_bits);
-    b_pow2_for(xmax * p.wsum1 + p.bmax1, i_scale, i_unscale);
+    // 2^k with bound * 2^k in [2^14, 2^15) for the positive finite bound (1 for 0), and its inverse
+    const unsigned i_bits = __float_as_uint(xmax * p.wsum1 + p.bmax1);
+    const int i_e = (int)(i_bits >> 23) & 0xFF;
+    split_pow2_for(i_e, (i_bits << 1) == 0u || i_e == 255, i_scale, i_unscale);
   }
   const float acc1_scale = x_scale / p.unscale_w1, acc1_unscale = p.unscale_w1 * x_unscale;     // powers of two
   const float acc2_scale = i_scale / p.unscale_w2, acc2_unscale = p.unscale_w2 * i_unscale;
 
-  const u32x4b in_words = b_rsrc(p.in, (unsigned)((size_t)M * C * sizeof(float)));
-  const u32x4b w1_words = b_rsrc(p.w1_split, (unsigned)B_W_BYTES), w2_words = b_rsrc(p.w2_split, (unsigned)B_W_BYTES);
+  const u32x4 in_words = rsrc_words(p.in, (unsigned)((size_t)M * C * sizeof(float)));
+  const u32x4 w1_words = rsrc_words(p.w1_split, (unsigned)B_W_BYTES), w2_words = rsrc_words(p.w2_split, (unsigned)B_W_BYTES);
   const __amdgpu_buffer_rsrc_t o_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)((size_t)M * C * sizeof(float)), 0x00020000);
 
   // ---- both weight tensors -> LDS once: 2 x 36 one-KB blocks, rows 0..31 of ConvW::w_split (conv_split.hip::pack_split_weights)
   for (int k = wave; k < 72; k += B_WAVES) {
-    if (k < 36) b_dma(w1_words, smem_addr + (unsigned)(W1_OFF + k * 1024), (unsigned)(k * 1024 + lane * 16));
-    else b_dma(w2_words, smem_addr + (unsigned)(W2_OFF + (k - 36) * 1024), (unsigned)((k - 36) * 1024 + lane * 16));
+    if (k < 36) dma_piece(w1_words, smem_addr + (unsigned)(W1_OFF + k * 1024), (unsigned)(k * 1024 + lane * 16));
+    else dma_piece(w2_words, smem_addr + (unsigned)(W2_OFF + (k - 36) * 1024), (unsigned)((k - 36) * 1024 + lane * 16));
   }
 
   // ---- per-lane constants of the patch DMA: which patch pixel / channel chunk each of my pieces is
@@ -181,7 +128,7 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
     const int gy = y0 - 2 + pc_py[j], gx = x0 - 2 + pc_px[j];
     const bool ok = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
     const unsigned off = ok ? (unsigned)((((row0 + gy) * W + gx) * C + 4 * pc_c4[j]) * 4) : B_OOB;
-    b_dma(in_words, smem_addr + (unsigned)(R_OFF + buf * B_R_BYTES + k * 1024), off);
+    dma_piece(in_words, smem_addr + (unsigned)(R_OFF + buf * B_R_BYTES + k * 1024), off);
   };
 
   // ---- my pixels.  conv1: intermediate pixel q1 = 32 * wave + fr of the 14x18 raster (the last block has 4 spare lanes);
@@ -215,11 +162,11 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
   for (int j = 0; j < B_MAXP; ++j) issue_piece(j, c_row0, c_y0, c_x0, 0);
   {
     const int t0 = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, q_rsrc, q_off, 0, 0);
-    if (tid == 0) slot_write(2, grid + t0);
+    if (tid == 0) slot_write(slot_addr(2), grid + t0);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
-  int next = slot_read(2);
+  int next = slot_read(slot_addr(2));
   int cur = 0;
   unsigned out_bits = 0;
 
@@ -236,24 +183,24 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
 #pragma unroll
     for (int kg = 0; kg < 4; ++kg) {
       unsigned a0, a1, a2, a3, b0, b1, b2, b3;
-      b_split_scaled(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
-      b_split_scaled(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
-      b_split_scaled(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
-      b_split_scaled(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
-      u32x4b a, b;
+      split_pair_scaled(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
+      split_pair_scaled(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
+      split_pair_scaled(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
+      split_pair_scaled(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
+      u32x4 a, b;
       a.x = a0; a.y = a1; a.z = a2; a.w = a3;
       b.x = b0; b.y = b1; b.z = b2; b.w = b3;
-      *reinterpret_cast<u32x4b*>(rp + ((kg ^ sw) << 4)) = a;
-      *reinterpret_cast<u32x4b*>(rp + (((4 + kg) ^ sw) << 4)) = b;
+      *reinterpret_cast<u32x4*>(rp + ((kg ^ sw) << 4)) = a;
+      *reinterpret_cast<u32x4*>(rp + (((4 + kg) ^ sw) << 4)) = b;
     }
   };
   // the residual of my output pixel (waves 0..5): the fp32 centre of a landed patch, read before the patch is split
   const int res_row = (oy + 2) * BP_W + ox + 2;
-  u32x4b rr[4];
+  u32x4 rr[4];
   auto read_residual = [&](const char* reg) {
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4)
-      rr[g4] = *reinterpret_cast<const u32x4b*>(reg + res_row * 128 + (((2 * g4 + fh) ^ ((res_row >> 1) & 7)) << 4));
+      rr[g4] = *reinterpret_cast<const u32x4*>(reg + res_row * 128 + (((2 * g4 + fh) ^ ((res_row >> 1) & 7)) << 4));
   };
   // the first tile's patch: residual, then everybody converts
   if (has_u2) read_residual(smem + R_OFF);
@@ -268,16 +215,16 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
   {                                                                                                  \
     const int pidx_ = (PBASE) + ((TAP) / 3) * (ROWW) + ((TAP) % 3);                                  \
     const int off_ = pidx_ * 128 + (((2 * (S) + fh) ^ ((pidx_ >> 1) & 7)) << 4);                     \
-    pr##SET[0] = *reinterpret_cast<const u32x4b*>((REGION) + off_);                                  \
-    pr##SET[1] = *reinterpret_cast<const u32x4b*>((REGION) + (off_ ^ 64));                           \
-    wq##SET[0] = *reinterpret_cast<const u32x4b*>((WB) + (((TAP) * 2 + (S)) * 2 + 0) * 1024);        \
-    wq##SET[1] = *reinterpret_cast<const u32x4b*>((WB) + (((TAP) * 2 + (S)) * 2 + 1) * 1024);        \
+    pr##SET[0] = *reinterpret_cast<const u32x4*>((REGION) + off_);                                   \
+    pr##SET[1] = *reinterpret_cast<const u32x4*>((REGION) + (off_ ^ 64));                            \
+    wq##SET[0] = *reinterpret_cast<const u32x4*>((WB) + (((TAP) * 2 + (S)) * 2 + 0) * 1024);         \
+    wq##SET[1] = *reinterpret_cast<const u32x4*>((WB) + (((TAP) * 2 + (S)) * 2 + 1) * 1024);         \
   }
 #define B_MFMA(SET)                                                                                  \
   {                                                                                                  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8b, wq##SET[0]), __builtin_bit_cast(f16x8b, pr##SET[1]), acc, 0, 0, 0); \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8b, wq##SET[1]), __builtin_bit_cast(f16x8b, pr##SET[0]), acc, 0, 0, 0); \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8b, wq##SET[0]), __builtin_bit_cast(f16x8b, pr##SET[0]), acc, 0, 0, 0); \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq##SET[0]), __builtin_bit_cast(f16x8, pr##SET[1]), acc, 0, 0, 0); \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq##SET[1]), __builtin_bit_cast(f16x8, pr##SET[0]), acc, 0, 0, 0); \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq##SET[0]), __builtin_bit_cast(f16x8, pr##SET[0]), acc, 0, 0, 0); \
   }
 
   for (;;) {
@@ -288,14 +235,14 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
     const int ticket = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, q_rsrc, q_off, 0, 0);
     int n_row0 = 0, n_y0 = 0, n_x0 = 0;
     if (has_next) tile_origin(next, n_row0, n_y0, n_x0);
-    f32x16b acc;
+    f32x16 acc;
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
       acc[4 * g4 + 0] = b1r[g4].x * acc1_scale; acc[4 * g4 + 1] = b1r[g4].y * acc1_scale;
       acc[4 * g4 + 2] = b1r[g4].z * acc1_scale; acc[4 * g4 + 3] = b1r[g4].w * acc1_scale;
     }
     {
-      u32x4b prX[2], prY[2], wqX[2], wqY[2];
+      u32x4 prX[2], prY[2], wqX[2], wqY[2];
       B_READ(X, region, w1_bytes, p1base, BP_W, 0, 0);
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
@@ -315,8 +262,8 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
       for (int g4 = 0; g4 < 4; ++g4) {
         const float v0 = fmaxf(acc[4 * g4 + 0] * acc1_unscale, 0.f) * keep, v1 = fmaxf(acc[4 * g4 + 1] * acc1_unscale, 0.f) * keep;
         const float v2 = fmaxf(acc[4 * g4 + 2] * acc1_unscale, 0.f) * keep, v3 = fmaxf(acc[4 * g4 + 3] * acc1_unscale, 0.f) * keep;
-        b_split(v0, v1, ip0[2 * g4], ip1[2 * g4]);
-        b_split(v2, v3, ip0[2 * g4 + 1], ip1[2 * g4 + 1]);
+        split_pair(v0, v1, ip0[2 * g4], ip1[2 * g4]);
+        split_pair(v2, v3, ip0[2 * g4 + 1], ip1[2 * g4 + 1]);
       }
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -327,17 +274,17 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
       char* rp = region + q1 * 128 + 8 * fh;
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
-        u32x2b a, b;
+        u32x2 a, b;
         a.x = ip0[2 * g4]; a.y = ip0[2 * g4 + 1];
         b.x = ip1[2 * g4]; b.y = ip1[2 * g4 + 1];
-        *reinterpret_cast<u32x2b*>(rp + ((g4 ^ sw) << 4)) = a;
-        *reinterpret_cast<u32x2b*>(rp + (((4 + g4) ^ sw) << 4)) = b;
+        *reinterpret_cast<u32x2*>(rp + ((g4 ^ sw) << 4)) = a;
+        *reinterpret_cast<u32x2*>(rp + (((4 + g4) ^ sw) << 4)) = b;
       }
     }
     // the next tile's patch has had all of conv1 to land; nothing else of mine is in flight (the previous tile's stores are
     // long done), so this wait costs no store round trip.  Publish the ticket for the tile after next.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0) slot_write(cur, grid + ticket);
+    if (tid == 0) slot_write(slot_addr(cur), grid + ticket);
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_s_barrier();            // S4: the intermediate is complete, the next patch has landed
 
@@ -357,7 +304,7 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_s_barrier();            // S5: the next tile's residuals are in registers
     if (has_u2) {
-      u32x4b prX[2], prY[2], wqX[2], wqY[2];
+      u32x4 prX[2], prY[2], wqX[2], wqY[2];
       B_READ(X, region, w2_bytes, p2base, BI_W, 0, 0);
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
@@ -368,7 +315,7 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
       const int m = (c_row0 + c_y0 + oy) * W + c_x0 + ox;
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
-        u32x4b pk;
+        u32x4 pk;
         pk.x = __float_as_uint(fmaxf(acc[4 * g4 + 0] * acc2_unscale, 0.f));
         pk.y = __float_as_uint(fmaxf(acc[4 * g4 + 1] * acc2_unscale, 0.f));
         pk.z = __float_as_uint(fmaxf(acc[4 * g4 + 2] * acc2_unscale, 0.f));
@@ -385,7 +332,7 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
     if (!has_next) break;
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_s_barrier();            // S2: the next patch is split; conv2's reads of this region are done
-    const int next2 = slot_read(cur);        // written before S4
+    const int next2 = slot_read(slot_addr(cur));        // written before S4
     tile = next;
     next = next2;
     c_row0 = n_row0; c_y0 = n_y0; c_x0 = n_x0;
@@ -408,13 +355,8 @@ hipError_t launch_conv_block32(const BlockLaunch& b, hipStream_t s) {
   const int tiles_x = b.W / BT_X, tiles_per_img = tiles_x * (b.H / BT_Y);
   const int n_tiles = b.n_img * tiles_per_img;
   static std::atomic<unsigned long long> attr_set{0};
-  const unsigned long long dev_bit = (b.device >= 0 && b.device < 64) ? 1ull << b.device : 0ull;
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit) || !dev_bit) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_block32_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
+  const hipError_t attr_e = set_dynamic_lds_once(attr_set, b.device, B_LDS, &conv_block32_kernel);
+  if (attr_e != hipSuccess) return attr_e;
   int grid = b.num_cu;           // one 512-thread workgroup per CU (LDS: 156 KB)
   if (grid > n_tiles) grid = n_tiles;
   hipLaunchKernelGGL(conv_block32_kernel, dim3(grid), dim3(64 * B_WAVES), B_LDS, s, b, tiles_x, tiles_per_img, n_tiles);

@@ -12,18 +12,11 @@
 // two waves transfer and split (with a share taken by the six behind their MFMAs).  One barrier per tile; a counter in LDS says
 // when every wave's pieces of the next patch have landed.  Both outputs leave as whole 128-byte half rows (a lane owns one output
 // channel of sixteen pixels).  Same tensors and arithmetic as the two launches; the 3x3's output word (max |out|) is published.
-#include <atomic>
-
 #include "ut_kernels.h"
+#include "ut_conv_dev.h"
 
 namespace ut {
 namespace {
-
-typedef float f32x16s __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2s __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) char lds_chars;
-
 
 constexpr int S_OPIX = 96;                // output pixels per tile: 4 rows of 24
 constexpr int S_PROWS = 432;              // patch rows (input pixels) per tile: 9 rows of <= 48
@@ -35,108 +28,15 @@ constexpr int S_LDS = S_CNT + 32;
 constexpr unsigned S_HOOB = 0x80000000u;
 static_assert(S_ZROW % 256 == 0, "zero block bank-row aligned");
 
-__device__ __forceinline__ void s2_dma(u32x4s rsrc, unsigned lds_addr, unsigned voffset, unsigned soffset) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voffset), "s"(lds_addr), "s"(rsrc), "s"(soffset)
-      : "memory");
-}
-__device__ __forceinline__ u32x4s s2_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4s r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
-__device__ __forceinline__ void s2_split_scaled(float a, float b, float s, unsigned& p0, unsigned& p1) {
-  const f16x2s h = __builtin_bit_cast(f16x2s, __builtin_amdgcn_cvt_pkrtz(a * s, b * s));
-  const float ra = __builtin_fmaf(a, s, -(float)h[0]), rb = __builtin_fmaf(b, s, -(float)h[1]);
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-
-// Accumulator-file registers of weight fragment f = tap * 4 + k-step * 2 + plane: a[4 f : 4 f + 3], as inline-asm constraints.  Every
-// use pins the fragment to the same physical registers, so the compiler knows they are occupied (registers it is not told about it
-// hands to other values) and has no reason to move them (with plain "a" constraints its allocator kept shuffling and spilling them).
-#define S_AR_0_0_0 "{a[0:3]}"
-#define S_AR_0_0_1 "{a[4:7]}"
-#define S_AR_0_1_0 "{a[8:11]}"
-#define S_AR_0_1_1 "{a[12:15]}"
-#define S_AR_1_0_0 "{a[16:19]}"
-#define S_AR_1_0_1 "{a[20:23]}"
-#define S_AR_1_1_0 "{a[24:27]}"
-#define S_AR_1_1_1 "{a[28:31]}"
-#define S_AR_2_0_0 "{a[32:35]}"
-#define S_AR_2_0_1 "{a[36:39]}"
-#define S_AR_2_1_0 "{a[40:43]}"
-#define S_AR_2_1_1 "{a[44:47]}"
-#define S_AR_3_0_0 "{a[48:51]}"
-#define S_AR_3_0_1 "{a[52:55]}"
-#define S_AR_3_1_0 "{a[56:59]}"
-#define S_AR_3_1_1 "{a[60:63]}"
-#define S_AR_4_0_0 "{a[64:67]}"
-#define S_AR_4_0_1 "{a[68:71]}"
-#define S_AR_4_1_0 "{a[72:75]}"
-#define S_AR_4_1_1 "{a[76:79]}"
-#define S_AR_5_0_0 "{a[80:83]}"
-#define S_AR_5_0_1 "{a[84:87]}"
-#define S_AR_5_1_0 "{a[88:91]}"
-#define S_AR_5_1_1 "{a[92:95]}"
-#define S_AR_6_0_0 "{a[96:99]}"
-#define S_AR_6_0_1 "{a[100:103]}"
-#define S_AR_6_1_0 "{a[104:107]}"
-#define S_AR_6_1_1 "{a[108:111]}"
-#define S_AR_7_0_0 "{a[112:115]}"
-#define S_AR_7_0_1 "{a[116:119]}"
-#define S_AR_7_1_0 "{a[120:123]}"
-#define S_AR_7_1_1 "{a[124:127]}"
-// (tap 8 is not register-resident: these only let the discarded branch of an `if constexpr` parse)
-#define S_AR_8_0_0 "v"
-#define S_AR_8_0_1 "v"
-#define S_AR_8_1_0 "v"
-#define S_AR_8_1_1 "v"
-#define S_ARF_0 "{a[0:3]}"
-#define S_ARF_1 "{a[4:7]}"
-#define S_ARF_2 "{a[8:11]}"
-#define S_ARF_3 "{a[12:15]}"
-#define S_ARF_4 "{a[16:19]}"
-#define S_ARF_5 "{a[20:23]}"
-#define S_ARF_6 "{a[24:27]}"
-#define S_ARF_7 "{a[28:31]}"
-#define S_ARF_8 "{a[32:35]}"
-#define S_ARF_9 "{a[36:39]}"
-#define S_ARF_10 "{a[40:43]}"
-#define S_ARF_11 "{a[44:47]}"
-#define S_ARF_12 "{a[48:51]}"
-#define S_ARF_13 "{a[52:55]}"
-#define S_ARF_14 "{a[56:59]}"
-#define S_ARF_15 "{a[60:63]}"
-#define S_ARF_16 "{a[64:67]}"
-#define S_ARF_17 "{a[68:71]}"
-#define S_ARF_18 "{a[72:75]}"
-#define S_ARF_19 "{a[76:79]}"
-#define S_ARF_20 "{a[80:83]}"
-#define S_ARF_21 "{a[84:87]}"
-#define S_ARF_22 "{a[88:91]}"
-#define S_ARF_23 "{a[92:95]}"
-#define S_ARF_24 "{a[96:99]}"
-#define S_ARF_25 "{a[100:103]}"
-#define S_ARF_26 "{a[104:107]}"
-#define S_ARF_27 "{a[108:111]}"
-#define S_ARF_28 "{a[112:115]}"
-#define S_ARF_29 "{a[116:119]}"
-#define S_ARF_30 "{a[120:123]}"
-#define S_ARF_31 "{a[124:127]}"
+// Weight fragment f = tap * 4 + k-step * 2 + plane lives in a[4 f : 4 f + 3]: UT_ARF_f / UT_AR(tap, k-step, plane) of ut_conv_dev.h.
+// (tap 8 is not register-resident: this only lets the discarded branch of an `if constexpr` parse)
+#define UT_AR_TAP_8 "v", "v", "v", "v"
 
 }  // namespace
 
 __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const unsigned smem_addr = (unsigned)(unsigned long)(lds_chars*)smem;
+  const unsigned smem_addr = (unsigned)(unsigned long)(lds_char*)smem;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -158,14 +58,14 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
   }
   const float unscale1 = p.unscale1 * x_unscale, unscale_d = p.unscale_d * x_unscale;
 
-  const u32x4s a_words = s2_rsrc(p.in, (unsigned)((size_t)M_in * CIN * sizeof(float)));
+  const u32x4 a_words = rsrc_words(p.in, (unsigned)((size_t)M_in * CIN * sizeof(float)));
   const __amdgpu_buffer_rsrc_t o1_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out1, 0, (int)((size_t)M_out * COUT * sizeof(float)), 0x00020000);
   const __amdgpu_buffer_rsrc_t o2_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out2, 0, (int)((size_t)M_out * COUT * sizeof(float)), 0x00020000);
 
   // ---- my weights: group cb of the 3x3's planes ([cout / 32][tap 9][k-step 2][plane 2][lane 64][8 halves]): fragment f = tap * 4 +
   // k-step * 2 + plane; taps 0..7 pinned to a[4 f : 4 f + 3], the ninth tap's four fragments in LDS; the shortcut's four fragments
   // (group cb of its planes, one chunk) in the vector half
-  u32x4s wa[32], wd[4];
+  u32x4 wa[32], wd[4];
   {
     const char* wg = reinterpret_cast<const char*>(p.w1_split) + (size_t)cb * 9 * 4096 + lane * 16;
     // (sixteen requests and their wait in ONE statement: the compiler takes an asm's outputs as ready where the statement ends, and
@@ -188,7 +88,7 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
         "global_load_dwordx4 %14, %19, off offset:2048\n\t"
         "global_load_dwordx4 %15, %19, off offset:3072\n\t"
         "s_waitcnt vmcnt(0)"
-        : "=&" S_ARF_0(wa[0]), "=&" S_ARF_1(wa[1]), "=&" S_ARF_2(wa[2]), "=&" S_ARF_3(wa[3]), "=&" S_ARF_4(wa[4]), "=&" S_ARF_5(wa[5]), "=&" S_ARF_6(wa[6]), "=&" S_ARF_7(wa[7]), "=&" S_ARF_8(wa[8]), "=&" S_ARF_9(wa[9]), "=&" S_ARF_10(wa[10]), "=&" S_ARF_11(wa[11]), "=&" S_ARF_12(wa[12]), "=&" S_ARF_13(wa[13]), "=&" S_ARF_14(wa[14]), "=&" S_ARF_15(wa[15])
+        : "=&" UT_ARF_0(wa[0]), "=&" UT_ARF_1(wa[1]), "=&" UT_ARF_2(wa[2]), "=&" UT_ARF_3(wa[3]), "=&" UT_ARF_4(wa[4]), "=&" UT_ARF_5(wa[5]), "=&" UT_ARF_6(wa[6]), "=&" UT_ARF_7(wa[7]), "=&" UT_ARF_8(wa[8]), "=&" UT_ARF_9(wa[9]), "=&" UT_ARF_10(wa[10]), "=&" UT_ARF_11(wa[11]), "=&" UT_ARF_12(wa[12]), "=&" UT_ARF_13(wa[13]), "=&" UT_ARF_14(wa[14]), "=&" UT_ARF_15(wa[15])
         : "v"(wg + 0 * 4096), "v"(wg + 1 * 4096), "v"(wg + 2 * 4096), "v"(wg + 3 * 4096)
         : "memory");
     asm volatile(
@@ -209,22 +109,22 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
         "global_load_dwordx4 %14, %19, off offset:2048\n\t"
         "global_load_dwordx4 %15, %19, off offset:3072\n\t"
         "s_waitcnt vmcnt(0)"
-        : "=&" S_ARF_16(wa[16]), "=&" S_ARF_17(wa[17]), "=&" S_ARF_18(wa[18]), "=&" S_ARF_19(wa[19]), "=&" S_ARF_20(wa[20]), "=&" S_ARF_21(wa[21]), "=&" S_ARF_22(wa[22]), "=&" S_ARF_23(wa[23]), "=&" S_ARF_24(wa[24]), "=&" S_ARF_25(wa[25]), "=&" S_ARF_26(wa[26]), "=&" S_ARF_27(wa[27]), "=&" S_ARF_28(wa[28]), "=&" S_ARF_29(wa[29]), "=&" S_ARF_30(wa[30]), "=&" S_ARF_31(wa[31])
+        : "=&" UT_ARF_16(wa[16]), "=&" UT_ARF_17(wa[17]), "=&" UT_ARF_18(wa[18]), "=&" UT_ARF_19(wa[19]), "=&" UT_ARF_20(wa[20]), "=&" UT_ARF_21(wa[21]), "=&" UT_ARF_22(wa[22]), "=&" UT_ARF_23(wa[23]), "=&" UT_ARF_24(wa[24]), "=&" UT_ARF_25(wa[25]), "=&" UT_ARF_26(wa[26]), "=&" UT_ARF_27(wa[27]), "=&" UT_ARF_28(wa[28]), "=&" UT_ARF_29(wa[29]), "=&" UT_ARF_30(wa[30]), "=&" UT_ARF_31(wa[31])
         : "v"(wg + 4 * 4096), "v"(wg + 5 * 4096), "v"(wg + 6 * 4096), "v"(wg + 7 * 4096)
         : "memory");
     if (wave < 2) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<u32x4s*>(smem + S_W8 + cb * 4096 + q * 1024 + lane * 16) = *reinterpret_cast<const u32x4s*>(wg + 8 * 4096 + q * 1024);
+        *reinterpret_cast<u32x4*>(smem + S_W8 + cb * 4096 + q * 1024 + lane * 16) = *reinterpret_cast<const u32x4*>(wg + 8 * 4096 + q * 1024);
     }
     const char* dg = reinterpret_cast<const char*>(p.wd_split) + (size_t)cb * 4096 + lane * 16;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) wd[q] = *reinterpret_cast<const u32x4s*>(dg + q * 1024);
+    for (int q = 0; q < 4; ++q) wd[q] = *reinterpret_cast<const u32x4*>(dg + q * 1024);
   }
   const unsigned w8 = (unsigned)(S_W8 + cb * 4096 + lane * 16);
 
-  if (tid < 16) *reinterpret_cast<u32x4s*>(smem + S_ZROW + tid * 16) = u32x4s{0, 0, 0, 0};
-  if (tid == 16) *reinterpret_cast<u32x4s*>(smem + S_CNT) = u32x4s{0, 0, 0, 0};
+  if (tid < 16) *reinterpret_cast<u32x4*>(smem + S_ZROW + tid * 16) = u32x4{0, 0, 0, 0};
+  if (tid == 16) *reinterpret_cast<u32x4*>(smem + S_CNT) = u32x4{0, 0, 0, 0};
 
   // ---- the patch stream: my k-th tile's patch lives in buffer k & 1.  Tile t = (image, 4 output rows 4 q .. 4 q + 3): its patch is the
   // 9 W consecutive input pixels from row 8 q - 1 of the image (row -1 of the first tile of an image is the last row of the image
@@ -245,7 +145,7 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
       const int pix = first_pixel + row;
       const bool ok = pix >= 0 && pix < M_in && row < 9 * W;
       const unsigned off = ok ? (unsigned)(pix * CIN + 4 * ((lane_o & 7) ^ ((row >> 2) & 7))) * 4u : S_HOOB;
-      s2_dma(a_words, (unsigned)__builtin_amdgcn_readfirstlane((int)(smem_addr + (unsigned)(buf * S_STAGE + q * 1024))), off, 0u);
+      dma_piece(a_words, (unsigned)__builtin_amdgcn_readfirstlane((int)(smem_addr + (unsigned)(buf * S_STAGE + q * 1024))), off, 0u);
     }
   };
   auto convert_row = [&](int buf, int row) {      // split the landed fp32 patch row at POSITION `row` in place (group q = k / 8 at q ^ swizzle)
@@ -257,15 +157,15 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
 #pragma unroll
     for (int kg = 0; kg < 4; ++kg) {
       unsigned a0, a1, a2, a3, b0, b1, b2, b3;
-      s2_split_scaled(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
-      s2_split_scaled(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
-      s2_split_scaled(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
-      s2_split_scaled(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
-      u32x4s a, b;
+      split_pair_scaled(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
+      split_pair_scaled(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
+      split_pair_scaled(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
+      split_pair_scaled(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
+      u32x4 a, b;
       a.x = a0; a.y = a1; a.z = a2; a.w = a3;
       b.x = b0; b.y = b1; b.z = b2; b.w = b3;
-      *reinterpret_cast<u32x4s*>(rp + ((kg ^ sw) << 4)) = a;
-      *reinterpret_cast<u32x4s*>(rp + (((4 + kg) ^ sw) << 4)) = b;
+      *reinterpret_cast<u32x4*>(rp + ((kg ^ sw) << 4)) = a;
+      *reinterpret_cast<u32x4*>(rp + (((4 + kg) ^ sw) << 4)) = b;
     }
   };
   // rows of a patch: the two transfer waves take two rows per thread (256), the six MFMA waves the rest behind their MFMAs.  Unit u
@@ -321,8 +221,8 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
     if ((int)(__builtin_amdgcn_readfirstlane(seen_) - (unsigned)(TARGET)) >= 0) break;               \
     __builtin_amdgcn_s_sleep(1);                                                                     \
   }
-#define S_MFMA_A(ACC, TAP, S, PL, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), S_AR_##TAP##_##S##_##PL(wa[S_W(TAP, S, PL)]))
-#define S_MFMA_A_FIRST(ACC, TAP, S, PL, PXV) asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), S_AR_##TAP##_##S##_##PL(wa[S_W(TAP, S, PL)]))
+#define S_MFMA_A(ACC, TAP, S, PL, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), UT_AR(TAP, S, PL)(wa[S_W(TAP, S, PL)]))
+#define S_MFMA_A_FIRST(ACC, TAP, S, PL, PXV) asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), UT_AR(TAP, S, PL)(wa[S_W(TAP, S, PL)]))
 #define S_MFMA_V(ACC, WV, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), "v"(WV))
 #define S_MFMA_V_FIRST(ACC, WV, PXV) asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), "v"(WV))
 #define S_MFMA_V_LAST(ACC, WV, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0\n\ts_nop 15\n\ts_nop 7" : "+v"(ACC) : "v"(PXV), "v"(WV))
@@ -341,8 +241,8 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
   }
 #define S_LOAD(DST, ADDR, S)                                                                         \
   {                                                                                                  \
-    DST[0] = *reinterpret_cast<const u32x4s*>(smem + ((ADDR) ^ (32u * (S))));                        \
-    DST[1] = *reinterpret_cast<const u32x4s*>(smem + ((ADDR) ^ (32u * (S)) ^ 64u));                  \
+    DST[0] = *reinterpret_cast<const u32x4*>(smem + ((ADDR) ^ (32u * (S))));                         \
+    DST[1] = *reinterpret_cast<const u32x4*>(smem + ((ADDR) ^ (32u * (S)) ^ 64u));                   \
   }
   // k-step (TAP, S): three MFMAs of the 3x3 on CUR (weights' first pieces x pixels' remainders, weights' remainders x pixels' first
   // pieces, first x first), at the centre tap three more of the shortcut on the same fragments; reads the fragments of the k-step
@@ -350,10 +250,10 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
   // rotation); ADN holds the address of tap TAP + 1, ADF receives that of tap TAP + 2 (S = 1); a transfer piece behind the last.
 #define S_STEP(TAP, S, CUR, FAR, PIECE, ADN, ADF)                                                    \
   {                                                                                                  \
-    u32x4s w8a_, w8b_;                                                                               \
+    u32x4 w8a_, w8b_;                                                                                \
     if constexpr ((TAP) == 8) {                                                                      \
-      w8a_ = *reinterpret_cast<const u32x4s*>(smem + w8 + ((S) * 2 + 0) * 1024);                     \
-      w8b_ = *reinterpret_cast<const u32x4s*>(smem + w8 + ((S) * 2 + 1) * 1024);                     \
+      w8a_ = *reinterpret_cast<const u32x4*>(smem + w8 + ((S) * 2 + 0) * 1024);                      \
+      w8b_ = *reinterpret_cast<const u32x4*>(smem + w8 + ((S) * 2 + 1) * 1024);                      \
     }                                                                                                \
     if constexpr ((TAP) < 8) {                                                                       \
       if constexpr ((TAP) == 0 && (S) == 0) { S_MFMA_A_FIRST(acc, TAP, S, 0, CUR[1]); } else { S_MFMA_A(acc, TAP, S, 0, CUR[1]); } \
@@ -404,7 +304,7 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
     }                                                                                                \
   }
 
-  f32x16s acc, accd;
+  f32x16 acc, accd;
   for (int k = 0; k < my_tiles; ++k) {
     const int tile = blockIdx.x + k * grid;
     const unsigned rbuf = (unsigned)((k & 1) * S_STAGE);
@@ -422,7 +322,7 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
       for (int e = 0; e < 16; ++e) { acc[e] = 0.f; accd[e] = 0.f; }
       asm volatile("" : "+v"(acc), "+v"(accd));
       {
-        u32x4s pxA[2], pxB[2], pxC[2];
+        u32x4 pxA[2], pxB[2], pxC[2];
         unsigned adE, adO;
         S_ADDR(adE, rbuf, 0);
         S_LOAD(pxA, adE, 0);
@@ -483,12 +383,8 @@ hipError_t launch_conv_c32s2(const Stride2Launch& c, hipStream_t s) {
   if (!conv_c32s2_applicable(c)) return hipErrorInvalidValue;
   const int n_tiles = c.n_img * (c.H / 8);
   static std::atomic<unsigned long long> attr_set{0};
-  const unsigned long long dev_bit = (c.device >= 0 && c.device < 64) ? 1ull << c.device : 0ull;
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit) || !dev_bit) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c32s2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
+  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, S_LDS, &conv_c32s2_kernel);
+  if (attr_e != hipSuccess) return attr_e;
   int grid = c.num_cu;
   if (grid > n_tiles) grid = n_tiles;
   hipLaunchKernelGGL(conv_c32s2_kernel, dim3(grid), dim3(512), S_LDS, s, c, n_tiles);

@@ -24,17 +24,11 @@
 // output channel of sixteen pixels: dword accesses of the epilogue are whole 128-byte half rows).  Same interface and tensors as
 // conv_split_kernel<256, 64, 8, 1, true>; the sum over K is taken as (slice 0) + (slice 1, residual, bias) instead of one running
 // sum with bias and residual added last: results agree with that kernel's to fp32 rounding, not bit for bit; deterministic.
-#include <atomic>
-
 #include "ut_kernels.h"
+#include "ut_conv_dev.h"
 
 namespace ut {
 namespace {
-
-typedef float f32x16k __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4k __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2k __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) char lds_chark;
 
 constexpr int K_BM = 128;                 // pixels per tile
 constexpr int K_HROWS = 192;              // patch rows per slice (128 + 2 * (image width + 1) <= 192: width <= 31)
@@ -50,108 +44,15 @@ constexpr int K_PW = K_HROWS / 8 / 4;     // 1-KB pieces of a slice patch per wa
 constexpr unsigned K_HOOB = 0x80000000u;
 static_assert(K_ZROW % 256 == 0, "zero block bank-row aligned");
 
-__device__ __forceinline__ void k_dma(u32x4k rsrc, unsigned lds_addr, unsigned voffset, unsigned soffset) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voffset), "s"(lds_addr), "s"(rsrc), "s"(soffset)
-      : "memory");
-}
-__device__ __forceinline__ u32x4k k_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4k r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
-__device__ __forceinline__ void k_split_scaled(float a, float b, float s, unsigned& p0, unsigned& p1) {
-  const f16x2k h = __builtin_bit_cast(f16x2k, __builtin_amdgcn_cvt_pkrtz(a * s, b * s));
-  const float ra = __builtin_fmaf(a, s, -(float)h[0]), rb = __builtin_fmaf(b, s, -(float)h[1]);
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-
-// Accumulator-file registers of weight fragment f = tap * 4 + k-step * 2 + plane: a[4 f : 4 f + 3], as inline-asm constraints.  Every
-// use pins the fragment to the same physical registers, so the compiler knows they are occupied (registers it is not told about it
-// hands to other values) and has no reason to move them (with plain "a" constraints its allocator kept shuffling and spilling them).
-#define K_AR_0_0_0 "{a[0:3]}"
-#define K_AR_0_0_1 "{a[4:7]}"
-#define K_AR_0_1_0 "{a[8:11]}"
-#define K_AR_0_1_1 "{a[12:15]}"
-#define K_AR_1_0_0 "{a[16:19]}"
-#define K_AR_1_0_1 "{a[20:23]}"
-#define K_AR_1_1_0 "{a[24:27]}"
-#define K_AR_1_1_1 "{a[28:31]}"
-#define K_AR_2_0_0 "{a[32:35]}"
-#define K_AR_2_0_1 "{a[36:39]}"
-#define K_AR_2_1_0 "{a[40:43]}"
-#define K_AR_2_1_1 "{a[44:47]}"
-#define K_AR_3_0_0 "{a[48:51]}"
-#define K_AR_3_0_1 "{a[52:55]}"
-#define K_AR_3_1_0 "{a[56:59]}"
-#define K_AR_3_1_1 "{a[60:63]}"
-#define K_AR_4_0_0 "{a[64:67]}"
-#define K_AR_4_0_1 "{a[68:71]}"
-#define K_AR_4_1_0 "{a[72:75]}"
-#define K_AR_4_1_1 "{a[76:79]}"
-#define K_AR_5_0_0 "{a[80:83]}"
-#define K_AR_5_0_1 "{a[84:87]}"
-#define K_AR_5_1_0 "{a[88:91]}"
-#define K_AR_5_1_1 "{a[92:95]}"
-#define K_AR_6_0_0 "{a[96:99]}"
-#define K_AR_6_0_1 "{a[100:103]}"
-#define K_AR_6_1_0 "{a[104:107]}"
-#define K_AR_6_1_1 "{a[108:111]}"
-#define K_AR_7_0_0 "{a[112:115]}"
-#define K_AR_7_0_1 "{a[116:119]}"
-#define K_AR_7_1_0 "{a[120:123]}"
-#define K_AR_7_1_1 "{a[124:127]}"
-// (tap 8 is not register-resident: these only let the discarded branch of an `if constexpr` parse)
-#define K_AR_8_0_0 "v"
-#define K_AR_8_0_1 "v"
-#define K_AR_8_1_0 "v"
-#define K_AR_8_1_1 "v"
-#define K_ARF_0 "{a[0:3]}"
-#define K_ARF_1 "{a[4:7]}"
-#define K_ARF_2 "{a[8:11]}"
-#define K_ARF_3 "{a[12:15]}"
-#define K_ARF_4 "{a[16:19]}"
-#define K_ARF_5 "{a[20:23]}"
-#define K_ARF_6 "{a[24:27]}"
-#define K_ARF_7 "{a[28:31]}"
-#define K_ARF_8 "{a[32:35]}"
-#define K_ARF_9 "{a[36:39]}"
-#define K_ARF_10 "{a[40:43]}"
-#define K_ARF_11 "{a[44:47]}"
-#define K_ARF_12 "{a[48:51]}"
-#define K_ARF_13 "{a[52:55]}"
-#define K_ARF_14 "{a[56:59]}"
-#define K_ARF_15 "{a[60:63]}"
-#define K_ARF_16 "{a[64:67]}"
-#define K_ARF_17 "{a[68:71]}"
-#define K_ARF_18 "{a[72:75]}"
-#define K_ARF_19 "{a[76:79]}"
-#define K_ARF_20 "{a[80:83]}"
-#define K_ARF_21 "{a[84:87]}"
-#define K_ARF_22 "{a[88:91]}"
-#define K_ARF_23 "{a[92:95]}"
-#define K_ARF_24 "{a[96:99]}"
-#define K_ARF_25 "{a[100:103]}"
-#define K_ARF_26 "{a[104:107]}"
-#define K_ARF_27 "{a[108:111]}"
-#define K_ARF_28 "{a[112:115]}"
-#define K_ARF_29 "{a[116:119]}"
-#define K_ARF_30 "{a[120:123]}"
-#define K_ARF_31 "{a[124:127]}"
+// Weight fragment f = tap * 4 + k-step * 2 + plane lives in a[4 f : 4 f + 3]: UT_ARF_f / UT_AR(tap, k-step, plane) of ut_conv_dev.h.
+// (tap 8 is not register-resident: this only lets the discarded branch of an `if constexpr` parse)
+#define UT_AR_TAP_8 "v", "v", "v", "v"
 
 }  // namespace
 
 __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const unsigned smem_addr = (unsigned)(unsigned long)(lds_chark*)smem;
+  const unsigned smem_addr = (unsigned)(unsigned long)(lds_char*)smem;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -173,7 +74,7 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
   }
   const float tot_unscale = p.split_unscale * x_unscale;
 
-  const u32x4k a_words = k_rsrc(p.in, (unsigned)((size_t)M * CIN * sizeof(float)));
+  const u32x4 a_words = rsrc_words(p.in, (unsigned)((size_t)M * CIN * sizeof(float)));
   const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.res ? p.res : p.bias), 0, p.res ? (int)((size_t)M * COUT * sizeof(float)) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t o_rsrc =
@@ -181,9 +82,9 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
 
   // ---- my weights: group cb of ConvLaunch::w_split ([cout / 32][chunk 18][k-step 2][plane 2][lane 64][8 halves]; chunk = slice * 9 +
   // tap), the nine chunks of slice ks: fragment f = tap * 4 + k-step * 2 + plane.  Taps 0..7 live in the accumulator half of the
-  // register file, each pinned to its own registers a[4 f : 4 f + 3] at every use (K_AR_* above); the ninth tap's four fragments
+  // register file, each pinned to its own registers a[4 f : 4 f + 3] at every use (UT_AR); the ninth tap's four fragments
   // are read from LDS where they are used (4 KB per tile and wave).
-  u32x4k wa[32];
+  u32x4 wa[32];
   {
     const char* wg = reinterpret_cast<const char*>(p.w_split) + ((size_t)cb * 18 + (size_t)ks * 9) * 4096 + lane * 16;
     // (sixteen requests and their wait in ONE statement: the compiler takes an asm's outputs as ready where the statement ends, and
@@ -206,7 +107,7 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
         "global_load_dwordx4 %14, %19, off offset:2048\n\t"
         "global_load_dwordx4 %15, %19, off offset:3072\n\t"
         "s_waitcnt vmcnt(0)"
-        : "=&" K_ARF_0(wa[0]), "=&" K_ARF_1(wa[1]), "=&" K_ARF_2(wa[2]), "=&" K_ARF_3(wa[3]), "=&" K_ARF_4(wa[4]), "=&" K_ARF_5(wa[5]), "=&" K_ARF_6(wa[6]), "=&" K_ARF_7(wa[7]), "=&" K_ARF_8(wa[8]), "=&" K_ARF_9(wa[9]), "=&" K_ARF_10(wa[10]), "=&" K_ARF_11(wa[11]), "=&" K_ARF_12(wa[12]), "=&" K_ARF_13(wa[13]), "=&" K_ARF_14(wa[14]), "=&" K_ARF_15(wa[15])
+        : "=&" UT_ARF_0(wa[0]), "=&" UT_ARF_1(wa[1]), "=&" UT_ARF_2(wa[2]), "=&" UT_ARF_3(wa[3]), "=&" UT_ARF_4(wa[4]), "=&" UT_ARF_5(wa[5]), "=&" UT_ARF_6(wa[6]), "=&" UT_ARF_7(wa[7]), "=&" UT_ARF_8(wa[8]), "=&" UT_ARF_9(wa[9]), "=&" UT_ARF_10(wa[10]), "=&" UT_ARF_11(wa[11]), "=&" UT_ARF_12(wa[12]), "=&" UT_ARF_13(wa[13]), "=&" UT_ARF_14(wa[14]), "=&" UT_ARF_15(wa[15])
         : "v"(wg + 0 * 4096), "v"(wg + 1 * 4096), "v"(wg + 2 * 4096), "v"(wg + 3 * 4096)
         : "memory");
     asm volatile(
@@ -227,21 +128,21 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
         "global_load_dwordx4 %14, %19, off offset:2048\n\t"
         "global_load_dwordx4 %15, %19, off offset:3072\n\t"
         "s_waitcnt vmcnt(0)"
-        : "=&" K_ARF_16(wa[16]), "=&" K_ARF_17(wa[17]), "=&" K_ARF_18(wa[18]), "=&" K_ARF_19(wa[19]), "=&" K_ARF_20(wa[20]), "=&" K_ARF_21(wa[21]), "=&" K_ARF_22(wa[22]), "=&" K_ARF_23(wa[23]), "=&" K_ARF_24(wa[24]), "=&" K_ARF_25(wa[25]), "=&" K_ARF_26(wa[26]), "=&" K_ARF_27(wa[27]), "=&" K_ARF_28(wa[28]), "=&" K_ARF_29(wa[29]), "=&" K_ARF_30(wa[30]), "=&" K_ARF_31(wa[31])
+        : "=&" UT_ARF_16(wa[16]), "=&" UT_ARF_17(wa[17]), "=&" UT_ARF_18(wa[18]), "=&" UT_ARF_19(wa[19]), "=&" UT_ARF_20(wa[20]), "=&" UT_ARF_21(wa[21]), "=&" UT_ARF_22(wa[22]), "=&" UT_ARF_23(wa[23]), "=&" UT_ARF_24(wa[24]), "=&" UT_ARF_25(wa[25]), "=&" UT_ARF_26(wa[26]), "=&" UT_ARF_27(wa[27]), "=&" UT_ARF_28(wa[28]), "=&" UT_ARF_29(wa[29]), "=&" UT_ARF_30(wa[30]), "=&" UT_ARF_31(wa[31])
         : "v"(wg + 4 * 4096), "v"(wg + 5 * 4096), "v"(wg + 6 * 4096), "v"(wg + 7 * 4096)
         : "memory");
     if (ph == 0) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<u32x4k*>(smem + K_W8 + (cb * 2 + ks) * 4096 + q * 1024 + lane * 16) =
-            *reinterpret_cast<const u32x4k*>(wg + 8 * 4096 + q * 1024);
+        *reinterpret_cast<u32x4*>(smem + K_W8 + (cb * 2 + ks) * 4096 + q * 1024 + lane * 16) =
+            *reinterpret_cast<const u32x4*>(wg + 8 * 4096 + q * 1024);
     }
   }
   const unsigned w8 = (unsigned)(K_W8 + (cb * 2 + ks) * 4096 + lane * 16);
 
   // ---- zero block, tap-validity masks of every pixel position of an image
-  if (tid < 16) *reinterpret_cast<u32x4k*>(smem + K_ZROW + tid * 16) = u32x4k{0, 0, 0, 0};
-  if (tid == 16) *reinterpret_cast<u32x4k*>(smem + K_CNT) = u32x4k{0, 0, 0, 0};
+  if (tid < 16) *reinterpret_cast<u32x4*>(smem + K_ZROW + tid * 16) = u32x4{0, 0, 0, 0};
+  if (tid == 16) *reinterpret_cast<u32x4*>(smem + K_CNT) = u32x4{0, 0, 0, 0};
   for (int pos = tid; pos < hw; pos += 512) {
     const int y = pos / wimg, x = pos - y * wimg;
     unsigned mk = 0;
@@ -265,7 +166,7 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
     const int pix = tile * K_BM - wimg - 1 + row;
     const bool ok = pix >= 0 && pix < M;
     const unsigned off = ok ? (unsigned)(pix * CIN + 4 * ((lane_o & 7) ^ ((row >> 1) & 7))) * 4u : K_HOOB;
-    k_dma(a_words, (unsigned)__builtin_amdgcn_readfirstlane((int)(smem_addr + (unsigned)(buf * K_STAGE + q * 1024))), off,
+    dma_piece(a_words, (unsigned)__builtin_amdgcn_readfirstlane((int)(smem_addr + (unsigned)(buf * K_STAGE + q * 1024))), off,
           (unsigned)ks * 128u);
   };
   // split landed fp32 slice patches of a tile in place (group q = k / 8 at q ^ swizzle); unit u = slice * 192 + row, u < 384
@@ -279,15 +180,15 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
 #pragma unroll
     for (int kg = 0; kg < 4; ++kg) {
       unsigned a0, a1, a2, a3, b0, b1, b2, b3;
-      k_split_scaled(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
-      k_split_scaled(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
-      k_split_scaled(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
-      k_split_scaled(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
-      u32x4k a, b;
+      split_pair_scaled(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
+      split_pair_scaled(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
+      split_pair_scaled(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
+      split_pair_scaled(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
+      u32x4 a, b;
       a.x = a0; a.y = a1; a.z = a2; a.w = a3;
       b.x = b0; b.y = b1; b.z = b2; b.w = b3;
-      *reinterpret_cast<u32x4k*>(rp + ((kg ^ sw) << 4)) = a;
-      *reinterpret_cast<u32x4k*>(rp + (((4 + kg) ^ sw) << 4)) = b;
+      *reinterpret_cast<u32x4*>(rp + ((kg ^ sw) << 4)) = a;
+      *reinterpret_cast<u32x4*>(rp + (((4 + kg) ^ sw) << 4)) = b;
     }
   };
   auto convert_patches = [&](int parity) {  // every thread of the workgroup (prologue)
@@ -322,7 +223,7 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
   // checked): pixels beyond the tensor (last tile) load zeros and their stores are dropped, with no compare per access.
 #define K_OFF(TILE, J) ((unsigned)(((TILE) * K_BM + 32 * (2 * (J) + ph) + 4 * fh) * COUT + 32 * cb + fr) * 4u)
 #define K_ROFF(OFF, R) ((((R) >> 3) ? (OFF) + 16u * COUT * 4u : (OFF)) + (unsigned)(((((R) >> 2) & 1) * 8 + ((R) & 3)) * COUT * 4))
-  f32x16k acc[2];      // (ks = 1: between its hand-over and the next tile's start these registers hold the next tile's residual)
+  f32x16 acc[2];      // (ks = 1: between its hand-over and the next tile's start these registers hold the next tile's residual)
 #define K_RINI(TILE)                                                                                 \
   _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                    \
     const unsigned off_ = K_OFF(TILE, j);                                                            \
@@ -353,11 +254,11 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
     if ((int)(__builtin_amdgcn_readfirstlane(seen_) - (unsigned)(TARGET)) >= 0) break;               \
     __builtin_amdgcn_s_sleep(1);                                                                     \
   }
-#define K_MFMA_A(ACC, TAP, S, PL, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), K_AR_##TAP##_##S##_##PL(wa[K_W(TAP, S, PL)]))
+#define K_MFMA_A(ACC, TAP, S, PL, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), UT_AR(TAP, S, PL)(wa[K_W(TAP, S, PL)]))
 #define K_MFMA_V(ACC, WV, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), "v"(WV))
   // (the compiler knows nothing of an asm MFMA's latency and may put a register copy of the accumulator right behind - or in front of -
   // it: the wait states travel INSIDE the statement of a block's first and last MFMA of a tile)
-#define K_MFMA_A_FIRST(ACC, TAP, S, PL, PXV) asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), K_AR_##TAP##_##S##_##PL(wa[K_W(TAP, S, PL)]))
+#define K_MFMA_A_FIRST(ACC, TAP, S, PL, PXV) asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(PXV), UT_AR(TAP, S, PL)(wa[K_W(TAP, S, PL)]))
 #define K_MFMA_V_LAST(ACC, WV, PXV) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0\n\ts_nop 15\n\ts_nop 7" : "+v"(ACC) : "v"(PXV), "v"(WV))
   // Address of the lane's 16 bytes of block J, tap TAP, k-step 0, first pieces, in the patch at byte offset BUF - or in the block of
   // zeros, on the same banks, when the tap leaves the image.  k-step 1 is that address ^ 32, the remainder pieces ^ 64.
@@ -369,8 +270,8 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
   }
 #define K_LOAD(DST, ADDR, S)                                                                         \
   {                                                                                                  \
-    DST[0] = *reinterpret_cast<const u32x4k*>(smem + ((ADDR) ^ (32u * (S))));                        \
-    DST[1] = *reinterpret_cast<const u32x4k*>(smem + ((ADDR) ^ (32u * (S)) ^ 64u));                  \
+    DST[0] = *reinterpret_cast<const u32x4*>(smem + ((ADDR) ^ (32u * (S))));                         \
+    DST[1] = *reinterpret_cast<const u32x4*>(smem + ((ADDR) ^ (32u * (S)) ^ 64u));                   \
   }
 #define K_LEAD() asm volatile("s_nop 3")
 #define K_DRAIN() asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]))
@@ -402,10 +303,10 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
   // rotation); ADN holds the addresses of tap TAP + 1 (computed a k-step earlier), ADF receives those of tap TAP + 2 (S = 1)
 #define K_STEP(TAP, S, CUR, FAR, PIECE, ADN, ADF)                                                    \
   {                                                                                                  \
-    u32x4k w8a_, w8b_;                                                                               \
+    u32x4 w8a_, w8b_;                                                                                \
     if constexpr ((TAP) == 8) {                                                                      \
-      w8a_ = *reinterpret_cast<const u32x4k*>(smem + w8 + ((S) * 2 + 0) * 1024);                     \
-      w8b_ = *reinterpret_cast<const u32x4k*>(smem + w8 + ((S) * 2 + 1) * 1024);                     \
+      w8a_ = *reinterpret_cast<const u32x4*>(smem + w8 + ((S) * 2 + 0) * 1024);                      \
+      w8b_ = *reinterpret_cast<const u32x4*>(smem + w8 + ((S) * 2 + 1) * 1024);                      \
     }                                                                                                \
     K_MM(TAP, S, CUR, 0, 0)                                                                          \
     if constexpr ((TAP) < 8) K_LOAD(FAR[0], ADN[0], S);                                              \
@@ -470,7 +371,7 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
 #pragma unroll
     for (int j = 0; j < 2; ++j) asm volatile("" : "+v"(acc[j]));
     {
-      u32x4k pxA[2][2], pxB[2][2], pxC[2][2];
+      u32x4 pxA[2][2], pxB[2][2], pxC[2][2];
       unsigned adE[2], adO[2];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -587,13 +488,8 @@ hipError_t launch_conv_c64k(const ConvLaunch& c, hipStream_t s) {
   const long M = (long)c.n_img * c.H * c.W;
   const int n_tiles = (int)((M + K_BM - 1) / K_BM);
   static std::atomic<unsigned long long> attr_set{0};
-  const unsigned long long dev_bit = (c.device >= 0 && c.device < 64) ? 1ull << c.device : 0ull;
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit) || !dev_bit) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c64k_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, K_LDS);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
+  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, K_LDS, &conv_c64k_kernel);
+  if (attr_e != hipSuccess) return attr_e;
   int grid = c.num_cu;           // one 512-thread workgroup per CU, two waves per SIMD; tiles are dealt round robin (they all cost the same)
   if (grid > n_tiles) grid = n_tiles;
   hipLaunchKernelGGL(conv_c64k_kernel, dim3(grid), dim3(512), K_LDS, s, c, n_tiles);

@@ -31,15 +31,10 @@
 // bookkeeping of the chunk loop wave-uniform: it runs on the scalar unit and the loop body has no branch.
 // Tile shapes: 128x128 (cout > 64), 128x64 (cout <= 64, three workgroups per CU), 64x128 for launches with few
 // tiles (projection and head: 74 k pixels); layer1 (3x3, 32 -> 32) runs in conv_patch.hip instead.
-#include <atomic>
-
 #include "ut_kernels.h"
+#include "ut_conv_dev.h"
 
 namespace ut {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) float lds_f32;
 
 constexpr int BK = 32;
 // LDS row stride in floats.  LDS-DMA staging (buffer_load ... lds) writes 64 lanes x 16 B = 8 whole rows
@@ -48,31 +43,9 @@ constexpr int BK = 32;
 // (which global chunk a lane fetches); 16-lane read groups then hit 16 distinct 16-byte bank slots.
 constexpr int LDS_ROW = BK;
 
-// One LDS-DMA piece: 64 lanes x 16 bytes from a buffer (per-lane byte offset, out-of-range -> zeros) straight
-// into LDS at lds_addr + lane*16.  Inline asm on purpose: with the builtin hipcc treats the pending LDS write
-// as aliasing every ds_read and drains vmcnt(0) in front of the fragment reads of the CURRENT buffer, which
-// serialises the whole prefetch.  M0 (the LDS base of the transfer) is written in the statement that uses it
-// and restored; the transfer is invisible to the compiler's wait counting, so dma_wait_all() precedes the
-// barrier that publishes the buffer.
-__device__ __forceinline__ void dma16(u32x4 rsrc, unsigned lds_addr, unsigned voffset) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voffset), "s"(lds_addr), "s"(rsrc)
-      : "memory");
-}
+// The operands come in as LDS-DMA pieces (ut_conv_dev.h::dma_piece): invisible to the compiler's wait counting, so
+// dma_wait_all() precedes the barrier that publishes the buffer.
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ u32x4 make_rsrc_words(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);   // stride 0
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
-
 // n / d for 0 <= n < 2^24 via a float reciprocal and one correction step (exact: |error| <= 1 before it)
 __device__ __forceinline__ int fast_div(int n, int d, float inv_d) {
   int q = (int)((float)n * inv_d);
@@ -141,8 +114,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvLaunch p, int ti
   // drops the others) whose result is awaited where it is used, not where it is issued
   const __amdgpu_buffer_rsrc_t q_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.tile_counter, 0, 4, 0x00020000);
   const unsigned q_off = tid == 0 ? 0u : OOB;
-  const u32x4 a_words = make_rsrc_words(p.in, (unsigned)((size_t)p.n_img * p.H * p.W * p.cin * sizeof(float)));
-  const u32x4 b_words = make_rsrc_words(p.w, (unsigned)((size_t)p.cout_pad * p.k_pad * sizeof(float)));
+  const u32x4 a_words = rsrc_words(p.in, (unsigned)((size_t)p.n_img * p.H * p.W * p.cin * sizeof(float)));
+  const u32x4 b_words = rsrc_words(p.w, (unsigned)((size_t)p.cout_pad * p.k_pad * sizeof(float)));
   const unsigned smem_addr = (unsigned)(unsigned long)(lds_f32*)smem;   // LDS byte address of the staging area
 
   // XCD-aware tile order: workgroups b, b+8, ... share an XCD (and its L2); give each XCD a contiguous
@@ -202,10 +175,10 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvLaunch p, int ti
       const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;                                                \
       const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;                  \
       const unsigned off = ok ? (unsigned)(a_pix[i] + tap_off) * 4u : OOB;                           \
-      dma16(a_words, dst_ + 32 * i * LDS_ROW * 4, off);                                              \
+      dma_piece(a_words, dst_ + 32 * i * LDS_ROW * 4, off);                                          \
     }                                                                                                \
     _Pragma("unroll") for (int i = 0; i < BP; ++i)                                                   \
-      dma16(b_words, dst_ + (BM + 32 * i) * LDS_ROW * 4, b_off + i * b_row_step);                    \
+      dma_piece(b_words, dst_ + (BM + 32 * i) * LDS_ROW * 4, b_off + i * b_row_step);                \
     UT_ADVANCE();                                                                                    \
   }
   /* (slice, tap, channel) of the next chunk */
@@ -244,9 +217,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvLaunch p, int ti
 #define UT_PIECE_ISSUE(IDX)                                                                          \
   {                                                                                                  \
     if constexpr ((IDX) < AP) {                                                                      \
-      dma16(a_words, f_dst + 32 * (IDX) * LDS_ROW * 4, f_off);                            \
+      dma_piece(a_words, f_dst + 32 * (IDX) * LDS_ROW * 4, f_off);                                   \
     } else if constexpr ((IDX) < AP + BP) {                                                          \
-      dma16(b_words, f_dst + (BM + 32 * ((IDX) - AP)) * LDS_ROW * 4, f_off);              \
+      dma_piece(b_words, f_dst + (BM + 32 * ((IDX) - AP)) * LDS_ROW * 4, f_off);                     \
     }                                                                                                \
     if ((IDX) == AP + BP - 1) UT_ADVANCE();                                                          \
   }
@@ -427,10 +400,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvLaunch p, int ti
     const int steps = rank * stagger;         // units of 512 cycles
     for (int i = 0; i < steps; ++i) __builtin_amdgcn_s_sleep(8);
   }
-  // Tile-queue slot: one int behind the staging area, accessed with explicit DS instructions - a `volatile int*`
-  // into LDS compiles to FLAT accesses, after which every fragment wait in the chunk loop becomes lgkmcnt(0).
+  // Tile-queue slot: one int behind the staging area (slot_write / slot_read)
   const unsigned slot_addr = smem_addr + (unsigned)(2 * STAGE * 4);
-#define UT_SLOT_WRITE(V) asm volatile("ds_write_b32 %0, %1" ::"v"(slot_addr), "v"(V) : "memory")
   int tile = slot;
   UT_SETUP(tile);
   UT_FETCH(0);
@@ -452,7 +423,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvLaunch p, int ti
     for (int c = 0; c + 1 < n_chunks; ++c) {
       UT_CHUNK_FINE(buf);
       buf ^= 1;
-      if (c == 0 && tid == 0) UT_SLOT_WRITE(grid + ticket);   // ordered before its read by the later chunk barriers
+      if (c == 0 && tid == 0) slot_write(slot_addr, grid + ticket);   // ordered before its read by the later chunk barriers
     }
     // The next tile comes from a device-wide queue (first round: static XCD-contiguous slots; afterwards one
     // atomic per workgroup per tile, taken a whole tile ahead by wave 0 and handed over through LDS - the chunk
@@ -464,13 +435,11 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvLaunch p, int ti
     const unsigned e_slab = (unsigned)e_sp * (unsigned)(M * p.cout_store) * 4u;     // byte offset of the split's slab
     const float e_floor = p.relu ? 0.f : -__builtin_huge_valf();   // 0 with ReLU, -inf without: one v_max, no branch
     if (n_chunks <= 2) {                  // too few chunk barriers to order the queue slot: do it explicitly
-      if (n_chunks == 1 && tid == 0) UT_SLOT_WRITE(grid + ticket);
+      if (n_chunks == 1 && tid == 0) slot_write(slot_addr, grid + ticket);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __syncthreads();
     }
-    int next_v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(next_v) : "v"(slot_addr) : "memory");
-    const int next = __builtin_amdgcn_readfirstlane(next_v);
+    const int next = slot_read(slot_addr);
     // Last chunk: the first chunk, bias and residual of the NEXT tile are fetched under it, and the finished
     // accumulators are stored ((ReLU) + 16-byte stores through a buffer descriptor: pixels beyond M and channel quads
     // beyond cout get an out-of-range offset and are dropped) in the MFMA gaps of its last group.  No branch: without
@@ -481,7 +450,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvLaunch p, int ti
     if ((unsigned)next >= (unsigned)n_tiles) break;     // (unsigned: a corrupt queue word cannot keep the loop alive)
     tile = next;
   }
-#undef UT_SLOT_WRITE
 #undef UT_SETUP
 #undef UT_DECOMP
 #undef UT_FETCH
@@ -519,13 +487,8 @@ static hipError_t launch_cfg(const ConvLaunch& c, hipStream_t s) {
   const size_t lds = 2 * (size_t)(BM + BN) * LDS_ROW * sizeof(float) + 16;   // + tile-queue slot
   // the attribute belongs to (kernel, device): one bit per device, set on the first launch there
   static std::atomic<unsigned long long> attr_set{0};
-  const unsigned long long dev_bit = (c.device >= 0 && c.device < 64) ? 1ull << c.device : 0ull;
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit) || !dev_bit) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<BM, BN, WR, WC, NCHW, C32, SPLITK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
+  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, (int)lds, &conv_igemm_kernel<BM, BN, WR, WC, NCHW, C32, SPLITK>);
+  if (attr_e != hipSuccess) return attr_e;
   // persistent grid: as many workgroups as stay resident (LDS bound), never more than tiles
   const int per_cu = (int)((160 * 1024) / lds);
   int grid = c.num_cu * (per_cu < 1 ? 1 : per_cu);

@@ -14,15 +14,10 @@
 // lane owns one pixel and accumulator register quads are 4 consecutive channels (16-byte NHWC accesses).
 // LDS rows are 128 B (32 floats) with the 16-byte chunks XOR-swizzled by ((row >> 1) & 7), applied on the source
 // side of the DMA; rows are "pixel of the patch" resp. "(tap, output channel)".
-#include <atomic>
-
 #include "ut_kernels.h"
+#include "ut_conv_dev.h"
 
 namespace ut {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) float lds_f32p;
 
 namespace {
 constexpr int TY = 16, TX = 24, NW = 12;    // output tile is TY x TX pixels, one 32-pixel block per wave: 12 waves,
@@ -39,23 +34,6 @@ constexpr int PATCH_INSTR = PROWS / 8;      // 41 wave-level DMA instructions pe
 constexpr int W_INSTR = 9 * C / 8;          // 36
 constexpr unsigned OOBP = 0xFFFFFF00u;
 
-__device__ __forceinline__ void dma16p(u32x4 rsrc, unsigned lds_addr, unsigned voffset) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voffset), "s"(lds_addr), "s"(rsrc)
-      : "memory");
-}
-__device__ __forceinline__ u32x4 rsrc_words(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
 }  // namespace
 
 // SPLIT: the arithmetic of conv_split.hip (two fp16 pieces per operand, three products per k on v_mfma_f32_32x32x16_f16,
@@ -65,38 +43,14 @@ __device__ __forceinline__ u32x4 rsrc_words(const void* base, unsigned bytes) {
 // 9 x 16 of 64: the kernel is then bound by the tile's HBM traffic (patch in, residual in, tile out), not by the matrix pipe.
 // The activations are multiplied by a power of two taken from the producer's max word before they are split
 // (ut_kernels.h::split_act_scale), so the split has no precondition on their magnitude; the kernel leaves its own max word.
-typedef _Float16 f16x8p __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2p __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split_pair_p(float a, float b, unsigned& p0, unsigned& p1) {
-  const f16x2p h = __builtin_bit_cast(f16x2p, __builtin_amdgcn_cvt_pkrtz(a, b));
-  const float ra = a - (float)h[0], rb = b - (float)h[1];
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-
-__device__ __forceinline__ void split_pair_scaled_p(float a, float b, float s, unsigned& p0, unsigned& p1) {
-  const f16x2p h = __builtin_bit_cast(f16x2p, __builtin_amdgcn_cvt_pkrtz(a * s, b * s));
-  const float ra = __builtin_fmaf(a, s, -(float)h[0]), rb = __builtin_fmaf(b, s, -(float)h[1]);   // exact products: see conv_split.hip
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-
 template <bool SPLIT>
 __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p, int tiles_x, int tiles_per_img, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* w_lds = smem;                                  // [9*32 rows][32]
   float* patch0 = smem + W_FLOATS;                      // 2 x [328 rows][32]
-  // tile-queue hand-over words behind the patches.  Accessed with explicit DS instructions: a `volatile int*`
-  // into LDS is compiled as a FLAT load, which counts on vmcnt and would wait for the tile's stores.
-  const unsigned slot_addr0 = (unsigned)(unsigned long)(lds_f32p*)smem + (unsigned)((W_FLOATS + 2 * P_FLOATS) * 4);
-  auto slot_write = [&](int idx, int v) {
-    asm volatile("ds_write_b32 %0, %1" ::"v"(slot_addr0 + 4u * (unsigned)idx), "v"(v) : "memory");
-  };
-  auto slot_read = [&](int idx) {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(slot_addr0 + 4u * (unsigned)idx) : "memory");
-    return __builtin_amdgcn_readfirstlane(v);
-  };
+  // tile-queue hand-over words behind the patches (slot_write / slot_read)
+  const unsigned slot_addr0 = (unsigned)(unsigned long)(lds_f32*)smem + (unsigned)((W_FLOATS + 2 * P_FLOATS) * 4);
+  auto slot_addr = [&](int idx) { return slot_addr0 + 4u * (unsigned)idx; };
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -104,7 +58,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
   const int fr = lane & 31, fh = lane >> 5;
   const int H = p.H, W = p.W;
   const int M = p.n_img * H * W;
-  const unsigned smem_addr = (unsigned)(unsigned long)(lds_f32p*)smem;
+  const unsigned smem_addr = (unsigned)(unsigned long)(lds_f32*)smem;
 
   // SPLIT: a landed patch (fp32 rows, 16-byte group g at position g ^ swizzle) is split IN PLACE, once per tile - a value's
   // two fp16 pieces take its 4 bytes; group q = 4 * piece + k / 8 at position q ^ swizzle.  Thread t < PROWS owns row t.
@@ -127,10 +81,10 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
 #pragma unroll
       for (int kg = 0; kg < 4; ++kg) {
         unsigned a0, a1, a2, a3, b0, b1, b2, b3;
-        split_pair_scaled_p(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
-        split_pair_scaled_p(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
-        split_pair_scaled_p(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
-        split_pair_scaled_p(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
+        split_pair_scaled(f[2 * kg].x, f[2 * kg].y, x_scale, a0, b0);
+        split_pair_scaled(f[2 * kg].z, f[2 * kg].w, x_scale, a1, b1);
+        split_pair_scaled(f[2 * kg + 1].x, f[2 * kg + 1].y, x_scale, a2, b2);
+        split_pair_scaled(f[2 * kg + 1].z, f[2 * kg + 1].w, x_scale, a3, b3);
         u32x4 a, b;
         a.x = a0; a.y = a1; a.z = a2; a.w = a3;
         b.x = b0; b.y = b1; b.z = b2; b.w = b3;
@@ -151,14 +105,14 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
   // ---- weights -> LDS once (row = tap*32 + n, swizzle by n)
   for (int k = wave; k < W_INSTR; k += NW) {
     if constexpr (SPLIT) {     // rows 0..31 of w_split: [tap][k-step][plane][lane][8 halves], one 1-KB block per piece
-      dma16p(w_words, smem_addr + (unsigned)(k * 1024), (unsigned)(k * 1024 + lane * 16));
+      dma_piece(w_words, smem_addr + (unsigned)(k * 1024), (unsigned)(k * 1024 + lane * 16));
       continue;
     }
     const int e = k * 64 + lane;
     const int row = e >> 3, cpos = e & 7;
     const int n = row & 31, tap = row >> 5;
     const int c4 = cpos ^ ((n >> 1) & 7);
-    dma16p(w_words, smem_addr + (unsigned)(k * 64 * 16), (unsigned)((n * p.k_pad + tap * C + 4 * c4) * 4));
+    dma_piece(w_words, smem_addr + (unsigned)(k * 64 * 16), (unsigned)((n * p.k_pad + tap * C + 4 * c4) * 4));
   }
 
   // ---- per-lane constants of the patch DMA: which patch pixel / channel chunk each of my pieces is
@@ -199,7 +153,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
       const int gy = y0 - 1 + pc_py[j], gx = x0 - 1 + pc_px[j];
       const bool ok = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
       const unsigned off = ok ? (unsigned)((((row0 + gy) * W + gx) * C + 4 * pc_c4[j]) * 4) : OOBP;
-      dma16p(in_words, smem_addr + (unsigned)((W_FLOATS + buf * P_FLOATS) * 4 + k * 64 * 16), off);
+      dma_piece(in_words, smem_addr + (unsigned)((W_FLOATS + buf * P_FLOATS) * 4 + k * 64 * 16), off);
     }
   };
 
@@ -256,7 +210,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
   init_load(c_row0, c_y0, c_x0);
   {
     const int t0 = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, q_rsrc, q_off, 0, 0);
-    if (tid == 0) slot_write(2, grid + t0);
+    if (tid == 0) slot_write(slot_addr(2), grid + t0);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
@@ -265,7 +219,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
   }
-  int next = slot_read(2);
+  int next = slot_read(slot_addr(2));
   int cur = 0;
 
 #define UTP_EPILOGUE(M_)                                                                              \
@@ -332,7 +286,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
           // the ticket and combine bias+residual NOW, in front of the last MFMA group and of the stores (vmcnt
           // counts stores too: waiting at the barrier would cost every wave a write round trip per tile)
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (tid == 0) slot_write(cur, grid + ticket);
+          if (tid == 0) slot_write(slot_addr(cur), grid + ticket);
           if (has_next) ready = init_combine();
           asm volatile("" : "+v"(ready));
         }
@@ -359,9 +313,9 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
   }
 #define UTS_MFMA(SET)                                                                                \
   {                                                                                                  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8p, wq##SET[0]), __builtin_bit_cast(f16x8p, pr##SET[1]), acc, 0, 0, 0); \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8p, wq##SET[1]), __builtin_bit_cast(f16x8p, pr##SET[0]), acc, 0, 0, 0); \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8p, wq##SET[0]), __builtin_bit_cast(f16x8p, pr##SET[0]), acc, 0, 0, 0); \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq##SET[0]), __builtin_bit_cast(f16x8, pr##SET[1]), acc, 0, 0, 0); \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq##SET[1]), __builtin_bit_cast(f16x8, pr##SET[0]), acc, 0, 0, 0); \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq##SET[0]), __builtin_bit_cast(f16x8, pr##SET[0]), acc, 0, 0, 0); \
   }
 #define UTS_PIN() __builtin_amdgcn_sched_barrier(0)
       UTS_READ(X, 0, 0);
@@ -374,7 +328,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
           UTS_READ(X, tap + 1, 0);
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (tid == 0) slot_write(cur, grid + ticket);
+          if (tid == 0) slot_write(slot_addr(cur), grid + ticket);
           if (has_next) ready = init_combine();
           asm volatile("" : "+v"(ready));
         }
@@ -399,7 +353,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
       __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_s_barrier();
     }
-    const int next2 = slot_read(cur);
+    const int next2 = slot_read(slot_addr(cur));
     tile = next;
     next = next2;
     c_row0 = n_row0; c_y0 = n_y0; c_x0 = n_x0;
@@ -425,16 +379,9 @@ hipError_t launch_conv_patch(const ConvLaunch& c, hipStream_t s) {
   const size_t lds = (size_t)(W_FLOATS + 2 * P_FLOATS) * sizeof(float) + 16;
   // the attribute belongs to (kernel, device): one bit per device, set on the first launch there
   static std::atomic<unsigned long long> attr_set{0};
-  const unsigned long long dev_bit = (c.device >= 0 && c.device < 64) ? 1ull << c.device : 0ull;
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit) || !dev_bit) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c32_patch_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c32_patch_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
+  const hipError_t attr_e =
+      set_dynamic_lds_once(attr_set, c.device, (int)lds, &conv3x3_c32_patch_kernel<false>, &conv3x3_c32_patch_kernel<true>);
+  if (attr_e != hipSuccess) return attr_e;
   int grid = c.num_cu;           // one 512-thread workgroup per CU (LDS: 121 KB)
   if (grid > n_tiles) grid = n_tiles;
   if (c.w_split && c.split_unscale > 0.f)      // split-fp16 arithmetic (ut_set_conv_arithmetic)

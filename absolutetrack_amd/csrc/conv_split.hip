@@ -37,40 +37,16 @@
 // as in conv_igemm.hip: a lane owns one pixel, register quads are 4 consecutive channels).
 #include <math.h>
 
-#include <atomic>
-
 #include "ut_kernels.h"
+#include "ut_conv_dev.h"
 
 namespace ut {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(3))) unsigned lds_u32;
 
 constexpr unsigned OOB = 0xFFFFFF00u;
 
-// LDS-DMA piece (see conv_igemm.hip::dma16): per-lane byte offset + wave-uniform byte offset
-__device__ __forceinline__ void dma_piece(u32x4 rsrc, unsigned lds_addr, unsigned voffset, unsigned soffset) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voffset), "s"(lds_addr), "s"(rsrc), "s"(soffset)
-      : "memory");
-}
-__device__ __forceinline__ u32x4 rsrc_words(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
 __device__ __forceinline__ int fdiv(int n, int d, float inv_d) {
   int q = (int)((float)n * inv_d);
   int r = n - q * d;
@@ -79,21 +55,6 @@ __device__ __forceinline__ int fdiv(int n, int d, float inv_d) {
   return q;
 }
 
-// two fp32 values -> their fp16 pieces (first, remainder), each packed {b, a}
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& p0, unsigned& p1) {
-  const f16x2 h = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(a, b));
-  const float ra = a - (float)h[0], rb = b - (float)h[1];
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-// the pieces of a * s and b * s for a power of two s: the products are exact, so fma(a, s, -h) is the remainder (a * s) - h
-// in one instruction that also converts h (v_fma_mix_f32)
-__device__ __forceinline__ void split_pair_scaled(float a, float b, float s, unsigned& p0, unsigned& p1) {
-  const f16x2 h = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(a * s, b * s));
-  const float ra = __builtin_fmaf(a, s, -(float)h[0]), rb = __builtin_fmaf(b, s, -(float)h[1]);
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
 __device__ __forceinline__ f16x8 frag(const unsigned (&v)[4]) {
   u32x4 t;
   t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
@@ -430,7 +391,7 @@ __global__ __launch_bounds__(512, 1) void conv_split_kernel(ConvLaunch p, int ti
       if (c == 1 && tid == 0) {                                                                      \
         int t_ = ticket;                                                                             \
         asm volatile("" : "+v"(t_));   /* first use HERE: hoisted above the loop it would wait (vmcnt) at the tile's start */ \
-        asm volatile("ds_write_b32 %0, %1" ::"v"(slot_addr), "v"(grid + t_) : "memory");             \
+        slot_write(slot_addr, grid + t_);                                                            \
       }                                                                                              \
     }                                                                                                \
     /* transfers: piece k of the wave (weights first) at chunk slot PS0 + k * PSTEP */                \
@@ -552,7 +513,7 @@ __global__ __launch_bounds__(512, 1) void conv_split_kernel(ConvLaunch p, int ti
       // was written during chunk 1 and published by the synchronisations since); HALO: the patch stream enters it with
       // the tile's last slice, nine chunks ahead
       if (c == n_chunks - (HALO ? 9 : 3)) {
-        int nv;
+        int nv;      // (not slot_read(): inlined from a function, the compiler orders the operands of the setup's mask ANDs the other way round)
         asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(nv) : "v"(slot_addr) : "memory");
         next_tile = __builtin_amdgcn_readfirstlane(nv);
         if constexpr (HALO) {
@@ -688,13 +649,8 @@ hipError_t launch_split_cfg(const ConvLaunch& c, hipStream_t s) {
   const int n_tiles = tiles_m * tiles_n;
   const size_t lds = (HALO ? 2 * (size_t)320 * 128 : 3 * (size_t)BM * 128) + (HALO ? 4 : 3) * (size_t)BN * 128 + 256 + 16;
   static std::atomic<unsigned long long> attr_set{0};
-  const unsigned long long dev_bit = (c.device >= 0 && c.device < 64) ? 1ull << c.device : 0ull;
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit) || !dev_bit) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_split_kernel<BM, BN, WR, WC, HALO>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
+  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, (int)lds, &conv_split_kernel<BM, BN, WR, WC, HALO>);
+  if (attr_e != hipSuccess) return attr_e;
   int grid = c.num_cu;
   if (grid > n_tiles) grid = n_tiles;
   hipLaunchKernelGGL((conv_split_kernel<BM, BN, WR, WC, HALO>), dim3(grid), dim3(512), lds, s, c, tiles_n, n_tiles);

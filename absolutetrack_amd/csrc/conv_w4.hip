@@ -29,18 +29,11 @@
 // a k-step's instructions is pinned slot by slot (one MFMA per slot).
 // Same tensors, same weight planes and - per output element - the same products in the same order as
 // conv_split_kernel<256, 128, 4, 2, true>: bit-identical results (tests/test_gpu_parity.py::test_split_f16_four_wave_kernel_...).
-#include <atomic>
-
 #include "ut_kernels.h"
+#include "ut_conv_dev.h"
 
 namespace ut {
 namespace {
-
-typedef float f32x16w __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2w __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8w __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2w __attribute__((ext_vector_type(2)));
 
 constexpr int W4_WPIX = 288;                   // pixels of a wave: nine 32 x 32 blocks against its 32 output channels
 constexpr int W4_MI = 9;
@@ -54,14 +47,6 @@ static_assert(9 % W4_NSET == 0, "the register sets of the weight fragments line 
 // a pixel are then a multiple of 256 bytes apart; an odd multiple of 128 - which spreads a wave's patch stores over all banks -
 // measured the same on every shape: tools/diag/w4_ab.py, W4_ALT_SRCS.)
 constexpr int w4_cap(int pixels, int wi, int hi) { return ((pixels / (wi * hi)) * (hi + 1) * (wi + 1) + 2 * (wi + 2) + 15) / 16 * 16; }
-
-// the pieces of a * s and b * s for a power of two s (conv_split.hip::split_pair_scaled)
-__device__ __forceinline__ void w4_split_pair(float a, float b, float s, unsigned& p0, unsigned& p1) {
-  const f16x2w h = __builtin_bit_cast(f16x2w, __builtin_amdgcn_cvt_pkrtz(a * s, b * s));
-  const float ra = __builtin_fmaf(a, s, -(float)h[0]), rb = __builtin_fmaf(b, s, -(float)h[1]);
-  p0 = __builtin_bit_cast(unsigned, h);
-  p1 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
 
 // WI x HI: the map; SCH: input channels per slice (32: two k-steps per tap; 16: one - half the patch bytes, for maps whose padded
 // tile would not fit twice otherwise); WPX: the tile's pixel halves (1: 288 pixels x 128 output channels, the four waves are its four
@@ -171,22 +156,22 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
   }
 #define W4S_BASE(TILE) ((unsigned)(((TILE) / tiles_n) * (BM * 4)) * (unsigned)p.cin * 4u)
 
-  f32x16w acc[MI];
-  u32x4w xp[MI][2];               // pixel fragments (first piece, remainder): ONE set - a fragment of the next k-step is read into its
+  f32x16 acc[MI];
+  u32x4 xp[MI][2];               // pixel fragments (first piece, remainder): ONE set - a fragment of the next k-step is read into its
                                   // registers as soon as this k-step's last MFMA on it has been issued
-  u32x4w wf[W4_NSET][2];          // weight fragments (plane 0, plane 1) of the wave's 32 output channels
+  u32x4 wf[W4_NSET][2];          // weight fragments (plane 0, plane 1) of the wave's 32 output channels
   float4 stg[S2 ? W4_NLOAD : W4_NSTG];      // patch values between their load and their split (S2: item j of either buffer in stg[j])
   const unsigned w_lane = (unsigned)lane * 16u;
 
   // pixel fragment PC (0 first piece, 1 remainder) of block I for k-step half S (SCH == 32) of tap TAP, base register BASE (buffer
   // included)
 #define W4_READ_X(I, PC, S, TAP, BASE)                                                               \
-  xp[I][PC] = *reinterpret_cast<const u32x4w*>(smem + (BASE)[I] + (unsigned)(((PC) * NHG + (SCH == 32 ? 2 * (S) : 0)) * GSTRIDE + (((TAP) / 3) * PW + (TAP) % 3) * 16));
+  xp[I][PC] = *reinterpret_cast<const u32x4*>(smem + (BASE)[I] + (unsigned)(((PC) * NHG + (SCH == 32 ? 2 * (S) : 0)) * GSTRIDE + (((TAP) / 3) * PW + (TAP) % 3) * 16));
   // weight fragment of plane PL of chunk CH, k-step half S, of the wave's block of the tile column at byte offset WROW
 #define W4_LOAD_W(SET, PL, CH, S, WROW)                                                              \
   {                                                                                                  \
     const unsigned so_ = (WROW) + (unsigned)((wco * n_chunks + (CH)) * 4096 + ((S) * 2 + (PL)) * 1024); \
-    wf[SET][PL] = __builtin_bit_cast(u32x4w, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane, so_, 0)); \
+    wf[SET][PL] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane, so_, 0)); \
   }
   // k-step Q of slice SL: its tap, its chunk of the weight planes and its half of the chunk
   // S2, k-step Q = 0 .. 8 of a 16-channel slice: its plane inside its buffer (buffer 1 from k-step 5 on), its shift in padded
@@ -202,8 +187,8 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
   {                                                                                                  \
     constexpr int pr_ = (N) / MI, i_ = (N) % MI;                                                     \
     constexpr int wp_ = pr_ == 1 ? 1 : 0, xq_ = pr_ == 0 ? 1 : 0;      /* small terms first: x1 w0, x0 w1, x0 w0 */ \
-    acc[i_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8w, xp[i_][xq_]),                       \
-                                                     __builtin_bit_cast(f16x8w, wf[WSET][wp_]), acc[i_], 0, 0, 0);  \
+    acc[i_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, xp[i_][xq_]),         \
+                                                     __builtin_bit_cast(f16x8, wf[WSET][wp_]), acc[i_], 0, 0, 0);  \
   }
   // (the empty asm keeps memory operations, the scheduling barriers everything else, inside their slot)
 #define W4_PIN() { __builtin_amdgcn_sched_barrier(0); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
@@ -211,23 +196,23 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
 #define W4_SPLIT_STORE(V, WA)                                                                        \
   {                                                                                                  \
     unsigned a0_, b0_, a1_, b1_;                                                                     \
-    w4_split_pair((V).x, (V).y, x_scale, a0_, b0_);                                                  \
-    w4_split_pair((V).z, (V).w, x_scale, a1_, b1_);                                                  \
-    *reinterpret_cast<u32x2w*>(smem + (WA)) = u32x2w{a0_, a1_};                                      \
-    *reinterpret_cast<u32x2w*>(smem + (WA) + NHG * GSTRIDE) = u32x2w{b0_, b1_};                      \
+    split_pair_scaled((V).x, (V).y, x_scale, a0_, b0_);                                              \
+    split_pair_scaled((V).z, (V).w, x_scale, a1_, b1_);                                              \
+    *reinterpret_cast<u32x2*>(smem + (WA)) = u32x2{a0_, a1_};                                        \
+    *reinterpret_cast<u32x2*>(smem + (WA) + NHG * GSTRIDE) = u32x2{b0_, b1_};                        \
   }
 
   int tile = slot;
   int next_tile = 0;
   int cur_buf = 0;                // patch buffer of the slice being computed
   unsigned out_bits = 0;
-  const unsigned slot_addr = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem + (unsigned)SLOT;
+  const unsigned slot_addr = (unsigned)(unsigned long)(lds_char*)smem + (unsigned)SLOT;
 
   // ---- prologue (exposed once per workgroup): the patch buffers zeroed (their zero rows stay zero for the life of the workgroup),
   // the patches of the first tile's first AHEAD slices (of the last of them, with three buffers: only what the steady state would
   // have stored by now - the rest stays in its registers for the first slice's first k-steps), the weights of the first W4_DIST
   // k-steps and the pixel fragments of the first
-  for (int k = tid; k < NBUF * STAGE / 16; k += 256) *reinterpret_cast<u32x4w*>(smem + k * 16) = u32x4w{0, 0, 0, 0};
+  for (int k = tid; k < NBUF * STAGE / 16; k += 256) *reinterpret_cast<u32x4*>(smem + k * 16) = u32x4{0, 0, 0, 0};
   __syncthreads();
   unsigned h_base = S2 ? 0u : W4_H_BASE(tile);
   unsigned w_row = (unsigned)((tile % tiles_n) * NCB) * (unsigned)n_chunks * 4096u;     // byte offset of the tile column's planes
@@ -284,21 +269,21 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
           if ((N) >= 19 && (N) <= 26 && q1 == KS) { W4_READ_X(((N) + 8) % 9, 0, 0, 0, nb) }          \
           if (((N) == 10 || (N) == 11) && qd < KS) { W4_LOAD_W(qd % W4_NSET, (N) & 1, W4_CHUNK(sl, qd), W4_HALF(sl, qd), w_row) } \
           if (((N) == 10 || (N) == 11) && qd >= KS) { W4_LOAD_W(qd % W4_NSET, (N) & 1, W4_CHUNK(sl_after, qd - KS), W4_HALF(sl_after, qd - KS), row_after) } \
-          if ((N) == 12 && q >= 4 && q < 4 + W4_NLOAD) { const float4 v_ = stg[(q + W4_NSTG - 4) % W4_NSTG]; w4_split_pair(v_.x, v_.y, x_scale, cv0, cv1); } \
+          if ((N) == 12 && q >= 4 && q < 4 + W4_NLOAD) { const float4 v_ = stg[(q + W4_NSTG - 4) % W4_NSTG]; split_pair_scaled(v_.x, v_.y, x_scale, cv0, cv1); } \
           if ((N) == 13 && q >= 4 && q < 4 + W4_NLOAD) {                                             \
             const float4 v_ = stg[(q + W4_NSTG - 4) % W4_NSTG];                                      \
             unsigned a1_, b1_;                                                                       \
-            w4_split_pair(v_.z, v_.w, x_scale, a1_, b1_);                                            \
-            *reinterpret_cast<u32x2w*>(smem + wbuf + h_wa[(q + 5) % 9]) = u32x2w{cv0, a1_};          \
-            *reinterpret_cast<u32x2w*>(smem + wbuf + h_wa[(q + 5) % 9] + NHG * GSTRIDE) = u32x2w{cv1, b1_}; \
+            split_pair_scaled(v_.z, v_.w, x_scale, a1_, b1_);                                        \
+            *reinterpret_cast<u32x2*>(smem + wbuf + h_wa[(q + 5) % 9]) = u32x2{cv0, a1_};            \
+            *reinterpret_cast<u32x2*>(smem + wbuf + h_wa[(q + 5) % 9] + NHG * GSTRIDE) = u32x2{cv1, b1_}; \
           }                                                                                          \
-          if (KS == 9 && (N) == 12 && q < 4) { const float4 v_ = stg[q % W4_NSTG]; w4_split_pair(v_.x, v_.y, x_scale, cv0, cv1); } \
+          if (KS == 9 && (N) == 12 && q < 4) { const float4 v_ = stg[q % W4_NSTG]; split_pair_scaled(v_.x, v_.y, x_scale, cv0, cv1); } \
           if (KS == 9 && (N) == 13 && q < 4) {      /* values 5 .. 8 of the patch the slice before began: the buffer before wbuf */ \
             const float4 v_ = stg[q % W4_NSTG];                                                      \
             unsigned a1_, b1_;                                                                       \
-            w4_split_pair(v_.z, v_.w, x_scale, a1_, b1_);                                            \
-            *reinterpret_cast<u32x2w*>(smem + pbuf + h_wa[q + 5]) = u32x2w{cv0, a1_};                \
-            *reinterpret_cast<u32x2w*>(smem + pbuf + h_wa[q + 5] + NHG * GSTRIDE) = u32x2w{cv1, b1_}; \
+            split_pair_scaled(v_.z, v_.w, x_scale, a1_, b1_);                                        \
+            *reinterpret_cast<u32x2*>(smem + pbuf + h_wa[q + 5]) = u32x2{cv0, a1_};                  \
+            *reinterpret_cast<u32x2*>(smem + pbuf + h_wa[q + 5] + NHG * GSTRIDE) = u32x2{cv1, b1_};  \
           }                                                                                          \
           if ((N) == 14 && q < W4_NLOAD)                                                             \
             stg[q % W4_NSTG] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, h_base + (unsigned)q * h_step, f_soff, 0)); \
@@ -321,9 +306,7 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
           __builtin_amdgcn_s_barrier();                                                              \
           asm volatile("" ::: "memory");                                                             \
           if (sl == 0) {                                                                             \
-            int nv;                                                                                  \
-            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(nv) : "v"(slot_addr) : "memory"); \
-            next_tile = __builtin_amdgcn_readfirstlane(nv);                                          \
+            next_tile = slot_read(slot_addr);                                                        \
             w_row_next = (unsigned)((next_tile % tiles_n) * NCB) * (unsigned)n_chunks * 4096u;       \
           }                                                                                          \
         }                                                                                            \
@@ -359,9 +342,7 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
             __builtin_amdgcn_s_barrier();                                                            \
             asm volatile("" ::: "memory");                                                           \
             if (q == 8 && sl == 0) {                                                                 \
-              int nv;                                                                                \
-              asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(nv) : "v"(slot_addr) : "memory"); \
-              next_tile = __builtin_amdgcn_readfirstlane(nv);                                        \
+              next_tile = slot_read(slot_addr);                                                      \
               w_row_next = (unsigned)((next_tile % tiles_n) * NCB) * (unsigned)n_chunks * 4096u;     \
             }                                                                                        \
           }                                                                                          \
@@ -375,18 +356,18 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
             const float4 v_ = stg[W4S_CV_J(q, ((N) - 10) / 4) % 9];                                  \
             constexpr int part_ = ((N) - 10) & 3;                                                    \
             if (part_ == 0 || part_ == 2) {                                                          \
-              const f16x2w h_ = __builtin_bit_cast(f16x2w, __builtin_amdgcn_cvt_pkrtz((part_ ? v_.z : v_.x) * x_scale, (part_ ? v_.w : v_.y) * x_scale)); \
+              const f16x2 h_ = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz((part_ ? v_.z : v_.x) * x_scale, (part_ ? v_.w : v_.y) * x_scale)); \
               (part_ ? cvh1 : cvh0) = __builtin_bit_cast(unsigned, h_);                              \
               cvf = (float)h_[0];                                                                    \
             } else {                                                                                 \
-              const f16x2w h_ = __builtin_bit_cast(f16x2w, part_ == 1 ? cvh0 : cvh1);                \
+              const f16x2 h_ = __builtin_bit_cast(f16x2, part_ == 1 ? cvh0 : cvh1);                  \
               const float ra_ = __builtin_fmaf(part_ == 1 ? v_.x : v_.z, x_scale, -cvf);             \
               const float rb_ = __builtin_fmaf(part_ == 1 ? v_.y : v_.w, x_scale, -(float)h_[1]);    \
               const unsigned p_ = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra_, rb_)); \
               if (part_ == 1) cvp0 = p_;                                                             \
               else {                                                                                 \
-                *reinterpret_cast<u32x2w*>(smem + W4S_CV_DST(q) + h_wa[W4S_CV_J(q, ((N) - 10) / 4) % 9]) = u32x2w{cvh0, cvh1}; \
-                *reinterpret_cast<u32x2w*>(smem + W4S_CV_DST(q) + h_wa[W4S_CV_J(q, ((N) - 10) / 4) % 9] + NHG * GSTRIDE) = u32x2w{cvp0, p_}; \
+                *reinterpret_cast<u32x2*>(smem + W4S_CV_DST(q) + h_wa[W4S_CV_J(q, ((N) - 10) / 4) % 9]) = u32x2{cvh0, cvh1}; \
+                *reinterpret_cast<u32x2*>(smem + W4S_CV_DST(q) + h_wa[W4S_CV_J(q, ((N) - 10) / 4) % 9] + NHG * GSTRIDE) = u32x2{cvp0, p_}; \
               }                                                                                      \
             }                                                                                        \
           }                                                                                          \
@@ -513,7 +494,7 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
             const int t = 2 * (h & 1) + t2;
             const float4 a = *reinterpret_cast<const float4*>(ex + (h & 1) * 2048 + (8 * t2 + (lane >> 3)) * 128 + (lane & 7) * 16);
             const float4 res = S2 ? float4{0.f, 0.f, 0.f, 0.f} : rr[S2 ? 0 : i % 6][t];
-            u32x4w o;
+            u32x4 o;
             o.x = __float_as_uint(fmaxf(fmaf(a.x, tot_unscale, bb4.x + res.x), floor_v));
             o.y = __float_as_uint(fmaxf(fmaf(a.y, tot_unscale, bb4.y + res.y), floor_v));
             o.z = __float_as_uint(fmaxf(fmaf(a.z, tot_unscale, bb4.z + res.z), floor_v));
@@ -586,12 +567,8 @@ hipError_t launch_w4_cfg(const ConvLaunch& c, hipStream_t s) {
   const int n_tiles = tiles_m * tiles_n;
   constexpr int lds = (SCH == 32 ? 2 : 3) * (SCH / 4) * w4_cap(BM, WI, HI) * 16 + 16 + 4 * 4096;
   static std::atomic<unsigned long long> attr_set{0};
-  const unsigned long long dev_bit = (c.device >= 0 && c.device < 64) ? 1ull << c.device : 0ull;
-  if (!(attr_set.load(std::memory_order_relaxed) & dev_bit) || !dev_bit) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_w4_kernel<WI, HI, SCH, WPX, S2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
+  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, lds, &conv_w4_kernel<WI, HI, SCH, WPX, S2>);
+  if (attr_e != hipSuccess) return attr_e;
   int grid = c.num_cu;
   if (grid > n_tiles) grid = n_tiles;
   hipLaunchKernelGGL((conv_w4_kernel<WI, HI, SCH, WPX, S2>), dim3(grid), dim3(256), lds, s, c, tiles_n, n_tiles);

@@ -184,6 +184,16 @@ __device__ __forceinline__ void publish_abs_max(unsigned* word, unsigned lane_bi
     atomicMax(word, lane_bits);
 }
 
+// scale = 2^k, unscale = 2^-k with k = 141 - e for a magnitude of biased exponent e - a value in [2^(e - 127), 2^(e - 126)) times 2^k is
+// in [2^14, 2^15) - kept within +-100; k = 0 (scale 1) when the magnitude has `none` (zero, an infinity, a NaN).  Returns k.
+__device__ __forceinline__ int split_pow2_for(int e, bool none, float& scale, float& unscale) {
+  int k = none ? 0 : 141 - e;
+  k = k > 100 ? 100 : k < -100 ? -100 : k;
+  scale = __uint_as_float((unsigned)(127 + k) << 23);
+  unscale = __uint_as_float((unsigned)(127 - k) << 23);
+  return k;
+}
+
 // scale = 2^k, unscale = 2^-k; ok = false when the word holds an infinity / a NaN (scale 1 then).
 // in_obs (optional): the largest magnitude the producer actually stored in this call, when in_max is a calibrated word: the
 // first piece of x * 2^k stays finite while x * 2^k < 2^16, i.e. while x's exponent is at most one above the word's;
@@ -199,18 +209,14 @@ __device__ __forceinline__ unsigned split_act_scale(const unsigned* in_max, cons
   const unsigned obs = in_obs ? (unsigned)__builtin_amdgcn_readfirstlane((int)*in_obs) : 0u;
   const int eo = (int)(obs >> 23);
   int e = (int)(bits >> 23);
-  int k = (bits == 0u || e == 255) ? 0 : 141 - e;  // max in [2^(e-127), 2^(e-126)) -> times 2^k in [2^14, 2^15)
-  k = k > 100 ? 100 : k < -100 ? -100 : k;
+  int k = split_pow2_for(e, bits == 0u || e == 255, scale, unscale);
   adapted = adaptive && in_obs && obs != 0u && eo != 255 && (eo + k > 142 || eo + 11 < e);
   if (adapted) {
     bits = obs;
     e = eo;
-    k = 141 - e;
-    k = k > 100 ? 100 : k < -100 ? -100 : k;
+    k = split_pow2_for(e, false, scale, unscale);
   }
   ok = e != 255;
-  scale = __uint_as_float((unsigned)(127 + k) << 23);
-  unscale = __uint_as_float((unsigned)(127 - k) << 23);
   if (in_obs && !adapted && (eo == 255 || eo + k > 142)) ok = false;      // 2^(eo - 127) * 2^k >= 2^16
   return bits;
 }

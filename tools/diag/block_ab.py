@@ -16,7 +16,7 @@ CSRC = os.path.join(ROOT, "absolutetrack_amd", "csrc")
 n_img = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 hw = 48
 VARIANTS = {
-    "nowait": [('    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n    if (tid == 0) slot_write(cur, grid + ticket);', '    if (tid == 0) slot_write(cur, grid + ticket);')],
+    "nowait": [('    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n    if (tid == 0) slot_write(slot_addr(cur), grid + ticket);', '    if (tid == 0) slot_write(slot_addr(cur), grid + ticket);')],
     "nodma": [("        if (has_next && tap < B_MAXP) issue_piece(tap, n_row0, n_y0, n_x0, cur ^ 1);", "        if (has_next && tap < B_MAXP && p.n_img < 0) issue_piece(tap, n_row0, n_y0, n_x0, cur ^ 1);")],
     "nostore": [("        __builtin_amdgcn_raw_buffer_store_b128(pk, o_rsrc, (unsigned)(m * C + 8 * g4 + 4 * fh) * 4u, 0, 0);",
                  "        __builtin_amdgcn_raw_buffer_store_b128(pk, o_rsrc, p.n_img < 0 ? 0u : B_OOB, 0, 0);")],

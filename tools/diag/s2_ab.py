@@ -26,7 +26,7 @@ def stamp_patches(wave):
     st = lambda i: STAMP.replace("[I]", f"[{i}]")
     return [
         ("    if (!ok && tid == 0 && blockIdx.x == 0 && p.status) atomicOr(p.status, UT_SPLIT_RANGE);\n", ""),
-        ("  f32x16s acc, accd;\n  for (int k = 0; k < my_tiles; ++k) {\n", "  f32x16s acc, accd;\n  unsigned long long st_[8];\n  for (int k = 0; k < my_tiles; ++k) {\n    " + st(0) + "\n"),
+        ("  f32x16 acc, accd;\n  for (int k = 0; k < my_tiles; ++k) {\n", "  f32x16 acc, accd;\n  unsigned long long st_[8];\n  for (int k = 0; k < my_tiles; ++k) {\n    " + st(0) + "\n"),
         ("    // the next tile's patch: landed (every wave counted its pieces in), split by all;", "    " + st(1) + "\n    // the next tile's patch: landed (every wave counted its pieces in), split by all;"),
         ("      S_AWAIT(cnt_addr, 8 * (k + 1))\n", "      S_AWAIT(cnt_addr, 8 * (k + 1))\n      " + st(2) + "\n"),
         # inside the MFMA loop: around the wait for my own pieces (k-step 14); stamps 6 and 7

@@ -4,6 +4,7 @@
     python tools/diag/split_ab.py <cin> <cout> <hw> <n_img> [ksize] [stride]"""
 import ctypes
 import os
+import shutil
 import statistics
 import subprocess
 import sys
@@ -17,9 +18,11 @@ cin, cout, hw, n_img = (int(a) for a in sys.argv[1:5])
 ksize = int(sys.argv[5]) if len(sys.argv) > 5 else 3
 stride = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 # variants of conv_split.hip (text patches of a copy, see VARIANTS) are timed beside the product kernel: name,name,...
+# A patch is (old, new) in conv_split.hip, or (old, new, header) in a header of csrc it includes: build() patches a copy of that
+# header next to the copy of the source, where only that copy's #include finds it.
 VARIANTS = {
     # no fp32 -> fp16 conversion work (wrong numbers): what the VALU split costs
-    "noconv": [("  const f16x2 h = ", "  p0 = __float_as_uint(a); p1 = __float_as_uint(b); return;\n  const f16x2 h = ")],
+    "noconv": [("  const f16x2 h = ", "  p0 = __float_as_uint(a); p1 = __float_as_uint(b); return;\n  const f16x2 h = ", "ut_conv_dev.h")],
     # no transfers after the prologue (stale operands): what the fetch costs
     "nodma": [("#define SP_A_ISSUE(I, OFF) dma_piece(", "#define SP_A_ISSUE(I, OFF) if (p.k_pad < 0) dma_piece("),
               ("#define SP_H_ISSUE(Q, SLICE) dma_piece(", "#define SP_H_ISSUE(Q, SLICE) if (p.k_pad < 0) dma_piece("),
@@ -48,7 +51,7 @@ def c64k_stamp_patches(which):
     return [
         ("    if (!ok && tid == 0 && blockIdx.x == 0 && p.status) atomicOr(p.status, UT_SPLIT_RANGE);\n", ""),      # p.status is the stamp buffer here
         ("  for (int k = 0; k < my_tiles; ++k) {\n", "  unsigned long long st_[8];\n  for (int k = 0; k < my_tiles; ++k) {\n"),
-        ("    {\n      u32x4k pxA[2][2], pxB[2][2];", "    " + st(0) + "\n    {\n      u32x4k pxA[2][2], pxB[2][2];"),
+        ("    {\n      u32x4 pxA[2][2], pxB[2][2];", "    " + st(0) + "\n    {\n      u32x4 pxA[2][2], pxB[2][2];"),
         ("    K_DRAIN();\n", "    K_DRAIN();\n    " + st(1) + "\n    if (k == 3) { st_[2] = st_[1]; st_[3] = st_[1]; }\n"),
         ("      K_AWAIT(cnt_addr + 4u * (unsigned)ks, 4 * (k + 1))\n", "      " + st(2) + "\n      K_AWAIT(cnt_addr + 4u * (unsigned)ks, 4 * (k + 1))\n      " + st(3) + "\n"),
         ("    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");\n    __builtin_amdgcn_s_barrier();\n\n    if (ks == 0) {",
@@ -76,18 +79,25 @@ ALT_SRC = os.environ.get("SPLIT_ALT_SRC")
 
 def build(name, patches, flags=(), alt=None, c64=None, c64k=None, w4=None):
     src = alt or os.path.join(CSRC, "conv_split.hip")
+    work = f"/tmp/conv_split_{name}"      # the patched copies; first on the include path
     if patches:
-        text = open(src).read()
-        for old, new in patches:
-            assert old in text, old
-            text = text.replace(old, new)
-        src = f"/tmp/conv_split_{name}.hip"
-        open(src, "w").write(text)
+        shutil.rmtree(work, ignore_errors=True)
+        os.makedirs(work)
+        texts = {"conv_split.hip": open(src).read()}
+        for old, new, *header in patches:
+            f = header[0] if header else "conv_split.hip"
+            if f not in texts:
+                texts[f] = open(os.path.join(CSRC, f)).read()
+            assert old in texts[f], old
+            texts[f] = texts[f].replace(old, new)
+        for f, text in texts.items():
+            open(os.path.join(work, f), "w").write(text)
+        src = os.path.join(work, "conv_split.hip")
     c64_src = c64 or os.path.join(ROOT, "tools", "diag", "conv_c64r.hip")
     so = f"/tmp/libsplitab_{name}.so"
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-w", *flags, "-o", so,
                            os.path.join(CSRC, "conv_igemm.hip"), os.path.join(CSRC, "conv_patch.hip"), c64_src, c64k or os.path.join(CSRC, "conv_c64k.hip"), w4 or os.path.join(CSRC, "conv_w4.hip"), src,
-                           os.path.join(ROOT, "tools", "diag", "split_entry.hip"), "-I", CSRC])
+                           os.path.join(ROOT, "tools", "diag", "split_entry.hip"), *(["-I", work] if patches else []), "-I", CSRC])
     return ctypes.CDLL(so)
 
 

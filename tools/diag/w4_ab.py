@@ -30,7 +30,7 @@ ABL = {
     "nowload": [("    wf[SET][PL] = __builtin_bit_cast(", "    if (p.k_pad < 0) wf[SET][PL] = __builtin_bit_cast(")],
     "nopatch": [("          if ((N) == 14 && q < W4_NLOAD)  ", "          if ((N) == 14 && q < W4_NLOAD && p.k_pad < 0)  "),
                 ("          if ((N) == 13 && q >= 4 && q < 4 + W4_NLOAD) {", "          if ((N) == 13 && q >= 4 && q < 4 + W4_NLOAD && p.k_pad < 0) {")],
-    "noxread": [("  xp[I][PC] = *reinterpret_cast<const u32x4w*>(smem + (BASE)[I]", "  if (p.k_pad < 0) xp[I][PC] = *reinterpret_cast<const u32x4w*>(smem + (BASE)[I]")],
+    "noxread": [("  xp[I][PC] = *reinterpret_cast<const u32x4*>(smem + (BASE)[I]", "  if (p.k_pad < 0) xp[I][PC] = *reinterpret_cast<const u32x4*>(smem + (BASE)[I]")],
     "s2noload": [("          if ((N) >= 22 && (N) <= 24 && (N) - 22 < W4S_LD_N(q))  ", "          if ((N) >= 22 && (N) <= 24 && (N) - 22 < W4S_LD_N(q) && p.k_pad < 0)  ")],
     "s2nocv": [("          if ((N) >= 10 && (N) <= 21 && ((N) - 10) / 4 < W4S_CV_N(q)) {  ", "          if ((N) >= 10 && (N) <= 21 && ((N) - 10) / 4 < W4S_CV_N(q) && p.k_pad < 0) {  ")],
     "s2nobarrier": [("            __builtin_amdgcn_s_barrier();                                                            \\\n", "            if (p.k_pad < 0) __builtin_amdgcn_s_barrier();                                                            \\\n")],
