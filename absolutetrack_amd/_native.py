@@ -26,7 +26,7 @@ EXPORTS = (
     "ut_set_backbone_lanes", "ut_status_snapshot", "ut_warp_map", "ut_set_block_fusion", "ut_set_resident_weights",
     "ut_canonical_backbone_weights", "ut_set_split_scale", "ut_calibrate_split", "ut_get_split_calibration",
     "ut_gen_crop_cameras_from_window_points", "ut_get_split_adaptations",
-    "ut_mesh_create", "ut_mesh_destroy", "ut_mesh_counts", "ut_skin_mesh",
+    "ut_mesh_create", "ut_mesh_destroy", "ut_mesh_counts", "ut_skin_mesh", "ut_project_points", "ut_render_mesh",
 )
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
@@ -87,6 +87,10 @@ def load_library() -> ctypes.CDLL:
     lib.ut_mesh_counts.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.ut_skin_mesh.restype = i32
     lib.ut_skin_mesh.argtypes = [vp, vp, f32p, i32, f32p, i32, f32p, i32, vp, ctypes.c_float, i32, f32p, f32p, vp]
+    lib.ut_project_points.restype = i32
+    lib.ut_project_points.argtypes = [vp, f32p, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.ut_render_mesh.restype = i32
+    lib.ut_render_mesh.argtypes = [vp, vp, f32p, vp, i32, vp, i32, i32, f32p, vp, vp, vp]
     lib.ut_gen_crop_cameras.restype = i32
     lib.ut_gen_crop_cameras.argtypes = [vp, vp, vp, f32p, f32p, i32, f32p, f32p, vp, vp, i32, i32, i32, i32, i32, i32,
                                         i32, ctypes.c_double, vp, f32p, f32p, vp, vp, vp, f32p, vp]
@@ -329,6 +333,103 @@ def skin_mesh(mesh: Mesh, hand_model: torch.Tensor, joint_angles: torch.Tensor, 
     if rc != 0:
         raise RuntimeError(f"ut_skin_mesh failed ({rc}): {lib.ut_last_error(h).decode()}")
     return (out, out_normals) if out_normals is not None else out
+
+
+UT_CAMERA_FISHEYE62, UT_CAMERA_PINHOLE = 0, 1
+RENDER_MAX_VERTICES = 2368
+
+
+def _raise_entry_error(lib, h, rc: int, what: str):
+    msg = lib.ut_last_error(h).decode()
+    if rc == -1 and "index check:" in msg:
+        raise IndexError(msg)
+    if rc in (-1, -4):
+        raise ValueError(f"{what} failed ({rc}): {msg}")
+    raise RuntimeError(f"{what} failed ({rc}): {msg}")
+
+
+def project_points(points: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, width: int, height: int,
+                   n_points: Optional[int] = None, point_stride: Optional[int] = None, n: Optional[int] = None,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                   engine: Optional["HipEngine"] = None):
+    """ut_project_points: world points through cameras -> (window f64 [n,V,P,2] px, eye_z f64 [n,V,P], flags u8 [n,V,P]: bit 0
+    in front, bit 1 inside [0,width) x [0,height)).  points fp32 [n,P,3] - or, with n / n_points / point_stride given, any fp32
+    view whose row i starts point_stride floats after row i - 1 (keypoints inside pose records are read in place);
+    cam_rows i32 [n,V], -1 = unused view; table f64 [R,32] Fisheye62 source cameras or [R,24] pinhole crop cameras (told
+    apart by the row length).  A cam_rows entry outside [-1, R) raises IndexError - at once, or from engine.poll_status()
+    when `engine` runs deferred checks (then nothing synchronises)."""
+    lib, d = load_library(), points.device
+    table = _need(table, torch.float64, d, "table")
+    if table.dim() != 2 or table.shape[1] not in (24, 32):
+        raise ValueError(f"table must be [R,32] source cameras or [R,24] crop cameras, got {tuple(table.shape)}")
+    kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
+    if n is None:
+        points = _need(points, torch.float32, d, "points")
+        if points.dim() != 3 or points.shape[2] != 3:
+            raise ValueError(f"points must be [n,P,3], got {tuple(points.shape)}")
+        n, n_points = points.shape[0], points.shape[1]
+        point_stride = 3 * n_points
+    elif points.dtype != torch.float32 or n_points is None or point_stride is None:
+        raise ValueError("strided points must be fp32 with n_points and point_stride given")
+    cam_rows = _need(cam_rows, torch.int32, d, "cam_rows")
+    if cam_rows.dim() != 2 or cam_rows.shape[0] != n:
+        raise ValueError(f"cam_rows must be [{n},V], got {tuple(cam_rows.shape)}")
+    v = cam_rows.shape[1]
+    if out is None:
+        out = (torch.empty(n, v, n_points, 2, dtype=torch.float64, device=d),
+               torch.empty(n, v, n_points, dtype=torch.float64, device=d),
+               torch.empty(n, v, n_points, dtype=torch.uint8, device=d))
+    window, eye_z, flags = out
+    for t, shape, dt in ((window, (n, v, n_points, 2), torch.float64), (eye_z, (n, v, n_points), torch.float64),
+                         (flags, (n, v, n_points), torch.uint8)):
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != d or not t.is_contiguous():
+            raise ValueError(f"out must hold contiguous {dt} {shape} on {d}")
+    h = engine._h if engine is not None else None
+    with torch.cuda.device(d):
+        rc = lib.ut_project_points(h, _ptr(points), point_stride, n_points, _ptr(cam_rows), v, _ptr(table), table.shape[0], kind,
+                                   n, int(width), int(height), _ptr(window), _ptr(eye_z), _ptr(flags), _stream(d))
+    if rc != 0:
+        _raise_entry_error(lib, h, rc, "ut_project_points")
+    return window, eye_z, flags
+
+
+def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,
+                crop_size: int = 96, depth=True, tri=True, shade=True, engine: Optional["HipEngine"] = None):
+    """ut_render_mesh: posed meshes [n,V,3] (world, fp32) rasterised into their crop cameras (crop_params f64 [N,24];
+    sample_range i64 [n,2], 0 - 2 crops per pose) -> (depth f32, tri i32, shade u8), each [N,96,96] or None.
+    depth / tri / shade: True = allocate (crops no pose names keep the background: +inf, -1, 0), False = leave out, or a
+    preallocated contiguous tensor to write into (crops no pose names are then left as they are).  A bad sample_range raises
+    IndexError and draws nothing - at once, or from engine.poll_status() when `engine` runs deferred checks."""
+    lib, d = mesh.lib, mesh.device
+    if mesh._h is None:
+        raise ValueError("the Mesh has been closed")
+    vertices = _need(vertices, torch.float32, d, "vertices")
+    if vertices.dim() != 3 or tuple(vertices.shape[1:]) != (mesh.n_vertices, 3):
+        raise ValueError(f"vertices must be [n,{mesh.n_vertices},3], got {tuple(vertices.shape)}")
+    n = vertices.shape[0]
+    crop_params = _need(crop_params, torch.float64, d, "crop_params").reshape(-1, 24)
+    sample_range = _need(sample_range, torch.int64, d, "sample_range")
+    if tuple(sample_range.shape) != (n, 2):
+        raise ValueError(f"sample_range must be [{n},2], got {tuple(sample_range.shape)}")
+    n_crops = crop_params.shape[0]
+    shape = (n_crops, crop_size, crop_size)
+
+    def buf(t, dtype, fill, name):
+        if t is False or t is None:
+            return None
+        if t is True:
+            return torch.full(shape, fill, dtype=dtype, device=d)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != d or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {d}")
+        return t
+    depth, tri, shade = buf(depth, torch.float32, float("inf"), "depth"), buf(tri, torch.int32, -1, "tri"), buf(shade, torch.uint8, 0, "shade")
+    h = engine._h if engine is not None else None
+    with torch.cuda.device(d):
+        rc = lib.ut_render_mesh(h, mesh._h, _ptr(vertices), _ptr(crop_params), n_crops, _ptr(sample_range), n, crop_size,
+                                _ptr(depth), _ptr(tri), _ptr(shade), _stream(d))
+    if rc != 0:
+        _raise_entry_error(lib, h, rc, "ut_render_mesh")
+    return depth, tri, shade
 
 
 def gen_crop_cameras(cam_params: torch.Tensor, camera_angles: torch.Tensor, hand_model: torch.Tensor,

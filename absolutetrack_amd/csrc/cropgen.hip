@@ -10,6 +10,7 @@
 // FK in fp32 (the reference runs it in torch fp32), geometry in fp64 (numpy).  One wave per candidate: a few
 // kFLOP and ~1.5 KB each - latency bound; the win over the reference is doing all frames in one launch
 // instead of ~10 ms of numpy/scipy/torch calls per frame.
+#include "ut_camera.h"
 #include "ut_fk.h"
 #include "ut_kernels.h"
 #include "ut_math.h"
@@ -17,32 +18,6 @@
 namespace ut {
 
 namespace {
-
-// world -> eye of a camera given as cam_params row (R at [12..20], t at [21..23] of camera_to_world)
-__device__ inline void world_to_eye_d(const double* cam, const double* w, double* e) {
-  const double* r = cam + 12;
-  const double* t = cam + 21;
-  const double dx = w[0] - t[0], dy = w[1] - t[1], dz = w[2] - t[2];
-  e[0] = r[0] * dx + r[3] * dy + r[6] * dz;
-  e[1] = r[1] * dx + r[4] * dy + r[7] * dz;
-  e[2] = r[2] * dx + r[5] * dy + r[8] * dz;
-}
-
-// Fisheye62 eye -> window (lib/common/camera.py:80-85,122-143,308-312)
-__device__ inline void fisheye_project_d(const double* cam, const double* e, double* win) {
-  const double r = sqrt(e[0] * e[0] + e[1] * e[1]);
-  const double sc = atan2(r, e[2]) / fmax(r, 2.938735877055719e-39);
-  const double ux = e[0] * sc, uy = e[1] * sc;
-  const double k1 = cam[4], k2 = cam[5], k3 = cam[6], k4 = cam[7], p1 = cam[8], p2 = cam[9], k5 = cam[10], k6 = cam[11];
-  const double pi2 = 9.869604401089358;
-  const double r2 = fmin(fmax(ux * ux + uy * uy, -pi2), pi2);
-  const double r4 = r2 * r2, r6 = r2 * r4;
-  const double radial = 1 + k1 * r2 + k2 * r4 + k3 * r6 + k4 * (r4 * r4) + k5 * (r4 * r6) + k6 * (r6 * r6);
-  const double x = ux * radial, y = uy * radial;
-  const double x2 = x * x, y2 = y * y, xy = x * y, rr = x2 + y2;
-  win[0] = (x + (2 * p2 * xy + p1 * (rr + 2 * x2))) * cam[0] + cam[2];
-  win[1] = (y + (2 * p1 * xy + p2 * (rr + 2 * y2))) * cam[1] + cam[3];
-}
 
 __device__ inline void mat3_mul(const double* a, const double* b, double* c) {
   for (int i = 0; i < 3; ++i)

@@ -1410,6 +1410,7 @@ struct ut_mesh {
   void* verts = nullptr;          // float4 [n_vertices][2], see launch_skin_mesh
   uint32_t* csr_off = nullptr;    // [n_vertices + 1]
   uint32_t* csr_ent = nullptr;    // [3 * n_triangles]
+  int32_t* tris = nullptr;        // int4 [n_triangles]: (a, b, c, 0), the list ut_render_mesh walks
 };
 static_assert(UT_MESH_MAX_VERTICES == ut::MESH_MAX_VERTICES && UT_MESH_MAX_VERTICES <= 65536, "vertex cap");
 
@@ -1480,6 +1481,9 @@ int ut_mesh_create(const float* vertices, int n_vertices, const int32_t* triangl
         ent[fill[v]++] = a | (b << 16);
       }
   }
+  std::vector<int32_t> tri4(nt * 4 + 4, 0);
+  for (size_t t = 0; t < nt; ++t)
+    for (int k = 0; k < 3; ++k) tri4[4 * t + k] = triangles[3 * t + k];
   // ---- upload
   DeviceScope scope(device);
   if (scope.err != hipSuccess) return fail(nullptr, UT_E_HIP, "hipSetDevice", scope.err);
@@ -1488,11 +1492,13 @@ int ut_mesh_create(const float* vertices, int n_vertices, const int32_t* triangl
   hipError_t e = hipMalloc(&m->verts, packed.size() * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&m->csr_off, off.size() * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc((void**)&m->csr_ent, ent.size() * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->tris, tri4.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpy(m->tris, tri4.data(), tri4.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->verts, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->csr_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->csr_ent, ent.data(), ent.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    (void)hipFree(m->verts); (void)hipFree(m->csr_off); (void)hipFree(m->csr_ent);
+    (void)hipFree(m->verts); (void)hipFree(m->csr_off); (void)hipFree(m->csr_ent); (void)hipFree(m->tris);
     delete m;
     return fail(nullptr, UT_E_HIP, "ut_mesh_create: upload", e);
   }
@@ -1503,7 +1509,7 @@ int ut_mesh_create(const float* vertices, int n_vertices, const int32_t* triangl
 int ut_mesh_destroy(ut_mesh* m) {
   if (!m) return UT_OK;
   DeviceScope scope(m->device);
-  (void)hipFree(m->verts); (void)hipFree(m->csr_off); (void)hipFree(m->csr_ent);
+  (void)hipFree(m->verts); (void)hipFree(m->csr_off); (void)hipFree(m->csr_ent); (void)hipFree(m->tris);
   delete m;
   return UT_OK;
 }
@@ -1529,6 +1535,79 @@ int ut_skin_mesh(ut_handle h, const ut_mesh* mesh, const float* hand_model, int 
   HIPCHK(h, ut::launch_skin_mesh(hand_model, n_models, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale, n,
                                  mesh->verts, mesh->csr_off, mesh->csr_ent, mesh->n_vertices, out_vertices, out_normals,
                                  (hipStream_t)stream));
+  return UT_OK;
+}
+
+namespace {
+// the status words an entry with an optional handle checks into, and whether it reads them back itself
+struct StatusTarget { int *dev = nullptr, *host = nullptr, mode = UT_CHECK_SYNC, device = 0; };
+int status_target(ut_handle h, StatusTarget* t) {
+  if (h) { t->dev = h->status; t->host = h->status_host; t->mode = h->check_mode; t->device = h->device; return UT_OK; }
+  DevStatus st;
+  int rc = stateless_status(&t->device, &st);
+  if (rc) return rc;
+  t->dev = st.dev; t->host = st.host;
+  return UT_OK;
+}
+}  // namespace
+
+int ut_project_points(ut_handle h, const float* points, int point_stride, int n_points, const int32_t* cam_rows,
+                      int max_views, const double* table, int n_rows, int table_kind, int n, int width, int height,
+                      double* window, double* eye_z, uint8_t* flags, void* stream) {
+  if (!points || !cam_rows || !table || !window || !eye_z || !flags)
+    return fail(h, UT_E_INVALID, "ut_project_points: null argument");
+  if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
+    return fail(h, UT_E_INVALID, "ut_project_points: table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
+  if (n < 0 || n_points <= 0 || max_views <= 0 || n_rows <= 0 || point_stride < 3 * n_points || width < 0 || height < 0)
+    return fail(h, UT_E_INVALID, "ut_project_points: bad argument");
+  if (n == 0) return UT_OK;
+  StatusTarget st;
+  int rc = status_target(h, &st);
+  if (rc) return rc;
+  DeviceScope scope(st.device);
+  if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
+  hipStream_t s = (hipStream_t)stream;
+  ut::ProjectArgs g{};
+  g.points = points; g.point_stride = point_stride; g.n_points = n_points; g.cam_rows = cam_rows; g.max_views = max_views;
+  g.table = table; g.n_rows = n_rows; g.kind = table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE;
+  g.n = n; g.width = width; g.height = height; g.window = window; g.eye_z = eye_z; g.flags = flags; g.status = st.dev;
+  HIPCHK(h, ut::launch_project_points(g, s));
+  return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, "ut_project_points") : UT_OK;
+}
+
+static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");
+
+int ut_render_mesh(ut_handle h, const ut_mesh* mesh, const float* vertices, const double* crop_params, int n_crops,
+                   const int64_t* sample_range, int n, int crop_size, float* depth, int32_t* tri, uint8_t* shade,
+                   void* stream) {
+  if (!mesh) return fail(h, UT_E_INVALID, "ut_render_mesh: null mesh");
+  if (h && h->device != mesh->device) return fail(h, UT_E_INVALID, "ut_render_mesh: the mesh lives on another device than the handle");
+  if (mesh->n_triangles <= 0) return fail(h, UT_E_INVALID, "ut_render_mesh: the mesh has no triangles");
+  if (crop_size != ut::RENDER_CROP) return fail(h, UT_E_UNSUPPORTED, "ut_render_mesh: crop_size must be 96");
+  if (mesh->n_vertices > UT_RENDER_MAX_VERTICES) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "ut_render_mesh: %d vertices, more than UT_RENDER_MAX_VERTICES (%d) that fit a workgroup's LDS next "
+             "to the depth plane", mesh->n_vertices, UT_RENDER_MAX_VERTICES);
+    return fail(h, UT_E_UNSUPPORTED, msg);
+  }
+  if (n < 0 || n_crops < 0) return fail(h, UT_E_INVALID, "ut_render_mesh: bad argument");
+  if (n == 0) return UT_OK;
+  if (!vertices || !crop_params || !sample_range) return fail(h, UT_E_INVALID, "ut_render_mesh: null argument");
+  if (((uintptr_t)depth | (uintptr_t)tri | (uintptr_t)shade) & 15)
+    return fail(h, UT_E_INVALID, "ut_render_mesh: depth, tri and shade must be 16-byte aligned");
+  DeviceScope scope(mesh->device);
+  if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
+  StatusTarget st;
+  int rc = status_target(h, &st);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ut::RenderArgs g{};
+  g.vertices = vertices; g.nv = mesh->n_vertices; g.tris = (const int4*)mesh->tris; g.nt = mesh->n_triangles;
+  g.crop_params = crop_params; g.sample_range = sample_range; g.n = n; g.n_crops = n_crops;
+  g.depth = depth; g.tri = tri; g.shade = shade; g.status = st.dev;
+  HIPCHK(h, ut::launch_render_check(g, s));
+  if (st.mode == UT_CHECK_SYNC && (rc = check_status(h, st.dev, st.host, s, "ut_render_mesh"))) return rc;
+  HIPCHK(h, ut::launch_render_mesh(g, s));
   return UT_OK;
 }
 

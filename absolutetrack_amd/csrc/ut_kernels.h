@@ -287,6 +287,45 @@ hipError_t launch_skin_mesh(const float* hand_model, int n_models, const float* 
                             const uint32_t* csr_off, const uint32_t* csr_ent, int nv, float* out_v, float* out_n,
                             hipStream_t s);
 
+// World points into camera windows (render.hip), one thread per (pose, view, point).
+enum : int { PROJECT_FISHEYE62 = 0, PROJECT_PINHOLE = 1 };
+struct ProjectArgs {
+  const float* points;          // [n] rows of point_stride floats, the first 3 * n_points of a row are its points
+  int point_stride, n_points;
+  const int32_t* cam_rows;      // [n,max_views] row of `table`, -1 = unused view
+  int max_views;
+  const double* table;          // [n_rows,32] source cameras (PROJECT_FISHEYE62) or [n_rows,24] crop cameras (PROJECT_PINHOLE)
+  int n_rows, kind, n;
+  int width, height;            // bit 1 of flags: inside [0,width) x [0,height)
+  double* window;               // [n,max_views,n_points,2]
+  double* eye_z;                // [n,max_views,n_points]
+  uint8_t* flags;               // [n,max_views,n_points]
+  int* status;                  // sticky status word: UT_BAD_SRC_INDEX for a cam_rows entry outside [-1, n_rows)
+};
+hipError_t launch_project_points(const ProjectArgs& g, hipStream_t s);
+
+// Posed meshes rasterised into 96x96 crop cameras (render.hip), one workgroup per (pose, view).
+//  tris int4 [nt]: (a, b, c, 0) per triangle.  The projected vertices of a pose (12 nv bytes, dynamic) share the workgroup's LDS
+//  with a 48 x 96 plane of 64-bit (depth, triangle) words (36864 bytes): RENDER_MAX_VERTICES is what fits the 64 KB a workgroup
+//  gets without a per-device function attribute (65536 - 36864 = 28672 >= 12 * 2368).  Public as UT_RENDER_MAX_VERTICES.
+constexpr int RENDER_CROP = 96;
+constexpr int RENDER_MAX_VERTICES = 2368;
+struct RenderArgs {
+  const float* vertices;        // [n,nv,3] world
+  int nv;
+  const int4* tris;
+  int nt;
+  const double* crop_params;    // [n_crops,24]
+  const int64_t* sample_range;  // [n,2]
+  int n, n_crops;
+  float* depth;                 // [n_crops,96,96] or null
+  int32_t* tri;                 // [n_crops,96,96] or null
+  uint8_t* shade;               // [n_crops,96,96] or null
+  int* status;                  // sticky status word: UT_BAD_SAMPLE_RANGE
+};
+hipError_t launch_render_check(const RenderArgs& g, hipStream_t s);
+hipError_t launch_render_mesh(const RenderArgs& g, hipStream_t s);
+
 // Batched crop-camera generation (cropgen.hip): one candidate = one (frame, hand) label pose.
 struct CropGenArgs {
   const double* cam_params;     // [n_frames*n_cams,32] source camera rows (layout of ut_warp_crops)

@@ -216,3 +216,45 @@ def skin_mesh(hand_model: HandModel, joint_angles: torch.Tensor, wrist_transform
     if normals:
         return res[0].reshape(shape).to(src_device), res[1].reshape(shape).to(src_device)
     return res.reshape(shape).to(src_device)
+
+
+def render_mesh(hand_model: HandModel, joint_angles: torch.Tensor, wrist_transforms: torch.Tensor, crop_cameras,
+                mirror: Optional[torch.Tensor] = None, sample_range: Optional[torch.Tensor] = None):
+    """Pose the model's mesh (skin_mesh) and rasterise it into 96x96 pinhole crop cameras on the HIP kernel csrc/render.hip
+    (no CPU implementation): (depth f32 [N,96,96] eye-space z of the nearest surface, +inf on background; tri i32 [N,96,96]
+    the triangle seen, -1 on background; shade u8 [N,96,96] flat headlight shading, 0 on background).
+    joint_angles [n,22] (or [22]), wrist_transforms [n,4,4], mirror as for skin_mesh.  crop_cameras: an f64 [N,24] tensor /
+    array of crop_params rows (geometry.pack_crop_camera), or a list of PinholePlaneCameraModel.  sample_range i64 [n,2]:
+    pose i is drawn into crops [sample_range[i,0], sample_range[i,1]) - at most two; by default every pose is drawn into
+    N / n consecutive crops.  Results come back on the device of joint_angles."""
+    from . import geometry
+    ja = joint_angles.reshape(-1, 22)
+    n = ja.shape[0]
+    src_device = joint_angles.device
+    dev = src_device if src_device.type == "cuda" else fk_device()
+    if isinstance(crop_cameras, (list, tuple)):
+        crop_cameras = np.stack([geometry.pack_camera_model(c) for c in crop_cameras]) if len(crop_cameras) else np.zeros((0, 24))
+    if not isinstance(crop_cameras, torch.Tensor):
+        crop_cameras = torch.from_numpy(np.ascontiguousarray(crop_cameras, np.float64))
+    crop_params = crop_cameras.reshape(-1, 24).to(dev, torch.float64)
+    if sample_range is None:
+        per = crop_params.shape[0] // max(n, 1)
+        if per * n != crop_params.shape[0] or per > 2:
+            raise ValueError(f"{crop_params.shape[0]} crop cameras for {n} poses: give sample_range")
+        ends = torch.arange(1, n + 1, dtype=torch.int64) * per
+        sample_range = torch.stack([ends - per, ends], 1)
+    mesh = device_mesh(hand_model, dev)
+    verts = _native.skin_mesh(mesh, device_blob(hand_model, dev), ja.to(dev, torch.float32),
+                              wrist_transforms.reshape(n, 4, 4).to(dev, torch.float32),
+                              mirror=None if mirror is None else mirror.reshape(n).to(dev, torch.int64))
+    depth, tri, shade = _native.render_mesh(mesh, verts, crop_params, sample_range.to(dev, torch.int64))
+    return depth.to(src_device), tri.to(src_device), shade.to(src_device)
+
+
+def overlay(crops: torch.Tensor, shade: torch.Tensor, tri: torch.Tensor, alpha: float = 0.6) -> torch.Tensor:
+    """The shaded hand laid over fp32 crops [N,96,96] (HotPath(keep_crops=True).crops): where a triangle is seen
+    (tri >= 0) the pixel becomes (1 - alpha) * crop + alpha * shade / 255 * (the crops' largest value), elsewhere it stays.
+    Plain torch on the tensors' device; no kernel."""
+    white = crops.max().clamp_min(1e-12) if crops.numel() else crops.new_ones(())
+    lit = shade.to(crops.dtype) * (white / 255.0)
+    return torch.where(tri >= 0, (1.0 - alpha) * crops + alpha * lit, crops)

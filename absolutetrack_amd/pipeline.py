@@ -202,6 +202,28 @@ def crop_plan_from_window_points(cam_params, keypoints, src_row, hand_idx, devic
             "sample_range": torch.stack([ends - nv, ends], 1)[keep], "hand_idx": hand_idx[keep]}
 
 
+def project_keypoints(points: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor, src_wh: Tuple[int, int],
+                      engine: Optional[_native.HipEngine] = None, n_points: Optional[int] = None,
+                      point_stride: Optional[int] = None):
+    """Batched tracker.project_landmarks: the world points of n hand-samples into the source cameras that see them, ONE
+    ut_project_points launch.  points fp32 [n,P,3] on the device - or HotPath records [n,123] with n_points=21,
+    point_stride=RECORD passed as `records[:, POSE_REC:]`, read in place; cam_params f64 [R,32] (FrameBatch.cam_params);
+    src_row i32 [n,V] rows of cam_params per view, -1 where unused (FrameBatch.src_index gathered by sample_range);
+    src_wh (width, height) of the source images.  Returns (window f64 [n,V,P,2], eye_z f64 [n,V,P], flags u8 [n,V,P])."""
+    n = points.shape[0] if n_points is not None else None
+    return _native.project_points(points, src_row, cam_params, src_wh[0], src_wh[1], n_points=n_points,
+                                  point_stride=point_stride, n=n, engine=engine)
+
+
+def view_rows(src_index: torch.Tensor, sample_range: torch.Tensor, max_views: int = MAX_VIEW_NUM) -> torch.Tensor:
+    """[S,max_views] i32: the entries of a per-crop tensor (FrameBatch.src_index, or arange(n_crops) for the crop cameras
+    themselves) that belong to each sample's views, -1 where the sample has fewer - the cam_rows of project_keypoints."""
+    k = torch.arange(max_views, device=sample_range.device)[None]
+    idx = sample_range[:, :1] + k
+    used = idx < sample_range[:, 1:]
+    return torch.where(used, src_index.long()[idx.clamp(max=max(src_index.shape[0] - 1, 0))], -1).int()
+
+
 class DeviceCropPlanner:
     """Row f1 inside the step: the label poses of a frame block stay on the GPU and every call regenerates the
     crop cameras with one ut_gen_crop_cameras launch and no host round trip, like the reference's per-frame loop
@@ -271,13 +293,16 @@ class HotPath:
 
     def __init__(self, engine: _native.HipEngine, hand_model_mm: HandModel, known_skeleton: bool = True,
                  remap_mode: int = _native.UT_REMAP_CV2_FIXED, keep_crops: bool = False, mesh: bool = False,
-                 mesh_normals: bool = False):
+                 mesh_normals: bool = False, render: bool = False):
         """keep_crops: materialise the fp32 crop tensor (ut_warp_crops + ut_backbone, the crops are then in
         `self.crops`) instead of the fused ut_warp_backbone, whose crops stay u8 in the engine's workspace.
         mesh: every step also poses the hand model's mesh (ut_skin_mesh on the step's pose records, read in place like
         the FK reads them; right hands un-mirrored by hand_idx) into `self.mesh_vertices` [S,V,3] in mm, and with
         mesh_normals the outward unit normals into `self.mesh_normals`.  Needs a hand model with a mesh; the returned
-        records are the same with and without it."""
+        records are the same with and without it.
+        render: implies mesh; every step also draws the step's posed meshes into the step's own crop cameras
+        (ut_render_mesh on b.crop_params / b.sample_range) into `self.render_depth` f32, `self.render_tri` i32 and
+        `self.render_shade` u8, each [n_crops,96,96].  The records are the same with and without it."""
         self.engine = engine
         self.keep_crops = keep_crops
         self.mode = _native.UT_MODE_KNOWN if known_skeleton else _native.UT_MODE_UNKNOWN
@@ -293,7 +318,9 @@ class HotPath:
         self.mesh = None
         self.mesh_vertices = self.mesh_normals = None
         self._mesh_normals_on = bool(mesh_normals)
-        if mesh or mesh_normals:
+        self.render = bool(render)
+        self.render_depth = self.render_tri = self.render_shade = None
+        if mesh or mesh_normals or render:
             self.mesh = device_mesh(hand_model_mm, dev)
         self._bufs = None
 
@@ -308,6 +335,11 @@ class HotPath:
                 shape = (b.n_samples, self.mesh.n_vertices, 3)
                 self.mesh_vertices = torch.empty(shape, device=dev)
                 self.mesh_normals = torch.empty(shape, device=dev) if self._mesh_normals_on else None
+            if self.render:
+                shape = (b.n_crops, arch.CROP, arch.CROP)
+                self.render_depth = torch.full(shape, float("inf"), device=dev)
+                self.render_tri = torch.full(shape, -1, dtype=torch.int32, device=dev)
+                self.render_shade = torch.zeros(shape, dtype=torch.uint8, device=dev)
             self.engine.reserve(b.n_crops, b.n_samples, b.n_slots)
         return self._bufs[1:]
 
@@ -332,6 +364,9 @@ class HotPath:
                 _native.skin_mesh(self.mesh, self.hand_blob, pose, pose[:, 22:], mirror=b.hand_idx, t_scale=1000.0,
                                   ja_stride=arch.POSE_REC, xf_stride=arch.POSE_REC, n=s, out=self.mesh_vertices,
                                   out_normals=self.mesh_normals, engine=eng)
+            if self.render:
+                _native.render_mesh(self.mesh, self.mesh_vertices, b.crop_params, b.sample_range, crop_size=arch.CROP,
+                                    depth=self.render_depth, tri=self.render_tri, shade=self.render_shade, engine=eng)
         rec[:, : arch.POSE_REC].copy_(pose)
         rec[:, arch.POSE_REC:].copy_(kp.reshape(s, -1))
         return rec

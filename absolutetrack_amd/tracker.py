@@ -19,6 +19,7 @@ import torch
 from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
+from .hand import fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
 
 logger = logging.getLogger(__name__)
@@ -82,6 +83,43 @@ def mesh_from_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, hand_i
     if normals:
         return res[0].cpu().numpy(), res[1].cpu().numpy()
     return res.cpu().numpy()
+
+
+def render_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, hand_idx: int, crop_cameras):
+    """The pose drawn into its crop cameras - the dict (or list) of PinholePlaneCameraModel that gen_crop_cameras returns for
+    the hand, at most two: (depth [V,96,96] f32, tri [V,96,96] i32, shade [V,96,96] u8) as numpy arrays, in the cameras'
+    order.  The companion of mesh_from_hand_pose; right hands are un-mirrored the same way, and their crop cameras are
+    x-mirrored, so both hands come out as left hands like the crops the network reads."""
+    cams = list(crop_cameras.values()) if isinstance(crop_cameras, dict) else list(crop_cameras)
+    res = _render_mesh(hand_model, torch.from_numpy(np.asarray(hand_pose.joint_angles)).float()[None],
+                       torch.from_numpy(np.asarray(hand_pose.wrist_xform)).float()[None], cams,
+                       mirror=torch.tensor([1 if hand_idx == RIGHT_HAND_INDEX else 0]),
+                       sample_range=torch.tensor([[0, len(cams)]]))
+    return tuple(r.cpu().numpy() for r in res)
+
+
+def project_landmarks(cameras: List[CameraModel], landmarks_world: np.ndarray) -> np.ndarray:
+    """[n_cams,P,2] window coordinates of world points [P,3] in every camera: camera.eye_to_window(camera.world_to_eye(p))
+    of the reference's analysis scripts (run_eval_known_skeleton_analysis.py:296-358), for all cameras in one
+    ut_project_points launch when they are all Fisheye62 or all pinhole models without distortion; any other camera
+    model goes through its own host methods, as gen_crop_cameras_from_window_points does."""
+    pts = np.asarray(landmarks_world)
+    kinds = {type(c) for c in cameras}
+    native = len(cameras) > 0 and pts.ndim == 2 and (kinds == {geometry.Fisheye62CameraModel} or kinds == {PinholePlaneCameraModel})
+    if native:                               # the kernel serves these cameras: no host fallback, a missing device is an error
+        dev = fk_device()
+        table = torch.from_numpy(np.stack([geometry.pack_camera_model(c) for c in cameras])).to(dev)
+        rows = torch.arange(len(cameras), dtype=torch.int32, device=dev)[None]
+        win, _, _ = _native.project_points(torch.from_numpy(np.ascontiguousarray(pts, np.float32))[None].to(dev), rows, table,
+                                           int(cameras[0].width), int(cameras[0].height))
+        return win[0].cpu().numpy()
+    return project_landmarks_host(cameras, pts)
+
+
+def project_landmarks_host(cameras: List[CameraModel], landmarks_world: np.ndarray) -> np.ndarray:
+    """project_landmarks through the cameras' own numpy methods (float64), any camera model."""
+    pts = np.asarray(landmarks_world, np.float64)
+    return np.stack([cam.eye_to_window(cam.world_to_eye(pts)) for cam in cameras]) if len(cameras) else np.zeros((0,) + pts.shape[:-1] + (2,))
 
 
 def _visible_counts(cameras: List[CameraModel], landmarks_world: np.ndarray) -> List[int]:

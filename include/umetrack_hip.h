@@ -334,6 +334,56 @@ int ut_skin_mesh(ut_handle h, const ut_mesh* mesh, const float* hand_model, int 
                  int ja_stride, const float* wrist_xf, int xf_stride, const int64_t* mirror, float t_scale, int n,
                  float* out_vertices, float* out_normals, void* stream);
 
+/* World points into camera windows, for many (pose, view) pairs in one launch: camera.eye_to_window(camera.world_to_eye(p)) of
+ * lib/common/camera.py:76-94,296-312 (world_to_eye, project, distort.evaluate, * f + c in that order), fp64 throughout, every
+ * multiply and add rounded on its own.
+ *  points     f32, n rows of point_stride floats (point_stride >= 3 * n_points): row i starts with its n_points world points,
+ *             so [n,21,3] landmarks, [n,V,3] mesh vertices and the keypoints inside [n,123] records are read in place
+ *  cam_rows   i32 [n,max_views]: the row of `table` per view, -1 = unused view (window, eye_z and flags are 0 there)
+ *  table      f64 [n_rows,32] Fisheye62 source cameras (table_kind UT_CAMERA_FISHEYE62: the cam_params rows of ut_warp_crops) or
+ *             f64 [n_rows,24] pinhole crop cameras (UT_CAMERA_PINHOLE: its crop_params rows)
+ *  window     f64 [n,max_views,n_points,2] px;  eye_z f64 [n,max_views,n_points];
+ *  flags      u8 [n,max_views,n_points]: bit 0 eye_z > 0 (in front), bit 1 window inside [0,width) x [0,height)
+ * cam_rows is checked on the device like every index tensor: an entry outside [-1, n_rows) writes nothing for its view and
+ * gives UT_E_INVALID - from this call with UT_CHECK_SYNC or h == NULL (one stream synchronisation), from the next
+ * ut_poll_status with UT_CHECK_DEFERRED (then nothing synchronises: capturable).  Stateless: h may be NULL (the caller's
+ * current device).  Stream ordered, no allocation. */
+enum { UT_CAMERA_FISHEYE62 = 0, UT_CAMERA_PINHOLE = 1 };
+int ut_project_points(ut_handle h, const float* points, int point_stride, int n_points, const int32_t* cam_rows,
+                      int max_views, const double* table, int n_rows, int table_kind, int n, int width, int height,
+                      double* window, double* eye_z, uint8_t* flags, void* stream);
+
+/* Posed meshes rasterised into the 96x96 pinhole crop cameras that show them, one launch.
+ *  mesh          its triangles (ut_mesh_create); at most UT_RENDER_MAX_VERTICES vertices (a pose's projected vertices share
+ *                the workgroup's LDS with the depth plane)
+ *  vertices      f32 [n,n_vertices,3] world, e.g. the output of ut_skin_mesh
+ *  crop_params   f64 [n_crops,24], the rows of ut_warp_crops;  sample_range i64 [n,2]: pose i is seen by crops
+ *                [sample_range[i][0], sample_range[i][1]) - 0, 1 or 2 of them, inside [0, n_crops] (the head's tensor)
+ *  crop_size     96
+ * Outputs, each [n_crops,96,96], 16-byte aligned, or NULL; only crops named by sample_range are written:
+ *  depth f32  eye-space z of the nearest surface at the pixel centre (pixel centres at integer coordinates); +inf on background
+ *  tri   i32  the triangle seen there; -1 on background
+ *  shade u8   round(255 |n . c|), n the triangle's unit face normal and c the unit vector from the eye to its centroid, both
+ *             in eye space (flat headlight shading; the same in a mirrored camera); 0 on background
+ * Rules: a vertex is projected in fp64 (world_to_eye, / z, * f + c) and rounded to fp32 (x, y, 1 / z); the rest is fp32 with every
+ * operation rounded on its own.  A triangle with a vertex at eye z < 1e-4 is skipped whole (lib/common/crop.py:25).  No
+ * culling.  With E_ab(p) = (xb - xa)(py - ya) - (yb - ya)(px - xa), taken from the edge's start vertex, and the vertices
+ * ordered so that the area E_01(v2) is positive (zero area covers nothing), a pixel is covered when E_01, E_12 and E_20 are >= 0,
+ * a zero counting only on a top or left edge (yb - ya < 0, or yb == ya and xb - xa > 0; y grows downwards), so a pixel centre
+ * on an edge shared by two triangles belongs to exactly one.  Depth is perspective correct:
+ * 1 / z = w0 + (E_20 (w1 - w0) + E_01 (w2 - w0)) / area with w = 1 / z of the vertices.  The smallest depth wins, the smaller
+ * triangle index on equal depth.  A crop's images depend on nothing but its pose's vertices and its camera: not on the
+ * batch, the launch geometry or scheduling.
+ * Refused with nothing launched: a null mesh / vertices / crop_params / sample_range, a mesh without triangles, a handle of
+ * another device, misaligned outputs -> UT_E_INVALID; crop_size != 96, a mesh beyond UT_RENDER_MAX_VERTICES ->
+ * UT_E_UNSUPPORTED.  sample_range is checked on the device: a bad row gives UT_E_INVALID and nothing is drawn - from this call
+ * with UT_CHECK_SYNC or h == NULL (one stream synchronisation), from the next ut_poll_status with UT_CHECK_DEFERRED (no
+ * synchronisation: capturable).  Runs on the mesh's device; stream ordered, no allocation. */
+#define UT_RENDER_MAX_VERTICES 2368
+int ut_render_mesh(ut_handle h, const ut_mesh* mesh, const float* vertices, const double* crop_params, int n_crops,
+                   const int64_t* sample_range, int n, int crop_size, float* depth, int32_t* tri, uint8_t* shade,
+                   void* stream);
+
 /* HandTracker.gen_crop_cameras for a batch of (frame, hand) label poses in one launch
  * (lib/tracker/tracker.py:222-260 -> lib/tracker/perspective_crop.py:136-180 -> lib/common/crop.py:31-82,
  * lib/common/affine.py:34-76) plus the network camera inputs of lib/tracker/tracker.py:333-337.

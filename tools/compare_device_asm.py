@@ -34,6 +34,8 @@ def export(rev, dst):
 def device_asm(csrc, name):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     out = os.path.join(csrc, name + ".s")
+    if not os.path.exists(os.path.join(csrc, name)):      # a source that one of the two revisions does not have
+        return None
     subprocess.check_call([hipcc] + FLAGS + ["-Wno-unused-command-line-argument", "--offload-device-only", "-S", name, "-o", out], cwd=csrc)
     return [line for line in open(out) if "__hip_cuid_" not in line]
 
@@ -47,10 +49,13 @@ def main():
     differ = 0
     for i, f in enumerate(SOURCES):
         a, b = asm[i], asm[len(SOURCES) + i]
+        if a is None or b is None:
+            print(f"{f:20s} only in {rev_a if b is None else rev_b or 'the working tree'}")
+            continue
         same = a == b
         differ += not same
         print(f"{f:20s} {'identical' if same else 'DIFFERENT'}   ({len(a)} lines)")
-    print(f"{len(SOURCES) - differ} of {len(SOURCES)} identical: {rev_a} vs {rev_b or 'working tree'}")
+    print(f"{len(SOURCES) - differ} of {len(SOURCES)} identical or new: {rev_a} vs {rev_b or 'working tree'}")
     return differ
 
 
