@@ -17,17 +17,57 @@ from . import arch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libumetrack_hip.so")
 
-EXPORTS = (
-    "ut_weight_blob_floats", "ut_create", "ut_destroy", "ut_last_error", "ut_reserve",
-    "ut_set_backbone_chunk", "ut_warp_crops", "ut_backbone", "ut_fuse_temporal_regress",
-    "ut_reset_memory", "ut_get_memory", "ut_fk", "ut_gen_crop_cameras", "ut_gen_crop_matrices",
-    "ut_resample_homography", "ut_keypoint_metrics", "ut_profile_begin", "ut_profile_end", "ut_profile_end_by_kind",
-    "ut_set_index_checks", "ut_poll_status", "ut_warp_backbone", "ut_set_latency_mode", "ut_set_conv_arithmetic",
-    "ut_set_backbone_lanes", "ut_status_snapshot", "ut_warp_map", "ut_set_block_fusion", "ut_set_resident_weights",
-    "ut_canonical_backbone_weights", "ut_set_split_scale", "ut_calibrate_split", "ut_get_split_calibration",
-    "ut_gen_crop_cameras_from_window_points", "ut_get_split_adaptations",
-    "ut_mesh_create", "ut_mesh_destroy", "ut_mesh_counts", "ut_skin_mesh", "ut_project_points", "ut_render_mesh",
-)
+_vp, _i32, _f32, _f64, _sz, _P = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t,
+                                  ctypes.POINTER)
+# Every entry of include/umetrack_hip.h, in the header's order: name -> (restype, argtypes).  load_library() declares
+# exactly these, so an entry cannot be exported without its prototype (tests compare the counts with the header).
+_PROTOTYPES = {
+    "ut_weight_blob_floats": (_sz, []),
+    "ut_create": (_i32, [_i32, _vp, _sz, _P(_vp)]),
+    "ut_canonical_backbone_weights": (_i32, [_vp, _sz, _vp, _sz, _P(_sz)]),
+    "ut_destroy": (_i32, [_vp]),
+    "ut_last_error": (ctypes.c_char_p, [_vp]),
+    "ut_set_index_checks": (_i32, [_vp, _i32]),
+    "ut_poll_status": (_i32, [_vp, _vp]),
+    "ut_status_snapshot": (_i32, [_vp, _vp, _vp]),
+    "ut_set_backbone_lanes": (_i32, [_vp, _i32]),
+    "ut_set_conv_arithmetic": (_i32, [_vp, _i32]),
+    "ut_set_split_scale": (_i32, [_vp, _i32]),
+    "ut_get_split_adaptations": (_i32, [_vp, _P(ctypes.c_uint32), _i32, _vp]),
+    "ut_calibrate_split": (_i32, [_vp, _vp, _i32, _vp]),
+    "ut_get_split_calibration": (_i32, [_vp, _vp]),
+    "ut_set_block_fusion": (_i32, [_vp, _i32]),
+    "ut_set_resident_weights": (_i32, [_vp, _i32]),
+    "ut_set_latency_mode": (_i32, [_vp, _i32]),
+    "ut_reserve": (_i32, [_vp, _i32, _i32, _i32]),
+    "ut_set_backbone_chunk": (_i32, [_vp, _i32]),
+    "ut_warp_crops": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "ut_warp_map": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "ut_backbone": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "ut_warp_backbone": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "ut_fuse_temporal_regress": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32,
+                                        _vp, _vp, _vp]),
+    "ut_reset_memory": (_i32, [_vp]),
+    "ut_get_memory": (_i32, [_vp, _vp, _vp, _i32, _vp]),
+    "ut_fk": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _vp]),
+    "ut_mesh_create": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _P(_vp)]),
+    "ut_mesh_destroy": (_i32, [_vp]),
+    "ut_mesh_counts": (_i32, [_vp, _P(_i32), _P(_i32)]),
+    "ut_skin_mesh": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _vp, _vp]),
+    "ut_project_points": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ut_render_mesh": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ut_gen_crop_cameras": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                   _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ut_gen_crop_cameras_from_window_points": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp,
+                                                      _vp, _vp, _vp, _vp]),
+    "ut_gen_crop_matrices": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "ut_resample_homography": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "ut_keypoint_metrics": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ut_profile_begin": (_i32, [_vp, _vp]),
+    "ut_profile_end": (_i32, [_vp, _vp, _P(_f64), _P(ctypes.c_int64), _P(_f64)]),
+    "ut_profile_end_by_kind": (_i32, [_vp, _vp, _P(_f64), _P(ctypes.c_int64), _P(_f64)]),
+}
+EXPORTS = tuple(_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -51,95 +91,9 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    vp, i32, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    lib.ut_weight_blob_floats.restype = ctypes.c_size_t
-    lib.ut_weight_blob_floats.argtypes = []
-    lib.ut_create.restype = i32
-    lib.ut_create.argtypes = [i32, vp, ctypes.c_size_t, ctypes.POINTER(vp)]
-    lib.ut_destroy.restype = i32
-    lib.ut_destroy.argtypes = [vp]
-    lib.ut_last_error.restype = ctypes.c_char_p
-    lib.ut_last_error.argtypes = [vp]
-    lib.ut_reserve.restype = i32
-    lib.ut_reserve.argtypes = [vp, i32, i32, i32]
-    lib.ut_set_backbone_chunk.restype = i32
-    lib.ut_set_backbone_chunk.argtypes = [vp, i32]
-    lib.ut_warp_crops.restype = i32
-    lib.ut_warp_crops.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, f32p, vp]
-    lib.ut_warp_backbone.restype = i32
-    lib.ut_warp_backbone.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, f32p, vp]
-    lib.ut_backbone.restype = i32
-    lib.ut_backbone.argtypes = [vp, f32p, i32, f32p, vp]
-    lib.ut_fuse_temporal_regress.restype = i32
-    lib.ut_fuse_temporal_regress.argtypes = [vp, f32p, f32p, f32p, vp, vp, vp, vp, i32, i32, i32, i32,
-                                             f32p, i32, i32, f32p, f32p, vp]
-    lib.ut_reset_memory.restype = i32
-    lib.ut_reset_memory.argtypes = [vp]
-    lib.ut_get_memory.restype = i32
-    lib.ut_get_memory.argtypes = [vp, f32p, f32p, i32, vp]
-    lib.ut_fk.restype = i32
-    lib.ut_fk.argtypes = [vp, f32p, i32, f32p, i32, f32p, i32, vp, ctypes.c_float, i32, f32p, vp]
-    lib.ut_mesh_create.restype = i32
-    lib.ut_mesh_create.argtypes = [vp, i32, vp, i32, vp, i32, ctypes.POINTER(vp)]
-    lib.ut_mesh_destroy.restype = i32
-    lib.ut_mesh_destroy.argtypes = [vp]
-    lib.ut_mesh_counts.restype = i32
-    lib.ut_mesh_counts.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    lib.ut_skin_mesh.restype = i32
-    lib.ut_skin_mesh.argtypes = [vp, vp, f32p, i32, f32p, i32, f32p, i32, vp, ctypes.c_float, i32, f32p, f32p, vp]
-    lib.ut_project_points.restype = i32
-    lib.ut_project_points.argtypes = [vp, f32p, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.ut_render_mesh.restype = i32
-    lib.ut_render_mesh.argtypes = [vp, vp, f32p, vp, i32, vp, i32, i32, f32p, vp, vp, vp]
-    lib.ut_gen_crop_cameras.restype = i32
-    lib.ut_gen_crop_cameras.argtypes = [vp, vp, vp, f32p, f32p, i32, f32p, f32p, vp, vp, i32, i32, i32, i32, i32, i32,
-                                        i32, ctypes.c_double, vp, f32p, f32p, vp, vp, vp, f32p, vp]
-    lib.ut_gen_crop_cameras_from_window_points.restype = i32
-    lib.ut_gen_crop_cameras_from_window_points.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, ctypes.c_double, vp,
-                                                           f32p, f32p, vp, vp, vp, vp]
-    lib.ut_gen_crop_matrices.restype = i32
-    lib.ut_gen_crop_matrices.argtypes = [vp, f32p, f32p, f32p, vp, i32, i32, i32, i32, ctypes.c_double, f32p, f32p, f32p,
-                                         vp, vp]
-    lib.ut_resample_homography.restype = i32
-    lib.ut_resample_homography.argtypes = [vp, vp, i32, i32, i32, i32, f32p, i32, i32, f32p, vp]
-    lib.ut_keypoint_metrics.restype = i32
-    lib.ut_keypoint_metrics.argtypes = [vp, f32p, f32p, vp, i32, i32, vp, vp, vp, vp, vp]
-    lib.ut_profile_begin.restype = i32
-    lib.ut_profile_begin.argtypes = [vp, vp]
-    lib.ut_profile_end_by_kind.restype = i32
-    lib.ut_profile_end_by_kind.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
-                                           ctypes.POINTER(ctypes.c_double)]
-    lib.ut_profile_end.restype = i32
-    lib.ut_profile_end.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
-                                   ctypes.POINTER(ctypes.c_double)]
-    lib.ut_set_index_checks.restype = i32
-    lib.ut_set_index_checks.argtypes = [vp, i32]
-    lib.ut_set_backbone_lanes.restype = i32
-    lib.ut_set_backbone_lanes.argtypes = [vp, i32]
-    lib.ut_set_block_fusion.restype = i32
-    lib.ut_set_block_fusion.argtypes = [vp, i32]
-    lib.ut_set_resident_weights.restype = i32
-    lib.ut_set_resident_weights.argtypes = [vp, i32]
-    lib.ut_warp_map.restype = i32
-    lib.ut_warp_map.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-    lib.ut_status_snapshot.restype = i32
-    lib.ut_status_snapshot.argtypes = [vp, vp, vp]
-    lib.ut_set_latency_mode.restype = i32
-    lib.ut_set_latency_mode.argtypes = [vp, i32]
-    lib.ut_set_conv_arithmetic.restype = i32
-    lib.ut_set_conv_arithmetic.argtypes = [vp, i32]
-    lib.ut_poll_status.restype = i32
-    lib.ut_poll_status.argtypes = [vp, vp]
-    lib.ut_set_split_scale.restype = i32
-    lib.ut_set_split_scale.argtypes = [vp, i32]
-    lib.ut_calibrate_split.restype = i32
-    lib.ut_calibrate_split.argtypes = [vp, vp, i32, vp]
-    lib.ut_get_split_calibration.restype = i32
-    lib.ut_get_split_calibration.argtypes = [vp, vp]
-    lib.ut_get_split_adaptations.restype = i32
-    lib.ut_get_split_adaptations.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), i32, vp]
-    lib.ut_canonical_backbone_weights.restype = i32
-    lib.ut_canonical_backbone_weights.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -174,13 +128,11 @@ def canonical_backbone_weights(state_dict) -> np.ndarray:
     blob = state_dict_to_blob(state_dict)
     n = ctypes.c_size_t()
     rc = lib.ut_canonical_backbone_weights(blob.ctypes.data_as(ctypes.c_void_p), blob.size, None, 0, ctypes.byref(n))
-    if rc != 0:
-        raise RuntimeError(f"ut_canonical_backbone_weights failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_canonical_backbone_weights")
     out = np.empty(n.value, np.float32)
     rc = lib.ut_canonical_backbone_weights(blob.ctypes.data_as(ctypes.c_void_p), blob.size,
                                            out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n))
-    if rc != 0:
-        raise RuntimeError(f"ut_canonical_backbone_weights failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_canonical_backbone_weights")
     return out
 
 
@@ -214,26 +166,91 @@ def _need(t: torch.Tensor, dtype, device, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _hip_device(t: torch.Tensor, who: str) -> torch.device:
+    if t.device.type != "cuda":
+        raise NativeLibraryError(f"{who} needs tensors on a HIP device (no CPU fallback)")
+    return t.device
+
+
+def _out(t: Optional[torch.Tensor], shape, dtype, device, name: str, fill=None, flat: bool = False) -> torch.Tensor:
+    """The output buffer of a call.  t is None: a fresh tensor, filled with `fill` if one is given.  Otherwise the caller's
+    own, returned as it is (never pre-filled): it must be contiguous, of this dtype, on this device and of this shape - with
+    flat=True of this many elements, so that e.g. a [n,V,9] staging view stands for [n,V,3,3] - else ValueError."""
+    shape = tuple(shape)
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
+    same = t.numel() == int(np.prod(shape)) if flat else tuple(t.shape) == shape
+    if not same or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {device}")
+    return t
+
+
+# How a negative return code becomes an exception, per family of entries: (class of UT_E_INVALID, class of UT_E_UNSUPPORTED,
+# {marker in a UT_E_INVALID message: its class}); every other code is a RuntimeError.
+_UT_E_INVALID, _UT_E_UNSUPPORTED = -1, -4
+_ERROR_CLASSES = {
+    # HipEngine methods: the reference asserts where the library says "unsupported" (umetrack_model.py:224-229), its tensor
+    # indexing raises IndexError, and the split-fp16 backbone reports an infinity / a NaN among a layer's inputs
+    "engine": (RuntimeError, AssertionError, {"index check:": IndexError, "range check:": FloatingPointError}),
+    "points": (ValueError, ValueError, {"index check:": IndexError}),        # project_points, render_mesh
+    "mesh": (ValueError, ValueError, {}),                                    # Mesh(...): the library refused the mesh
+    "stateless": (RuntimeError, RuntimeError, {}),
+}
+
+
+def _check_rc(lib, h, rc: int, what: str, family: str = "stateless") -> int:
+    """Return a non-negative rc (ut_get_memory's slot count); raise for a negative one with ut_last_error's text - the
+    handle's when there is a handle, else the NULL slot's - as the class _ERROR_CLASSES gives this family of entries."""
+    if rc >= 0:
+        return rc
+    invalid, unsupported, marked = _ERROR_CLASSES[family]
+    msg = lib.ut_last_error(h).decode()
+    cls = RuntimeError
+    if rc == _UT_E_UNSUPPORTED:
+        cls = unsupported
+    elif rc == _UT_E_INVALID:
+        cls = next((c for marker, c in marked.items() if marker in msg), invalid)
+    raise cls(f"{what} failed ({rc}): {msg}")
+
+
+def _fk_args(d, hand_model, joint_angles, wrist_xf, mirror, n: Optional[int]):
+    """The pose arguments of ut_fk / ut_skin_mesh on device d: hand_model [1|n,321]; joint_angles / wrist_xf either packed
+    [n,22] / [n,4,4] (n None) or, with n given, fp32 views into a pose-record buffer that are read in place with the
+    caller's strides; mirror [n] or None.  Returns them ready for the call, with n."""
+    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
+    if n is None:
+        joint_angles = _need(joint_angles, torch.float32, d, "joint_angles").reshape(-1, 22)
+        wrist_xf = _need(wrist_xf, torch.float32, d, "wrist_xf").reshape(-1, 16)
+        n = joint_angles.shape[0]
+        if wrist_xf.shape[0] != n:
+            raise ValueError("joint_angles / wrist_xf batch mismatch")
+    elif joint_angles.device != d or wrist_xf.device != d or joint_angles.dtype != torch.float32 or wrist_xf.dtype != torch.float32:
+        raise ValueError(f"strided pose views must be fp32 on {d}")
+    if hand_model.shape[0] not in (1, n) and n:
+        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
+    if mirror is not None:
+        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
+        if mirror.shape[0] != n:
+            raise ValueError("mirror batch mismatch")
+    return hand_model, joint_angles, wrist_xf, mirror, n
+
+
+def _fk(lib, h, d, family, hand_model, joint_angles, wrist_xf, mirror, t_scale, ja_stride=22, xf_stride=16, n=None, out=None):
+    """ut_fk with a model handle (HipEngine.fk) or without one (fk_stateless)."""
+    hand_model, joint_angles, wrist_xf, mirror, n = _fk_args(d, hand_model, joint_angles, wrist_xf, mirror, n)
+    if out is None:
+        out = torch.empty(n, arch.N_LANDMARKS, 3, dtype=torch.float32, device=d)
+    _check_rc(lib, h, lib.ut_fk(h, _ptr(hand_model), hand_model.shape[0], _ptr(joint_angles), ja_stride, _ptr(wrist_xf),
+                                xf_stride, _ptr(mirror), ctypes.c_float(t_scale), n, _ptr(out), _stream(d)), "ut_fk", family)
+    return out
+
+
 def fk_stateless(hand_model: torch.Tensor, joint_angles: torch.Tensor, wrist_xf: torch.Tensor,
                  mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0) -> torch.Tensor:
     """ut_fk without a model handle (the FK kernel needs no network weights).  All tensors on one HIP device."""
-    lib = load_library()
-    d = joint_angles.device
-    if d.type != "cuda":
-        raise NativeLibraryError("fk_stateless needs tensors on a HIP device (no CPU fallback)")
-    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
-    joint_angles = _need(joint_angles, torch.float32, d, "joint_angles").reshape(-1, 22)
-    wrist_xf = _need(wrist_xf, torch.float32, d, "wrist_xf").reshape(-1, 16)
-    n = joint_angles.shape[0]
-    if mirror is not None:
-        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
-    out = torch.empty(n, arch.N_LANDMARKS, 3, dtype=torch.float32, device=d)
+    d = _hip_device(joint_angles, "fk_stateless")
     with torch.cuda.device(d):
-        rc = lib.ut_fk(None, _ptr(hand_model), hand_model.shape[0], _ptr(joint_angles), 22, _ptr(wrist_xf), 16,
-                       _ptr(mirror), ctypes.c_float(t_scale), n, _ptr(out), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_fk failed ({rc}): {lib.ut_last_error(None).decode()}")
-    return out
+        return _fk(load_library(), None, d, "stateless", hand_model, joint_angles, wrist_xf, mirror, t_scale)
 
 
 class Mesh:
@@ -264,17 +281,13 @@ class Mesh:
         h = ctypes.c_void_p()
         rc = self.lib.ut_mesh_create(v.ctypes.data, v.shape[0], t.ctypes.data, t.shape[0], w.ctypes.data, self.device.index,
                                      ctypes.byref(h))
-        if rc != 0:
-            msg = f"ut_mesh_create failed ({rc}): {self.lib.ut_last_error(None).decode()}"
-            raise (ValueError if rc in (-1, -4) else RuntimeError)(msg)
+        _check_rc(self.lib, None, rc, "ut_mesh_create", "mesh")
         self._h = h
         self.n_vertices, self.n_triangles = v.shape[0], t.shape[0]
 
     def counts(self) -> Tuple[int, int]:
         nv, nt = ctypes.c_int(), ctypes.c_int()
-        rc = self.lib.ut_mesh_counts(self._h, ctypes.byref(nv), ctypes.byref(nt))
-        if rc != 0:
-            raise RuntimeError(f"ut_mesh_counts failed ({rc}): {self.lib.ut_last_error(None).decode()}")
+        _check_rc(self.lib, None, self.lib.ut_mesh_counts(self._h, ctypes.byref(nv), ctypes.byref(nt)), "ut_mesh_counts")
         return nv.value, nt.value
 
     def close(self):
@@ -300,52 +313,21 @@ def skin_mesh(mesh: Mesh, hand_model: torch.Tensor, joint_angles: torch.Tensor, 
     lib, d = mesh.lib, mesh.device
     if mesh._h is None:
         raise ValueError("the Mesh has been closed")
-    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
-    if n is None:
-        joint_angles = _need(joint_angles, torch.float32, d, "joint_angles").reshape(-1, 22)
-        wrist_xf = _need(wrist_xf, torch.float32, d, "wrist_xf").reshape(-1, 16)
-        n = joint_angles.shape[0]
-        if wrist_xf.shape[0] != n:
-            raise ValueError("joint_angles / wrist_xf batch mismatch")
-    elif joint_angles.device != d or wrist_xf.device != d or joint_angles.dtype != torch.float32 or wrist_xf.dtype != torch.float32:
-        raise ValueError(f"strided pose views must be fp32 on {d}")
-    if hand_model.shape[0] not in (1, n) and n:
-        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
-    if mirror is not None:
-        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
-        if mirror.shape[0] != n:
-            raise ValueError("mirror batch mismatch")
+    hand_model, joint_angles, wrist_xf, mirror, n = _fk_args(d, hand_model, joint_angles, wrist_xf, mirror, n)
     shape = (n, mesh.n_vertices, 3)
-
-    def buf(t, name):
-        if t is None:
-            return torch.empty(shape, dtype=torch.float32, device=d)
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != d or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous fp32 {shape} tensor on {d}")
-        return t
-    out = buf(out, "out")
+    out = _out(out, shape, torch.float32, d, "out")
     if normals or out_normals is not None:
-        out_normals = buf(out_normals, "out_normals")
+        out_normals = _out(out_normals, shape, torch.float32, d, "out_normals")
     h = engine._h if engine is not None else None
     with torch.cuda.device(d):
         rc = lib.ut_skin_mesh(h, mesh._h, _ptr(hand_model), hand_model.shape[0], _ptr(joint_angles), ja_stride, _ptr(wrist_xf),
                               xf_stride, _ptr(mirror), ctypes.c_float(t_scale), n, _ptr(out), _ptr(out_normals), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_skin_mesh failed ({rc}): {lib.ut_last_error(h).decode()}")
+    _check_rc(lib, h, rc, "ut_skin_mesh")
     return (out, out_normals) if out_normals is not None else out
 
 
 UT_CAMERA_FISHEYE62, UT_CAMERA_PINHOLE = 0, 1
 RENDER_MAX_VERTICES = 2368
-
-
-def _raise_entry_error(lib, h, rc: int, what: str):
-    msg = lib.ut_last_error(h).decode()
-    if rc == -1 and "index check:" in msg:
-        raise IndexError(msg)
-    if rc in (-1, -4):
-        raise ValueError(f"{what} failed ({rc}): {msg}")
-    raise RuntimeError(f"{what} failed ({rc}): {msg}")
 
 
 def project_points(points: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, width: int, height: int,
@@ -375,21 +357,15 @@ def project_points(points: torch.Tensor, cam_rows: torch.Tensor, table: torch.Te
     if cam_rows.dim() != 2 or cam_rows.shape[0] != n:
         raise ValueError(f"cam_rows must be [{n},V], got {tuple(cam_rows.shape)}")
     v = cam_rows.shape[1]
-    if out is None:
-        out = (torch.empty(n, v, n_points, 2, dtype=torch.float64, device=d),
-               torch.empty(n, v, n_points, dtype=torch.float64, device=d),
-               torch.empty(n, v, n_points, dtype=torch.uint8, device=d))
-    window, eye_z, flags = out
-    for t, shape, dt in ((window, (n, v, n_points, 2), torch.float64), (eye_z, (n, v, n_points), torch.float64),
-                         (flags, (n, v, n_points), torch.uint8)):
-        if tuple(t.shape) != shape or t.dtype != dt or t.device != d or not t.is_contiguous():
-            raise ValueError(f"out must hold contiguous {dt} {shape} on {d}")
+    window, eye_z, flags = out if out is not None else (None, None, None)
+    window = _out(window, (n, v, n_points, 2), torch.float64, d, "out[0]")
+    eye_z = _out(eye_z, (n, v, n_points), torch.float64, d, "out[1]")
+    flags = _out(flags, (n, v, n_points), torch.uint8, d, "out[2]")
     h = engine._h if engine is not None else None
     with torch.cuda.device(d):
         rc = lib.ut_project_points(h, _ptr(points), point_stride, n_points, _ptr(cam_rows), v, _ptr(table), table.shape[0], kind,
                                    n, int(width), int(height), _ptr(window), _ptr(eye_z), _ptr(flags), _stream(d))
-    if rc != 0:
-        _raise_entry_error(lib, h, rc, "ut_project_points")
+    _check_rc(lib, h, rc, "ut_project_points", "points")
     return window, eye_z, flags
 
 
@@ -414,22 +390,31 @@ def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, s
     n_crops = crop_params.shape[0]
     shape = (n_crops, crop_size, crop_size)
 
-    def buf(t, dtype, fill, name):
+    def buf(t, dtype, fill, name):      # True: allocate with the background value; False / None: leave the output out
         if t is False or t is None:
             return None
-        if t is True:
-            return torch.full(shape, fill, dtype=dtype, device=d)
-        if tuple(t.shape) != shape or t.dtype != dtype or t.device != d or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {d}")
-        return t
+        return _out(None if t is True else t, shape, dtype, d, name, fill)
     depth, tri, shade = buf(depth, torch.float32, float("inf"), "depth"), buf(tri, torch.int32, -1, "tri"), buf(shade, torch.uint8, 0, "shade")
     h = engine._h if engine is not None else None
     with torch.cuda.device(d):
         rc = lib.ut_render_mesh(h, mesh._h, _ptr(vertices), _ptr(crop_params), n_crops, _ptr(sample_range), n, crop_size,
                                 _ptr(depth), _ptr(tri), _ptr(shade), _stream(d))
-    if rc != 0:
-        _raise_entry_error(lib, h, rc, "ut_render_mesh")
+    _check_rc(lib, h, rc, "ut_render_mesh", "points")
     return depth, tri, shade
+
+
+def _crop_outputs(out, n: int, v: int, d, fill=None, landmarks: bool = False) -> Dict[str, torch.Tensor]:
+    """The outputs of the two crop-camera entries for n hands x v view slots.  out None: fresh tensors (the camera rows
+    filled with `fill` if one is given).  Otherwise the caller's tensors under the same keys, written in place and never
+    pre-filled; each is checked for dtype, device, contiguity and its element count for n rows, so leading-row views of
+    staging buffers laid out [n,V,9] / [n,V,16] pass."""
+    spec = {"crop_params": ((n, v, 24), torch.float64, fill), "intrinsics": ((n, v, 3, 3), torch.float32, fill),
+            "extrinsics": ((n, v, 4, 4), torch.float32, fill), "cam_index": ((n, v), torch.int32, None),
+            "n_views": ((n,), torch.int32, None), "status": ((n,), torch.int32, None)}
+    if landmarks:
+        spec["landmarks"] = ((n, arch.N_LANDMARKS, 3), torch.float32, None)
+    return {k: _out(None if out is None else out[k], shape, dtype, d, k, fill_k, flat=True)
+            for k, (shape, dtype, fill_k) in spec.items()}
 
 
 def gen_crop_cameras(cam_params: torch.Tensor, camera_angles: torch.Tensor, hand_model: torch.Tensor,
@@ -437,14 +422,14 @@ def gen_crop_cameras(cam_params: torch.Tensor, camera_angles: torch.Tensor, hand
                      frame_idx: torch.Tensor, hand_idx: torch.Tensor, n_cams: int, src_wh: Tuple[int, int],
                      max_views: int = 2, min_vis: int = 19, crop_size: int = arch.CROP,
                      focal_multiplier: float = 0.8, check_indices: bool = True,
-                     want_landmarks: bool = False) -> Dict[str, torch.Tensor]:
+                     want_landmarks: bool = False, *, out: Optional[Dict[str, torch.Tensor]] = None
+                     ) -> Dict[str, torch.Tensor]:
     """ut_gen_crop_cameras: crop cameras of n (frame, hand) label poses in one launch, padded to max_views.
     Returns crop_params [n,V,24] f64, intrinsics [n,V,3,3], extrinsics [n,V,4,4], cam_index [n,V] i32,
-    n_views [n] i32, status [n] i32.  All tensors on one HIP device; no CPU fallback."""
+    n_views [n] i32, status [n] i32 (and landmarks [n,21,3] with want_landmarks).  out: preallocated tensors under these
+    keys to write into (see _crop_outputs).  All tensors on one HIP device; no CPU fallback."""
     lib = load_library()
-    d = joint_angles.device
-    if d.type != "cuda":
-        raise NativeLibraryError("gen_crop_cameras needs tensors on a HIP device (no CPU fallback)")
+    d = _hip_device(joint_angles, "gen_crop_cameras")
     cam_params = _need(cam_params, torch.float64, d, "cam_params").reshape(-1, 32)
     camera_angles = _need(camera_angles, torch.float64, d, "camera_angles").reshape(-1)
     hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
@@ -463,14 +448,7 @@ def gen_crop_cameras(cam_params: torch.Tensor, camera_angles: torch.Tensor, hand
     # (reads frame_idx back: pass check_indices=False when the same index tensor was validated before)
     if check_indices and n and (int(frame_idx.max()) + 1) * n_cams > cam_params.shape[0]:
         raise ValueError("gen_crop_cameras: frame_idx points past cam_params")
-    out = {"crop_params": torch.zeros(n, max_views, 24, dtype=torch.float64, device=d),
-           "intrinsics": torch.zeros(n, max_views, 3, 3, dtype=torch.float32, device=d),
-           "extrinsics": torch.zeros(n, max_views, 4, 4, dtype=torch.float32, device=d),
-           "cam_index": torch.empty(n, max_views, dtype=torch.int32, device=d),
-           "n_views": torch.empty(n, dtype=torch.int32, device=d),
-           "status": torch.empty(n, dtype=torch.int32, device=d)}
-    if want_landmarks:
-        out["landmarks"] = torch.empty(n, arch.N_LANDMARKS, 3, dtype=torch.float32, device=d)
+    out = _crop_outputs(out, n, max_views, d, fill=0, landmarks=want_landmarks)      # unused view slots stay zero
     with torch.cuda.device(d):
         rc = lib.ut_gen_crop_cameras(None, _ptr(cam_params), _ptr(camera_angles), _ptr(hand_model), _ptr(joint_limits),
                                      hand_model.shape[0], _ptr(joint_angles), _ptr(wrist_xf), _ptr(frame_idx),
@@ -478,24 +456,22 @@ def gen_crop_cameras(cam_params: torch.Tensor, camera_angles: torch.Tensor, hand
                                      crop_size, ctypes.c_double(focal_multiplier), _ptr(out["crop_params"]),
                                      _ptr(out["intrinsics"]), _ptr(out["extrinsics"]), _ptr(out["cam_index"]),
                                      _ptr(out["n_views"]), _ptr(out["status"]), _ptr(out.get("landmarks")), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_gen_crop_cameras failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_gen_crop_cameras")
     return out
 
 
 def gen_crop_cameras_from_window_points(cam_params: torch.Tensor, keypoints: torch.Tensor, src_row: torch.Tensor,
                                         hand_idx: torch.Tensor, crop_size: int = arch.CROP,
-                                        focal_multiplier: float = 0.8, check_indices: bool = True
-                                        ) -> Dict[str, torch.Tensor]:
+                                        focal_multiplier: float = 0.8, check_indices: bool = True, *,
+                                        out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """ut_gen_crop_cameras_from_window_points: crop cameras of n hand candidates placed from 21 window keypoints per
     view (lib/tracker/tracker.py:111-219), one launch.  cam_params [R,32] f64, keypoints [n,V,21,2] (window px),
     src_row [n,V] (row of cam_params, -1 = not seen in that view), hand_idx [n].  Returns crop_params [n,V,24] f64,
     intrinsics [n,V,3,3], extrinsics [n,V,4,4], cam_index [n,V] i32 (the src_row of each filled slot, -1 after),
-    n_views [n] i32, status [n] i32.  All tensors on one HIP device; no CPU fallback."""
+    n_views [n] i32, status [n] i32.  out: preallocated tensors under these keys to write into (see _crop_outputs).  All
+    tensors on one HIP device; no CPU fallback."""
     lib = load_library()
-    d = keypoints.device
-    if d.type != "cuda":
-        raise NativeLibraryError("gen_crop_cameras_from_window_points needs tensors on a HIP device (no CPU fallback)")
+    d = _hip_device(keypoints, "gen_crop_cameras_from_window_points")
     if keypoints.dim() != 4 or tuple(keypoints.shape[2:]) != (arch.N_LANDMARKS, 2):
         raise ValueError("keypoints must be [n, views, 21, 2]")
     n, v = keypoints.shape[:2]
@@ -512,19 +488,13 @@ def gen_crop_cameras_from_window_points(cam_params: torch.Tensor, keypoints: tor
             raise ValueError("gen_crop_cameras_from_window_points: src_row points past cam_params")
         if bool(((hand_idx != 0) & (hand_idx != 1)).any()):
             raise ValueError("gen_crop_cameras_from_window_points: hand_idx must be 0 or 1")
-    out = {"crop_params": torch.empty(n, v, 24, dtype=torch.float64, device=d),
-           "intrinsics": torch.empty(n, v, 3, 3, dtype=torch.float32, device=d),
-           "extrinsics": torch.empty(n, v, 4, 4, dtype=torch.float32, device=d),
-           "cam_index": torch.empty(n, v, dtype=torch.int32, device=d),
-           "n_views": torch.empty(n, dtype=torch.int32, device=d),
-           "status": torch.empty(n, dtype=torch.int32, device=d)}
+    out = _crop_outputs(out, n, v, d)
     with torch.cuda.device(d):
         rc = lib.ut_gen_crop_cameras_from_window_points(
             None, _ptr(cam_params), cam_params.shape[0], _ptr(keypoints), _ptr(src_row), _ptr(hand_idx), n, v,
             crop_size, ctypes.c_double(focal_multiplier), _ptr(out["crop_params"]), _ptr(out["intrinsics"]),
             _ptr(out["extrinsics"]), _ptr(out["cam_index"]), _ptr(out["n_views"]), _ptr(out["status"]), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_gen_crop_cameras_from_window_points failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_gen_crop_cameras_from_window_points")
     return out
 
 
@@ -534,9 +504,7 @@ def gen_crop_matrices(orig_extrinsics: torch.Tensor, orig_intrinsics: torch.Tens
     """ut_gen_crop_matrices.  orig_extrinsics [F,V,4,4], orig_intrinsics [F,V,3,3], crop_points [F,P,3], hand_idx [F]
     -> extrinsics_xf [F,V,4,4], new_intrinsics [F,V,3,3], resample_xf [F,V,4,4], status [F,V] (i32)."""
     lib = load_library()
-    d = orig_extrinsics.device
-    if d.type != "cuda":
-        raise NativeLibraryError("gen_crop_matrices needs tensors on a HIP device (no CPU fallback)")
+    d = _hip_device(orig_extrinsics, "gen_crop_matrices")
     if orig_extrinsics.dim() != 4 or tuple(orig_extrinsics.shape[2:]) != (4, 4):
         raise ValueError("orig_extrinsics must be [frames, views, 4, 4]")
     f, v = orig_extrinsics.shape[:2]
@@ -556,8 +524,7 @@ def gen_crop_matrices(orig_extrinsics: torch.Tensor, orig_intrinsics: torch.Tens
         rc = lib.ut_gen_crop_matrices(None, _ptr(ext), _ptr(intr), _ptr(pts), _ptr(hand), f, v, pts.shape[1], crop_size,
                                       ctypes.c_double(focal_multiplier), _ptr(out["extrinsics_xf"]),
                                       _ptr(out["new_intrinsics"]), _ptr(out["resample_xf"]), _ptr(out["status"]), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_gen_crop_matrices failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_gen_crop_matrices")
     return out
 
 
@@ -565,9 +532,7 @@ def resample_homography(src: torch.Tensor, resample_xf: torch.Tensor, out_hw: Tu
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ut_resample_homography.  src [n,H,W] u8 or f32, resample_xf [n,4,4] f32 -> [n,h,w] f32 in [0,1]."""
     lib = load_library()
-    d = src.device
-    if d.type != "cuda":
-        raise NativeLibraryError("resample_homography needs tensors on a HIP device (no CPU fallback)")
+    d = _hip_device(src, "resample_homography")
     if src.dim() != 3 or src.dtype not in (torch.uint8, torch.float32):
         raise ValueError("src must be [n,H,W] uint8 or float32")
     n = src.shape[0]
@@ -575,15 +540,11 @@ def resample_homography(src: torch.Tensor, resample_xf: torch.Tensor, out_hw: Tu
     if xf.shape[0] != n:
         raise ValueError("resample_xf must hold one 4x4 matrix per source image")
     src = src.contiguous()
-    if out is None:
-        out = torch.empty(n, out_hw[0], out_hw[1], device=d)
-    elif tuple(out.shape) != (n, out_hw[0], out_hw[1]) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != d:
-        raise ValueError("out must be a contiguous float32 [n,h,w] tensor on the source's device")
+    out = _out(out, (n, out_hw[0], out_hw[1]), torch.float32, d, "out")
     with torch.cuda.device(d):
         rc = lib.ut_resample_homography(None, _ptr(src), int(src.dtype == torch.float32), n, src.shape[1], src.shape[2],
                                         _ptr(xf), out_hw[0], out_hw[1], _ptr(out), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_resample_homography failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_resample_homography")
     return out
 
 
@@ -591,9 +552,7 @@ def keypoint_metrics(gt: torch.Tensor, tracked: torch.Tensor, valid: torch.Tenso
     """ut_keypoint_metrics.  gt, tracked [hands, frames, 21, 3] f32, valid [hands, frames] bool/u8 on one HIP device ->
     err f64 [hands, frames], acc / gt_acc f64 [hands, frames-2], valid_acc bool [hands, frames-2]."""
     lib = load_library()
-    d = gt.device
-    if d.type != "cuda":
-        raise NativeLibraryError("keypoint_metrics needs tensors on a HIP device (no CPU fallback)")
+    d = _hip_device(gt, "keypoint_metrics")
     if gt.dim() != 4 or tuple(gt.shape[2:]) != (arch.N_LANDMARKS, 3) or gt.shape != tracked.shape:
         raise ValueError("gt and tracked must both be [hands, frames, 21, 3]")
     h, t = gt.shape[:2]
@@ -607,8 +566,7 @@ def keypoint_metrics(gt: torch.Tensor, tracked: torch.Tensor, valid: torch.Tenso
     with torch.cuda.device(d):
         rc = lib.ut_keypoint_metrics(None, _ptr(g), _ptr(p), _ptr(v), h, t, _ptr(out["err"]), _ptr(out["acc"]),
                                      _ptr(out["gt_acc"]), _ptr(out["valid_acc"]), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_keypoint_metrics failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_keypoint_metrics")
     out["valid_acc"] = out["valid_acc"].bool()
     return out
 
@@ -617,9 +575,7 @@ def warp_map(cam_params: torch.Tensor, crop_params: torch.Tensor, src_index: tor
     """ut_warp_map: the fp32 coordinate maps [n_crops,96,96,2] (x, y) the resampler samples with (what the reference hands to
     cv2.remap, lib/tracker/tracker.py:69-85)."""
     lib = load_library()
-    d = cam_params.device
-    if d.type != "cuda":
-        raise NativeLibraryError("warp_map needs tensors on a HIP device (no CPU fallback)")
+    d = _hip_device(cam_params, "warp_map")
     cam, crop = _need(cam_params, torch.float64, d, "cam_params"), _need(crop_params, torch.float64, d, "crop_params")
     idx = _need(src_index, torch.int32, d, "src_index")
     n = crop.shape[0]
@@ -628,8 +584,7 @@ def warp_map(cam_params: torch.Tensor, crop_params: torch.Tensor, src_index: tor
     out = torch.empty(n, arch.CROP, arch.CROP, 2, device=d)
     with torch.cuda.device(d):
         rc = lib.ut_warp_map(_ptr(cam), _ptr(crop), _ptr(idx), int(n_src_images), n, _ptr(out), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"ut_warp_map failed ({rc}): {lib.ut_last_error(None).decode()}")
+    _check_rc(lib, None, rc, "ut_warp_map")
     return out
 
 
@@ -648,8 +603,7 @@ class HipEngine:
         blob = state_dict_to_blob(state_dict)
         h = ctypes.c_void_p()
         rc = self.lib.ut_create(self.device.index, blob.ctypes.data_as(ctypes.c_void_p), blob.size, ctypes.byref(h))
-        if rc != 0:
-            raise RuntimeError(f"ut_create failed ({rc}): {self.lib.ut_last_error(None).decode()}")
+        _check_rc(self.lib, None, rc, "ut_create")
         self._h = h
         self.deferred_checks = False      # mirrors of the handle's modes (the C ABI has setters only)
         self.latency_mode = False
@@ -666,17 +620,8 @@ class HipEngine:
         except Exception:
             pass
 
-    def _check(self, rc: int, what: str):
-        if rc < 0:
-            msg = self.lib.ut_last_error(self._h).decode()
-            if rc == -4:
-                raise AssertionError(msg)      # the reference asserts here (umetrack_model.py:224-229)
-            if rc == -1 and "index check:" in msg:
-                raise IndexError(msg)          # the reference's tensor indexing raises IndexError on these
-            if rc == -1 and "range check:" in msg:
-                raise FloatingPointError(msg)  # split-fp16 backbone: an infinity / a NaN among a layer's input activations
-            raise RuntimeError(f"{what} failed ({rc}): {msg}")
-        return rc
+    def _check(self, rc: int, what: str) -> int:
+        return _check_rc(self.lib, self._h, rc, what, "engine")
 
     def set_index_checks(self, deferred: bool):
         """Default: every call that takes index tensors reads the device-side verdict back (one stream sync) and
@@ -791,9 +736,8 @@ class HipEngine:
     def set_backbone_chunk(self, crops: int):
         self._check(self.lib.ut_set_backbone_chunk(self._h, crops), "ut_set_backbone_chunk")
 
-    def warp_crops(self, src_u8: torch.Tensor, cam_params: torch.Tensor, crop_params: torch.Tensor,
-                   src_index: torch.Tensor, mode: int = UT_REMAP_CV2_FIXED,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _warp(self, entry: str, out_shape, src_u8, cam_params, crop_params, src_index, mode, out):
+        """ut_warp_crops / ut_warp_backbone: the same arguments, another output per crop."""
         d = self.device
         src_u8 = _need(src_u8, torch.uint8, d, "src")
         if src_u8.dim() != 3:
@@ -805,32 +749,23 @@ class HipEngine:
         if cam_params.shape != (src_u8.shape[0], 32) or crop_params.shape != (n, 24) or src_index.shape != (n,):
             raise ValueError("bad cam_params / crop_params / src_index shape")
         if out is None:
-            out = torch.empty(n, arch.CROP, arch.CROP, dtype=torch.float32, device=d)
-        self._check(self.lib.ut_warp_crops(self._h, _ptr(src_u8), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2],
-                                           _ptr(cam_params), _ptr(crop_params), _ptr(src_index), n, mode, _ptr(out),
-                                           _stream(d)), "ut_warp_crops")
+            out = torch.empty(n, *out_shape, dtype=torch.float32, device=d)
+        self._check(getattr(self.lib, entry)(self._h, _ptr(src_u8), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2],
+                                             _ptr(cam_params), _ptr(crop_params), _ptr(src_index), n, mode, _ptr(out),
+                                             _stream(d)), entry)
         return out
+
+    def warp_crops(self, src_u8: torch.Tensor, cam_params: torch.Tensor, crop_params: torch.Tensor,
+                   src_index: torch.Tensor, mode: int = UT_REMAP_CV2_FIXED,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._warp("ut_warp_crops", (arch.CROP, arch.CROP), src_u8, cam_params, crop_params, src_index, mode, out)
 
     def warp_backbone(self, src_u8: torch.Tensor, cam_params: torch.Tensor, crop_params: torch.Tensor,
                       src_index: torch.Tensor, mode: int = UT_REMAP_CV2_FIXED,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ut_warp_backbone: resample + backbone with the crops kept in the handle's workspace (u8 in cv2 mode)."""
-        d = self.device
-        src_u8 = _need(src_u8, torch.uint8, d, "src")
-        if src_u8.dim() != 3:
-            raise ValueError("src must be [n_images, H, W] uint8")
-        cam_params = _need(cam_params, torch.float64, d, "cam_params")
-        crop_params = _need(crop_params, torch.float64, d, "crop_params")
-        src_index = _need(src_index, torch.int32, d, "src_index")
-        n = crop_params.shape[0]
-        if cam_params.shape != (src_u8.shape[0], 32) or crop_params.shape != (n, 24) or src_index.shape != (n,):
-            raise ValueError("bad cam_params / crop_params / src_index shape")
-        if out is None:
-            out = torch.empty(n, arch.FEAT_CH, arch.FEAT_HW, arch.FEAT_HW, dtype=torch.float32, device=d)
-        self._check(self.lib.ut_warp_backbone(self._h, _ptr(src_u8), src_u8.shape[0], src_u8.shape[1], src_u8.shape[2],
-                                              _ptr(cam_params), _ptr(crop_params), _ptr(src_index), n, mode, _ptr(out),
-                                              _stream(d)), "ut_warp_backbone")
-        return out
+        return self._warp("ut_warp_backbone", (arch.FEAT_CH, arch.FEAT_HW, arch.FEAT_HW), src_u8, cam_params, crop_params,
+                          src_index, mode, out)
 
     def backbone(self, crops: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         d = self.device
@@ -891,24 +826,8 @@ class HipEngine:
            n: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """hand_model [1|n,321]; joint_angles/wrist_xf either packed [n,22]/[n,4,4] or views into a pose
         record buffer with explicit strides (in floats)."""
-        d = self.device
-        hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
-        if n is None:
-            joint_angles = _need(joint_angles, torch.float32, d, "joint_angles").reshape(-1, 22)
-            wrist_xf = _need(wrist_xf, torch.float32, d, "wrist_xf").reshape(-1, 16)
-            n = joint_angles.shape[0]
-            if wrist_xf.shape[0] != n:
-                raise ValueError("joint_angles / wrist_xf batch mismatch")
-        if mirror is not None:
-            mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
-            if mirror.shape[0] != n:
-                raise ValueError("mirror batch mismatch")
-        if out is None:
-            out = torch.empty(n, arch.N_LANDMARKS, 3, dtype=torch.float32, device=d)
-        self._check(self.lib.ut_fk(self._h, _ptr(hand_model), hand_model.shape[0], _ptr(joint_angles), ja_stride,
-                                   _ptr(wrist_xf), xf_stride, _ptr(mirror), ctypes.c_float(t_scale), n, _ptr(out),
-                                   _stream(d)), "ut_fk")
-        return out
+        return _fk(self.lib, self._h, self.device, "engine", hand_model, joint_angles, wrist_xf, mirror, t_scale, ja_stride,
+                   xf_stride, n, out)
 
     def profile_begin(self):
         self._check(self.lib.ut_profile_begin(self._h, _stream(self.device)), "ut_profile_begin")

@@ -8,7 +8,6 @@ packing of kernel argument rows, dict bookkeeping.  The heavy steps run natively
   * the network                                        -> ut_backbone + ut_fuse_temporal_regress
 """
 import contextlib
-import ctypes
 import logging
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Tuple
@@ -412,7 +411,6 @@ class HandTracker:
         """All hands of the frame through one ut_gen_crop_cameras launch (lib/tracker/tracker.py:222-260): one
         staged upload (camera rows + poses), one launch, one read-back.  The launch also returns the landmarks of
         every pose; they are remembered for landmarks_from_hand_pose (the eval scripts ask for them next)."""
-        import ctypes
         from .hand import device_blob
         dev = torch.device("cuda", torch.cuda.current_device())
         n, nc, v = len(hands), len(cameras), MAX_VIEW_NUM
@@ -443,18 +441,15 @@ class HandTracker:
             self._limits_dev = (lim, lim.float().contiguous().to(dev))
         blob = device_blob(hand_model, dev)
         ti, to = st.t_in, st.t_out
-        lib = _native.load_library()
-        with torch.cuda.device(dev):
-            rc = lib.ut_gen_crop_cameras(
-                None, _native._ptr(ti["cam"]), _native._ptr(ti["angles"]), _native._ptr(blob),
-                _native._ptr(self._limits_dev[1]), 1, _native._ptr(ti["ja"]), _native._ptr(ti["xf"]),
-                _native._ptr(ti["frame"]), _native._ptr(ti["hand"]), n, nc, v, self._min_required_vis_landmarks,
-                int(cameras[0].width), int(cameras[0].height), int(self._input_size[0]),
-                ctypes.c_double(self._hand_ratio_in_crop), _native._ptr(to["crop"]), _native._ptr(to["k"]),
-                _native._ptr(to["ext"]), _native._ptr(to["cam_index"]), _native._ptr(to["n_views"]),
-                _native._ptr(to["status"]), _native._ptr(to["landmarks"]), _native._stream(dev))
-        if rc != 0:
-            raise RuntimeError(f"ut_gen_crop_cameras failed ({rc}): {lib.ut_last_error(None).decode()}")
+        # (the staged frame index is always 0 and the hands come from the caller's dict: no index read-back)
+        _native.gen_crop_cameras(
+            ti["cam"][:nc], ti["angles"][:nc], blob, self._limits_dev[1], ti["ja"][:n], ti["xf"][:n], ti["frame"][:n],
+            ti["hand"][:n], nc, (cameras[0].width, cameras[0].height), max_views=v,
+            min_vis=self._min_required_vis_landmarks, crop_size=int(self._input_size[0]),
+            focal_multiplier=self._hand_ratio_in_crop, check_indices=False, want_landmarks=True,
+            out={"crop_params": to["crop"][:n], "intrinsics": to["k"][:n], "extrinsics": to["ext"][:n],
+                 "cam_index": to["cam_index"][:n], "n_views": to["n_views"][:n], "status": to["status"][:n],
+                 "landmarks": to["landmarks"][:n]})
         st.download()                                                         # one read-back
         o = st.np_out
         crop_cameras: Dict[int, Dict[int, PinholePlaneCameraModel]] = {}
@@ -520,15 +515,12 @@ class HandTracker:
         st.upload()
         ti, to = st.t_in, st.t_out
         n = len(hands)
-        lib = _native.load_library()
-        with torch.cuda.device(dev):
-            rc = lib.ut_gen_crop_cameras_from_window_points(
-                None, _native._ptr(ti["cam"]), 2, _native._ptr(ti["kp"]), _native._ptr(ti["src_row"]),
-                _native._ptr(ti["hand"]), n, v, int(self._input_size[0]), ctypes.c_double(self._hand_ratio_in_crop),
-                _native._ptr(to["crop"]), _native._ptr(to["k"]), _native._ptr(to["ext"]), _native._ptr(to["cam_index"]),
-                _native._ptr(to["n_views"]), _native._ptr(to["status"]), _native._stream(dev))
-        if rc != 0:
-            raise RuntimeError(f"ut_gen_crop_cameras_from_window_points failed ({rc}): {lib.ut_last_error(None).decode()}")
+        # (_window_cropgen_ok vetted the hands and the rows are 0 / 1 / -1; the C entry checks the indices again itself)
+        _native.gen_crop_cameras_from_window_points(
+            ti["cam"], ti["kp"][:n], ti["src_row"][:n], ti["hand"][:n], crop_size=int(self._input_size[0]),
+            focal_multiplier=self._hand_ratio_in_crop, check_indices=False,
+            out={"crop_params": to["crop"][:n], "intrinsics": to["k"][:n], "extrinsics": to["ext"][:n],
+                 "cam_index": to["cam_index"][:n], "n_views": to["n_views"][:n], "status": to["status"][:n]})
         st.download()                                                         # one read-back
         o = st.np_out
         if (o["status"][:n] != 0).any():

@@ -163,6 +163,38 @@ def test_landmarks_output_equals_fk(labels, hand_model):
     assert g["landmarks"].shape == want.shape and torch.equal(g["landmarks"], want)
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_out_buffers_equal_allocation(labels, hand_model, n):
+    """out=: leading-row views of buffers sized for 2 hands (the per-frame tracker's staging layout: intrinsics [2,V,9],
+    extrinsics [2,V,16]) receive, bit for bit, what the call allocates itself, in place; with n = 1 the second hand's rows
+    keep their sentinel: nothing is pre-filled or overrun.  (Both hands of frame 0 fill both view slots, so every element
+    of every output is written.)"""
+    c = pipeline.label_candidates(labels, [0])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    blob = torch.from_numpy(_native.hand_model_blob(
+        hand_model.joint_rotation_axes, hand_model.joint_rest_positions, hand_model.landmark_rest_positions,
+        hand_model.landmark_rest_bone_weights, hand_model.landmark_rest_bone_indices)).reshape(1, 321).to(DEV)
+    args = (t(c["cam_params"]), t(c["camera_angles"]), blob, hand_model.joint_limits.float().to(DEV), t(c["joint_angles"][:n]),
+            t(c["wrist_xf"][:n]), t(c["frame_idx"][:n]), t(c["hand_idx"][:n]), c["n_cams"], c["src_wh"])
+    want = _native.gen_crop_cameras(*args, want_landmarks=True)
+    assert want["n_views"].tolist() == [2] * n and want["status"].tolist() == [0] * n
+    f32, i32 = torch.float32, torch.int32
+    bufs = {k: torch.full((2,) + tail, 7, dtype=dt, device=DEV)
+            for k, tail, dt in (("crop_params", (2, 24), torch.float64), ("intrinsics", (2, 9), f32), ("extrinsics", (2, 16), f32),
+                                ("cam_index", (2,), i32), ("n_views", (), i32), ("status", (), i32), ("landmarks", (21, 3), f32))}
+    got = _native.gen_crop_cameras(*args, want_landmarks=True, check_indices=False, out={k: b[:n] for k, b in bufs.items()})
+    torch.cuda.synchronize()
+    assert sorted(got) == sorted(want)
+    for k, b in bufs.items():
+        assert got[k].data_ptr() == b.data_ptr(), k
+        assert torch.equal(got[k].reshape(want[k].shape), want[k]), k
+        assert bool((b[n:] == 7).all()), k
+    with pytest.raises(ValueError):      # a view of the wrong element count
+        _native.gen_crop_cameras(*args, want_landmarks=True, out={k: b[: n - 1] for k, b in bufs.items()})
+    with pytest.raises(ValueError):      # the wrong dtype
+        _native.gen_crop_cameras(*args, want_landmarks=True, out={k: b[:n].double() for k, b in bufs.items()})
+
+
 def test_argument_checks(labels, hand_model):
     c = pipeline.label_candidates(labels, [0])
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)

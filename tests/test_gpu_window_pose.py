@@ -235,6 +235,37 @@ def test_hot_path_on_a_keypoint_plan_matches_the_oracle(labels, conv):
     assert np.abs(rec[:, 60:].reshape(-1, 21, 3) - ref["keypoints_mm"]).max() < KEYPOINT_TOL_MM
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_out_buffers_equal_allocation(cases, n):
+    """out=: leading-row views of buffers sized for 2 hands (the per-frame tracker's staging layout: intrinsics [2,V,9],
+    extrinsics [2,V,16]) receive, bit for bit, what the call allocates itself, in place; with n = 1 the second hand's rows
+    keep their sentinel: nothing is pre-filled or overrun.  (A case with both hands in both views: every element of every
+    output is written.)"""
+    case = next(c for c in cases if c["real"] and all(len(c["expected"].get(h, {})) == 2 for h in (0, 1)))
+    hands = list(case["left"])[:n]
+    cam = torch.from_numpy(np.stack([geometry.pack_camera_model(c) for c in case["cams"]])).to(DEV)
+    kp = torch.from_numpy(np.stack([np.stack([np.asarray(d[h], np.float64)[:, :2] for d in (case["left"], case["right"])])
+                                    for h in hands])).to(DEV)
+    rows = torch.tensor([[0, 1]] * n, dtype=torch.int32, device=DEV)
+    hand = torch.tensor(hands, dtype=torch.int64, device=DEV)
+    want = _native.gen_crop_cameras_from_window_points(cam, kp, rows, hand)
+    assert want["n_views"].tolist() == [2] * n and want["status"].tolist() == [0] * n
+    f32, i32 = torch.float32, torch.int32
+    bufs = {k: torch.full((2,) + tail, 7, dtype=dt, device=DEV)
+            for k, tail, dt in (("crop_params", (2, 24), torch.float64), ("intrinsics", (2, 9), f32), ("extrinsics", (2, 16), f32),
+                                ("cam_index", (2,), i32), ("n_views", (), i32), ("status", (), i32))}
+    got = _native.gen_crop_cameras_from_window_points(cam, kp, rows, hand, check_indices=False,
+                                                      out={k: b[:n] for k, b in bufs.items()})
+    torch.cuda.synchronize()
+    assert sorted(got) == sorted(want)
+    for k, b in bufs.items():
+        assert got[k].data_ptr() == b.data_ptr(), k
+        assert torch.equal(got[k].reshape(want[k].shape), want[k]), k
+        assert bool((b[n:] == 7).all()), k
+    with pytest.raises(ValueError):      # a view of the wrong element count
+        _native.gen_crop_cameras_from_window_points(cam, kp, rows, hand, out={k: b[: n - 1] for k, b in bufs.items()})
+
+
 def test_c_entry_rejects_bad_arguments_and_writes_nothing():
     lib = _native.load_library()
     p = _native._ptr

@@ -27,6 +27,125 @@ def test_library_exports_every_declared_symbol():
     assert lib.ut_weight_blob_floats() == 4_259_410       # no compute, no device needed
 
 
+def test_prototype_table_matches_the_header():
+    """Every ut_* declaration of the header has one entry in the binding's table with as many argtypes as the C
+    declaration has parameters, and load_library() declares exactly the table."""
+    header = open(os.path.join(ROOT, "include", "umetrack_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    declared = {}
+    for name, params in re.findall(r"\b(ut_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", header):
+        assert name not in declared, name
+        params = params.strip()
+        declared[name] = 0 if params in ("", "void") else params.count(",") + 1
+    assert len(declared) == 41
+    assert set(declared) == set(_native.EXPORTS) and len(_native.EXPORTS) == len(set(_native.EXPORTS))
+    assert _native.EXPORTS == tuple(_native._PROTOTYPES)
+    lib = _native.load_library()
+    for name, (restype, argtypes) in _native._PROTOTYPES.items():
+        assert declared[name] == len(argtypes), (name, declared[name], len(argtypes))
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+class _ErrorLib:
+    """A stand-in for the library: every entry returns the chosen rc, ut_last_error the chosen message."""
+
+    def __init__(self, rc, message):
+        self.rc, self.message, self.asked = rc, message, []
+
+    def ut_last_error(self, h):
+        self.asked.append(h)
+        return self.message.encode()
+
+    def __getattr__(self, name):
+        if not name.startswith("ut_"):
+            raise AttributeError(name)
+        return lambda *args: self.rc
+
+
+def _fail_engine(lib, monkeypatch):
+    eng = object.__new__(_native.HipEngine)
+    eng.lib, eng._h = lib, object()
+    try:
+        eng.reset_memory()
+    finally:
+        lib.slot, eng._h = eng._h, None
+
+
+def _fail_points(lib, monkeypatch):
+    import contextlib
+    monkeypatch.setattr(_native, "load_library", lambda: lib)
+    monkeypatch.setattr(_native, "_stream", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "device", contextlib.nullcontext)
+    _native.project_points(torch.zeros(1, 2, 3), torch.zeros(1, 1, dtype=torch.int32), torch.zeros(1, 32, dtype=torch.float64),
+                           636, 480)
+
+
+def _fail_mesh(lib, monkeypatch):
+    monkeypatch.setattr(_native, "load_library", lambda: lib)
+    _native.Mesh(np.zeros((3, 3), np.float32), np.zeros((1, 3), np.int32), np.zeros((3, 17), np.float32), device="cuda:0")
+
+
+def _fail_stateless(lib, monkeypatch):
+    monkeypatch.setattr(_native, "load_library", lambda: lib)
+    monkeypatch.setattr(_native, "state_dict_to_blob", lambda sd: np.zeros(4, np.float32))
+    _native.canonical_backbone_weights({})
+
+
+_PLAIN, _INDEX, _RANGE = "bad argument", "index check: cam_rows[0] outside the table", "range check: layer2 input"
+_ERROR_CASES = [(-1, _PLAIN), (-1, _INDEX), (-1, _RANGE), (-2, "hipErrorUnknown"), (-4, "not supported")]
+# family -> (a call that fails in it, its entry, the exception class of each of _ERROR_CASES)
+_ERROR_FAMILIES = {
+    "HipEngine": (_fail_engine, "ut_reset_memory", [RuntimeError, IndexError, FloatingPointError, RuntimeError, AssertionError]),
+    "project_points": (_fail_points, "ut_project_points", [ValueError, IndexError, ValueError, RuntimeError, ValueError]),
+    "Mesh": (_fail_mesh, "ut_mesh_create", [ValueError, ValueError, ValueError, RuntimeError, ValueError]),
+    "stateless": (_fail_stateless, "ut_canonical_backbone_weights", [RuntimeError] * 5),
+}
+
+
+@pytest.mark.parametrize("case", range(len(_ERROR_CASES)))
+@pytest.mark.parametrize("family", list(_ERROR_FAMILIES))
+def test_error_translation(family, case, monkeypatch):
+    """A negative rc becomes the exception class of the entry's family, with "<entry> failed (<rc>): <ut_last_error>" as
+    its message, read from the handle's error slot when the call has a handle and from the NULL slot otherwise."""
+    fail, entry, classes = _ERROR_FAMILIES[family]
+    rc, message = _ERROR_CASES[case]
+    lib = _ErrorLib(rc, message)
+    with pytest.raises(Exception) as e:
+        fail(lib, monkeypatch)
+    assert type(e.value) is classes[case]
+    assert str(e.value) == f"{entry} failed ({rc}): {message}"
+    assert lib.asked == [getattr(lib, "slot", None)]
+
+
+def test_error_translation_returns_non_negative_codes():
+    lib = _ErrorLib(3, "unused")
+    eng = object.__new__(_native.HipEngine)
+    eng.lib, eng._h = lib, object()
+    assert eng._check(3, "ut_get_memory") == 3 and eng._check(0, "ut_get_memory") == 0 and lib.asked == []
+    eng._h = None
+
+
+def test_output_buffer_helper():
+    cpu = torch.device("cpu")
+    good = torch.zeros(2, 3, 4)
+    assert _native._out(good, (2, 3, 4), torch.float32, cpu, "out") is good
+    assert _native._out(good, (2, 12), torch.float32, cpu, "out", flat=True) is good      # element count only
+    for bad in (torch.zeros(2, 3, 4, dtype=torch.float64), torch.zeros(2, 3, 5), torch.zeros(2, 12),
+                torch.zeros(2, 4, 3).transpose(1, 2), torch.zeros(4, 3, 4)[::2]):
+        with pytest.raises(ValueError, match="out must be a contiguous"):
+            _native._out(bad, (2, 3, 4), torch.float32, cpu, "out")
+    for bad in (torch.zeros(2, 13), torch.zeros(2, 24)[:, ::2], torch.zeros(2, 12, dtype=torch.int32)):
+        with pytest.raises(ValueError):
+            _native._out(bad, (2, 3, 4), torch.float32, cpu, "out", flat=True)
+    with pytest.raises(ValueError):
+        _native._out(good, (2, 3, 4), torch.float32, torch.device("meta"), "out")
+    fresh = _native._out(None, (2, 3), torch.int32, cpu, "out", fill=-1)
+    assert fresh.shape == (2, 3) and fresh.dtype == torch.int32 and bool((fresh == -1).all())
+    assert _native._out(None, (0, 3), torch.float64, cpu, "out").shape == (0, 3)
+
+
 def test_state_dict_blob_is_strict():
     sd = synth.synthetic_state_dict(0)
     blob = _native.state_dict_to_blob(sd)
