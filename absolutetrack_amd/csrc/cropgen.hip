@@ -103,6 +103,12 @@ __device__ inline void fit_crop_camera(const double* c2w0, const float* pts, int
   fit_end(max_ndc, bad, crop_size, focal_multiplier, o);
 }
 
+// K of a square pinhole crop camera, row major 3x3
+__device__ inline void write_k(double focal, double cxy, float* kk) {
+  kk[0] = (float)focal; kk[1] = 0.f; kk[2] = (float)cxy; kk[3] = 0.f; kk[4] = (float)focal; kk[5] = (float)cxy;
+  kk[6] = 0.f; kk[7] = 0.f; kk[8] = 1.f;
+}
+
 // one view's outputs: the crop_params row of ut_warp_crops, K, and the network's world->eye (tracker.py:333-337)
 __device__ inline void write_crop_view(const CropFit& fit, double* cp, float* kk, float* ex) {
   const double focal = fit.focal, cxy = fit.cxy;
@@ -113,8 +119,7 @@ __device__ inline void write_crop_view(const CropFit& fit, double* cp, float* kk
     cp[13 + i] = c2w[4 * i + 3];
   }
   for (int i = 16; i < 24; ++i) cp[i] = 0.0;
-  kk[0] = (float)focal; kk[1] = 0.f; kk[2] = (float)cxy; kk[3] = 0.f; kk[4] = (float)focal; kk[5] = (float)cxy;
-  kk[6] = 0.f; kk[7] = 0.f; kk[8] = 1.f;
+  write_k(focal, cxy, kk);
   // extrinsics = inv(crop camera_to_world) with the translation in metres (tracker.py:335-337)
   double ext[16];
   inv4(c2w, ext);
@@ -137,11 +142,71 @@ __device__ inline void bbox_center(const float* pts, int n_pts, double* center, 
     center[d] = exact ? ((double)lo[d] + (double)hi[d]) / 2.0 : (double)((lo[d] + hi[d]) / 2.0f);
 }
 
+// ---- what the two one-wave-per-candidate kernels below share
+// wave reductions by xor shuffles: min / max / or are exact in any order, and every lane gets the result
+__device__ inline double wave_min(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off));
+  return x;
+}
+
+__device__ inline double wave_max(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off));
+  return x;
+}
+
+__device__ inline int wave_or(int x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x |= __shfl_xor(x, off);
+  return x;
+}
+
+// camera_to_world (row major 4x4) of a cam_params row: rotation at cam + 12, translation at cam + 21
+__device__ inline void cam_row_to_c2w(const double* cam, double* c2w0) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) c2w0[4 * i + j] = cam[12 + 3 * i + j];
+    c2w0[4 * i + 3] = cam[21 + i];
+  }
+  c2w0[12] = 0.0; c2w0[13] = 0.0; c2w0[14] = 0.0; c2w0[15] = 1.0;
+}
+
+// The end of one view, by the lane that owns it: fit the focal length to the view's largest |ndc|, write the view's
+// rows into output slot `slot` and name its source camera there.  g: CropGenArgs or CropGenWindowArgs.  Returns the
+// view's status (1 = "Unable to create crop camera").
+template <class Args>
+__device__ inline int finish_view(const Args& g, const double* w2e, double max_ndc, bool bad, size_t slot, int cam) {
+  CropFit fit;
+  for (int k = 0; k < 16; ++k) fit.w2e[k] = w2e[k];
+  fit_end(max_ndc, bad, g.crop_size, g.focal_multiplier, fit);
+  write_crop_view(fit, g.crop_params + slot * 24, g.intrinsics + slot * 9, g.extrinsics + slot * 16);
+  g.cam_index[slot] = cam;
+  return fit.bad ? 1 : 0;
+}
+
+// The three crop poses of one candidate as skinning_frames_lds reads them (perspective_crop.py:89-133): pose 0 the label
+// angles, pose 1 the neutral pose (perspective_crop.py:19-24), pose 2 the open hand; one model row, one wrist transform
+// (mm already: scale 1), mirrored for right hands.
+struct CropPoses {
+  const float* hm;      // the candidate's packed model
+  const float* ja;      // its 22 label angles
+  const float* lim;     // its [22,2] joint limits
+  const float* xf;      // its wrist transform
+  bool right;
+  float t_scale;
+  __device__ const float* model(int) const { return hm; }
+  __device__ float angle(int i, int q) const {
+    return i == 0 ? ja[q] : i == 1 ? lim[2 * q] * 0.5f + lim[2 * q + 1] * (1.0f - 0.5f) : 0.f;
+  }
+  __device__ const float* wrist(int) const { return xf; }
+  __device__ bool mirrored(int) const { return right; }
+};
+
 }  // namespace
 
 // One WAVE per candidate (one 64-thread workgroup): the pieces of the per-candidate work that are independent run on
 // different lanes and meet in LDS -
-//   (1) joint transforms of the three crop poses: 3 x 20 lanes            (fk.hip phases 1-3, same arithmetic)
+//   (1) joint transforms of the three crop poses: 3 x 20 lanes            (the code of fk.hip phases 1-3, ut_fk.h)
 //   (2) finger chains: 3 x 5 lanes   (3) landmarks: 3 x 21 lanes          -> 63 crop points, fp32
 //   (4) bounding-box centre: 3 lanes (one per axis; min / max are exact)
 //   (5) visible-landmark count: (camera, landmark) pairs on the lanes, three cameras per pass
@@ -168,76 +233,19 @@ __global__ __launch_bounds__(64) void cropgen_kernel(CropGenArgs g) {
   __shared__ int s_nsel;
   __shared__ double s_w2e[CG_MAX_VIEWS][16];
 
-  // ---- (1) joint local transforms of the label pose, the neutral pose and the open pose; wrist frames
-  if (lane < 60) {
-    const int pz = lane / 20, q = lane - pz * 20;
-    float angle;
-    if (pz == 0) angle = g.joint_angles[(size_t)s * 22 + q];
-    else if (pz == 1) {                                   // perspective_crop.py:19-24
-      const float* lim = g.joint_limits + (size_t)(g.n_models == 1 ? 0 : s) * 44;
-      angle = lim[2 * q] * 0.5f + lim[2 * q + 1] * (1.0f - 0.5f);
-    } else angle = 0.f;
-    const M34 l = joint_local(hm + 3 * q, hm + 66 + 3 * q, angle);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) s_local[pz][q][k] = l.m[k];
-  } else if (lane < 63) {
-    const int pz = lane - 60;
-    const float* x = g.wrist_xf + (size_t)s * 16;
-    M34 w;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) w.m[k] = x[k];
-    if (hand == 1) { w.m[0] = -w.m[0]; w.m[4] = -w.m[4]; w.m[8] = -w.m[8]; }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) { s_frame[pz][0][k] = w.m[k]; s_frame[pz][1][k] = w.m[k]; }
-  }
   if (lane < CG_MAX_CAMS) s_vis[lane] = 0;
-  __syncthreads();
-  // ---- (2) finger chains
-  if (lane < 15) {
-    const int pz = lane / 5, f = lane - pz * 5;
-    M34 t;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) t.m[k] = s_frame[pz][0][k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      M34 l;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) l.m[k] = s_local[pz][4 * f + j][k];
-      t = mul34(t, l);
-      if (j >= 1) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) s_frame[pz][2 + 3 * f + (j - 1)][k] = t.m[k];
-      }
-    }
-  }
-  __syncthreads();
-  // ---- (3) linear blend skinning, frames visited in ascending order like the dense reference sum
+  // ---- (1, 2) skinning frames of the label pose, the neutral pose and the open pose (ut_fk.h, the code of ut_fk)
+  const CropPoses poses{hm, g.joint_angles + (size_t)s * 22, g.joint_limits + (size_t)(g.n_models == 1 ? 0 : s) * 44,
+                        g.wrist_xf + (size_t)s * 16, hand == 1, 1.0f};
+  skinning_frames_lds<3>(s_local, s_frame, poses, 3, 0);
+  // ---- (3) linear blend skinning (ut_fk.h)
   if (lane < 63) {
     const int pz = lane / 21, l = lane - pz * 21;
-    const float* lm = hm + 132;
-    const float* wts = hm + 195;
-    const float* idx = hm + 258;
-    const float px = lm[3 * l], py = lm[3 * l + 1], pzz = lm[3 * l + 2];
-    const float w0 = wts[3 * l], w1 = wts[3 * l + 1], w2 = wts[3 * l + 2];
-    const int i0 = (int)idx[3 * l], i1 = (int)idx[3 * l + 1], i2 = (int)idx[3 * l + 2];
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    for (int f = 0; f < 17; ++f) {
-      float w = 0.f;
-      if (w0 != 0.f && i0 == f) w = w0;
-      if (w1 != 0.f && i1 == f) w = w1;
-      if (w2 != 0.f && i2 == f) w = w2;
-      if (w != 0.f) {
-        const float* t = s_frame[pz][f];
-        const float qx = px * w, qy = py * w, qz = pzz * w;
-        ax += t[0] * qx + t[1] * qy + t[2] * qz + t[3] * w;
-        ay += t[4] * qx + t[5] * qy + t[6] * qz + t[7] * w;
-        az += t[8] * qx + t[9] * qy + t[10] * qz + t[11] * w;
-      }
-    }
-    s_pts[3 * lane] = ax; s_pts[3 * lane + 1] = ay; s_pts[3 * lane + 2] = az;
+    float* p = s_pts + 3 * lane;
+    blend_landmark(hm, l, s_frame[pz], p);
     if (pz == 0 && g.landmarks) {   // = landmarks_from_hand_pose(hand_model, pose, hand_idx), same FK as ut_fk
       float* o = g.landmarks + (size_t)s * 63 + 3 * l;
-      o[0] = ax; o[1] = ay; o[2] = az;
+      o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
     }
   }
   __syncthreads();
@@ -276,9 +284,8 @@ __global__ __launch_bounds__(64) void cropgen_kernel(CropGenArgs g) {
   if (lane < n_views) {
     const int ci = s_sel[lane];
     const double* cam = g.cam_params + ((size_t)frame * g.n_cams + ci) * 32;
-    const double* rc = cam + 12;     // camera_to_world rotation (row major), translation at cam+21
-    const double* tc = cam + 21;
-    const double c2w0[16] = {rc[0], rc[1], rc[2], tc[0], rc[3], rc[4], rc[5], tc[1], rc[6], rc[7], rc[8], tc[2], 0, 0, 0, 1};
+    double c2w0[16];
+    cam_row_to_c2w(cam, c2w0);
     const double center[3] = {s_center[0], s_center[1], s_center[2]};
     double w2e[16];
     fit_begin(c2w0, center, g.camera_angles[ci], hand == 1, w2e);
@@ -291,30 +298,16 @@ __global__ __launch_bounds__(64) void cropgen_kernel(CropGenArgs g) {
     double m = 0.0;
     bool bad = false;
     if (lane < 63) fit_point(s_w2e[v], s_pts + 3 * lane, m, bad);
-    int badi = bad ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      m = fmax(m, __shfl_xor(m, off));
-      badi |= __shfl_xor(badi, off);
-    }
+    m = wave_max(m);
+    const int badi = wave_or(bad ? 1 : 0);
     if (lane == v) { my_ndc = m; my_bad = badi != 0; }
   }
+  // ---- outputs; an unused slot gets cam_index -1 only
   int my_status = 0;
-  if (lane < n_views) {
-    CropFit fit;
-    for (int k = 0; k < 16; ++k) fit.w2e[k] = s_w2e[lane][k];
-    fit_end(my_ndc, my_bad, g.crop_size, g.focal_multiplier, fit);
-    if (fit.bad) my_status = 1;
-    // ---- outputs
-    const size_t slot = (size_t)s * g.max_views + lane;
-    write_crop_view(fit, g.crop_params + slot * 24, g.intrinsics + slot * 9, g.extrinsics + slot * 16);
-    g.cam_index[(size_t)s * g.max_views + lane] = s_sel[lane];
-  } else if (lane < g.max_views) {
-    g.cam_index[(size_t)s * g.max_views + lane] = -1;
-  }
-  // "Unable to create crop camera" on any selected view
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) my_status |= __shfl_xor(my_status, off);
+  const size_t slot = (size_t)s * g.max_views + lane;
+  if (lane < n_views) my_status = finish_view(g, s_w2e[lane], my_ndc, my_bad, slot, s_sel[lane]);
+  else if (lane < g.max_views) g.cam_index[slot] = -1;
+  my_status = wave_or(my_status);     // "Unable to create crop camera" on any selected view
   if (lane == 0) {
     g.n_views[s] = n_views;
     g.status[s] = my_status;
@@ -333,18 +326,6 @@ __global__ __launch_bounds__(64) void cropgen_kernel(CropGenArgs g) {
 // One wave per candidate: lane v*21+k unprojects keypoint k of view v; the centre and the max-|ndc| reductions are
 // wave min / max (exact in any order); lane v (a valid view) aims and finishes view v.
 constexpr int WP_MAX_VIEWS = 3;   // 3 x 21 (view, keypoint) pairs fill a wave
-
-__device__ inline double wave_min(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off));
-  return x;
-}
-
-__device__ inline double wave_max(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off));
-  return x;
-}
 
 // window px -> world point through a cam_params row (Fisheye62CameraModel.window_to_eye, then eye_to_world)
 __device__ inline void window_to_world_d(const double* cam, const double* w, double* out) {
@@ -397,9 +378,8 @@ __global__ __launch_bounds__(64) void cropgen_window_kernel(CropGenWindowArgs g)
   const bool right = g.hand_idx[s] == 1;
   if (lane < g.max_views && rows[lane] >= 0) {
     const double* cam = g.cam_params + (size_t)rows[lane] * 32;
-    const double* rc = cam + 12;
-    const double* tc = cam + 21;
-    const double c2w0[16] = {rc[0], rc[1], rc[2], tc[0], rc[3], rc[4], rc[5], tc[1], rc[6], rc[7], rc[8], tc[2], 0, 0, 0, 1};
+    double c2w0[16];
+    cam_row_to_c2w(cam, c2w0);
     fit_begin(c2w0, s_center[lane], 0.0, right, s_w2e[lane]);
   }
   __syncthreads();
@@ -411,10 +391,8 @@ __global__ __launch_bounds__(64) void cropgen_window_kernel(CropGenWindowArgs g)
     double m = 0.0;
     bool bad = false;
     if (mine && v_me == v) fit_point(s_w2e[v], pt, m, bad);
-    int badi = bad ? 1 : 0;
     m = wave_max(m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) badi |= __shfl_xor(badi, off);
+    const int badi = wave_or(bad ? 1 : 0);
     if (lane == v) { my_ndc = m; my_bad = badi != 0; }
   }
   // ---- outputs: slots filled front to back in input order
@@ -426,16 +404,9 @@ __global__ __launch_bounds__(64) void cropgen_window_kernel(CropGenWindowArgs g)
       if (v < lane) ++slot;
       ++n_views;
     }
-    if (rows[lane] >= 0) {
-      CropFit fit;
-      for (int k = 0; k < 16; ++k) fit.w2e[k] = s_w2e[lane][k];
-      fit_end(my_ndc, my_bad, g.crop_size, g.focal_multiplier, fit);
-      if (fit.bad) my_status = 1;
-      const size_t o = (size_t)s * g.max_views + slot;
-      write_crop_view(fit, g.crop_params + o * 24, g.intrinsics + o * 9, g.extrinsics + o * 16);
-      g.cam_index[o] = rows[lane];
-    }
-    if (lane >= n_views) {                                       // unused slots: -1 and zeros, like cropgen_kernel
+    if (rows[lane] >= 0)
+      my_status = finish_view(g, s_w2e[lane], my_ndc, my_bad, (size_t)s * g.max_views + slot, rows[lane]);
+    if (lane >= n_views) {                                       // unused slots: -1 and zeroed rows
       const size_t o = (size_t)s * g.max_views + lane;
       g.cam_index[o] = -1;
       for (int i = 0; i < 24; ++i) g.crop_params[o * 24 + i] = 0.0;
@@ -444,8 +415,7 @@ __global__ __launch_bounds__(64) void cropgen_window_kernel(CropGenWindowArgs g)
     }
     if (lane == 0) g.n_views[s] = n_views;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) my_status |= __shfl_xor(my_status, off);
+  my_status = wave_or(my_status);
   if (lane == 0) g.status[s] = my_status;
 }
 
@@ -480,9 +450,7 @@ __global__ __launch_bounds__(64) void cropmat_kernel(CropMatArgs g) {
   double ext[16];
   inv4(fit.c2w, ext);              // new_world_to_eye_xf = inv(camera_new.camera_to_world_xf)  (:203)
   for (int k = 0; k < 16; ++k) g.extrinsics_xf[(size_t)i * 16 + k] = (float)ext[k];
-  float* kn = g.new_intrinsics + (size_t)i * 9;
-  kn[0] = (float)fit.focal; kn[1] = 0.f; kn[2] = (float)fit.cxy; kn[3] = 0.f; kn[4] = (float)fit.focal;
-  kn[5] = (float)fit.cxy; kn[6] = 0.f; kn[7] = 0.f; kn[8] = 1.f;
+  write_k(fit.focal, fit.cxy, g.new_intrinsics + (size_t)i * 9);
   // resample matrix (data_transform.py:57-76)
   const float* ko = g.orig_intrinsics + (size_t)i * 9;
   double k_orig[16] = {0}, k_inv[16] = {0}, w2e0[16], t0[16], t1[16], r[16];

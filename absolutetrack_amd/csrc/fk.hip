@@ -13,8 +13,8 @@ namespace ut {
 // Three phases per block of FK_P poses, all operands through LDS so that no thread indexes a private array
 // dynamically: (1) one thread per (pose, joint) builds the joint's local transform (sin/cos), (2) one thread per
 // (pose, finger) multiplies the chain wrist*L0*L1*L2*L3 and keeps the frames after 2, 3, 4 joints, (3) one thread
-// per (pose, landmark) blends.  Same arithmetic, in the same order, as the one-thread-per-pose
-// skin_landmarks_dev of ut_fk.h (which cropgen.hip still uses inside its own per-candidate thread).
+// per (pose, landmark) blends.  Phases 1, 2 are skinning_frames_lds and phase 3 is blend_landmark of ut_fk.h, which
+// mesh.hip (frames) and cropgen.hip (frames and blend, three crop poses per candidate) call as well.
 constexpr int FK_P = 12;
 
 __global__ __launch_bounds__(256) void fk_kernel(const float* __restrict__ hand_model, int n_models,
@@ -26,38 +26,14 @@ __global__ __launch_bounds__(256) void fk_kernel(const float* __restrict__ hand_
   __shared__ float s_frame[FK_P][17][12];
   const int tid = threadIdx.x;
   const int base = blockIdx.x * FK_P;
-  // ---- phases 1, 2: the skinning frames (ut_fk.h; mesh.hip builds its frames with the same code)
-  skinning_frames_lds<FK_P>(s_local, s_frame, hand_model, n_models, ja, ja_stride, xf, xf_stride, mirror, t_scale, n, base);
-  // ---- phase 3: linear blend skinning, frames visited in ascending order like the dense reference sum
+  const BatchPoses poses{hand_model, n_models, ja, ja_stride, xf, xf_stride, mirror, t_scale};
+  // ---- phases 1, 2: the skinning frames (ut_fk.h; mesh.hip and cropgen.hip build their frames with the same code)
+  skinning_frames_lds<FK_P>(s_local, s_frame, poses, n, base);
+  // ---- phase 3: linear blend skinning (ut_fk.h; cropgen.hip blends its crop points with the same code)
   if (tid < FK_P * 21) {
     const int pl = tid / 21, l = tid - pl * 21;
     const int i = base + pl;
-    if (i < n) {
-      const float* hm = hand_model + (size_t)(n_models == 1 ? 0 : i) * 321;
-      const float* lm = hm + 132;
-      const float* wts = hm + 195;
-      const float* idx = hm + 258;
-      const float px = lm[3 * l], py = lm[3 * l + 1], pz = lm[3 * l + 2];
-      const float w0 = wts[3 * l], w1 = wts[3 * l + 1], w2 = wts[3 * l + 2];
-      const int i0 = (int)idx[3 * l], i1 = (int)idx[3 * l + 1], i2 = (int)idx[3 * l + 2];
-      float ax = 0.f, ay = 0.f, az = 0.f;
-      for (int f = 0; f < 17; ++f) {
-        // dense skinning weight of frame f: the last non-zero entry naming it wins
-        float w = 0.f;
-        if (w0 != 0.f && i0 == f) w = w0;
-        if (w1 != 0.f && i1 == f) w = w1;
-        if (w2 != 0.f && i2 == f) w = w2;
-        if (w != 0.f) {
-          const float* t = s_frame[pl][f];
-          const float qx = px * w, qy = py * w, qz = pz * w;   // (p,1) * w, as the reference scales first
-          ax += t[0] * qx + t[1] * qy + t[2] * qz + t[3] * w;
-          ay += t[4] * qx + t[5] * qy + t[6] * qz + t[7] * w;
-          az += t[8] * qx + t[9] * qy + t[10] * qz + t[11] * w;
-        }
-      }
-      float* o = out + (size_t)i * 63 + 3 * l;
-      o[0] = ax; o[1] = ay; o[2] = az;
-    }
+    if (i < n) blend_landmark(poses.model(i), l, s_frame[pl], out + (size_t)i * 63 + 3 * l);
   }
 }
 

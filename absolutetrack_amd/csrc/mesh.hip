@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void skin_mesh_kernel(const float* __restrict_
   float* s_pos = reinterpret_cast<float*>(s_dyn);
   const int tid = threadIdx.x;
   const int i = blockIdx.x;                      // grid = n poses
-  skinning_frames_lds<1>(s_local, s_frame, hand_model, n_models, ja, ja_stride, xf, xf_stride, mirror, t_scale, n, i);
+  skinning_frames_lds<1>(s_local, s_frame, BatchPoses{hand_model, n_models, ja, ja_stride, xf, xf_stride, mirror, t_scale}, n, i);
   // ---- phase 3: linear blend skinning of the vertices
   for (int v = tid; v < nv; v += 256) {
     const float4 pb = verts[2 * v];

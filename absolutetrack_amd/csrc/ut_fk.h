@@ -1,4 +1,4 @@
-// Device-side forward kinematics + linear blend skinning shared by fk.hip and cropgen.hip.
+// Device-side forward kinematics + linear blend skinning shared by fk.hip, mesh.hip and cropgen.hip.
 // See fk.hip for the reference citations (lib/common/hand_skinning.py:17-209, pytorch3d so3_exp_map).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,26 +51,40 @@ __device__ inline M34 joint_local(const float* axis, const float* rest, float an
 }
 
 
+// The poses of a batch as skinning_frames_lds reads them (fk.hip, mesh.hip): pose i takes its 20 joint angles from
+// ja[i * ja_stride], its wrist transform (rows 0..2, row major) from xf[i * xf_stride] and row i of the packed models
+// (row 0 when there is one model); its translation is multiplied by t_scale and the hand is mirrored where mirror[i] == 1.
+struct BatchPoses {
+  const float* hand_model; int n_models;
+  const float* ja; int ja_stride;
+  const float* xf; int xf_stride;
+  const int64_t* mirror;
+  float t_scale;
+  __device__ const float* model(int i) const { return hand_model + (size_t)(n_models == 1 ? 0 : i) * 321; }
+  __device__ float angle(int i, int q) const { return ja[(size_t)i * ja_stride + q]; }
+  __device__ const float* wrist(int i) const { return xf + (size_t)i * xf_stride; }
+  __device__ bool mirrored(int i) const { return mirror && mirror[i] == 1; }
+};
+
 // The 17 skinning frames of P poses (base .. base + P - 1, those below n) into s_frame, by a workgroup of at least 21 * P
 // threads, operands through LDS so that no thread indexes a private array dynamically: (1) one thread per (pose, joint)
 // builds the joint's local transform (sin/cos) while one per pose writes the wrist frames (slots 0, 1: translation times
-// t_scale, column 0 negated where mirror[i] == 1), (2) one thread per (pose, finger) multiplies the chain wrist*L0*L1*L2*L3
-// and keeps the frames after 2, 3, 4 joints.  Ends on a barrier: every thread of the workgroup must call it, and may read
-// s_frame when it returns.  Shared by fk.hip (landmarks) and mesh.hip (mesh vertices): one arithmetic, one order.
-template <int P>
-__device__ inline void skinning_frames_lds(float (&s_local)[P][20][12], float (&s_frame)[P][17][12],
-                                           const float* __restrict__ hand_model, int n_models,
-                                           const float* __restrict__ ja, int ja_stride, const float* __restrict__ xf,
-                                           int xf_stride, const int64_t* __restrict__ mirror, float t_scale, int n,
-                                           int base) {
+// t_scale, column 0 negated where the pose is mirrored), (2) one thread per (pose, finger) multiplies the chain
+// wrist*L0*L1*L2*L3 and keeps the frames after 2, 3, 4 joints.  Ends on a barrier: every thread of the workgroup must call
+// it, and may read s_frame when it returns.  `poses` says where pose i's model row, angles, wrist, mirror flag and t_scale
+// come from (BatchPoses above; cropgen.hip has its own for the three crop poses of a candidate).  Shared by fk.hip
+// (landmarks), mesh.hip (mesh vertices) and cropgen.hip (crop points): one arithmetic, one order.
+template <int P, class Poses>
+__device__ inline void skinning_frames_lds(float (&s_local)[P][20][12], float (&s_frame)[P][17][12], const Poses& poses,
+                                           int n, int base) {
   const int tid = threadIdx.x;
   // ---- phase 1: joint local transforms (20 per pose) and the wrist frames (slots 0, 1)
   if (tid < P * 20) {
     const int pl = tid / 20, q = tid - pl * 20;
     const int i = base + pl;
     if (i < n) {
-      const float* hm = hand_model + (size_t)(n_models == 1 ? 0 : i) * 321;
-      const M34 l = joint_local(hm + 3 * q, hm + 66 + 3 * q, ja[(size_t)i * ja_stride + q]);
+      const float* hm = poses.model(i);
+      const M34 l = joint_local(hm + 3 * q, hm + 66 + 3 * q, poses.angle(i, q));
 #pragma unroll
       for (int k = 0; k < 12; ++k) s_local[pl][q][k] = l.m[k];
     }
@@ -78,12 +92,12 @@ __device__ inline void skinning_frames_lds(float (&s_local)[P][20][12], float (&
     const int pl = tid - P * 20;
     const int i = base + pl;
     if (i < n) {
-      const float* x = xf + (size_t)i * xf_stride;
+      const float* x = poses.wrist(i);
       M34 w;
 #pragma unroll
       for (int k = 0; k < 12; ++k) w.m[k] = x[k];
-      w.m[3] *= t_scale; w.m[7] *= t_scale; w.m[11] *= t_scale;
-      if (mirror && mirror[i] == 1) { w.m[0] = -w.m[0]; w.m[4] = -w.m[4]; w.m[8] = -w.m[8]; }
+      w.m[3] *= poses.t_scale; w.m[7] *= poses.t_scale; w.m[11] *= poses.t_scale;
+      if (poses.mirrored(i)) { w.m[0] = -w.m[0]; w.m[4] = -w.m[4]; w.m[8] = -w.m[8]; }
 #pragma unroll
       for (int k = 0; k < 12; ++k) { s_frame[pl][0][k] = w.m[k]; s_frame[pl][1][k] = w.m[k]; }
     }
@@ -112,47 +126,33 @@ __device__ inline void skinning_frames_lds(float (&s_local)[P][20][12], float (&
   __syncthreads();
 }
 
-// 21 landmarks [63] of one pose.  hm: packed hand model (321 floats, see include/umetrack_hip.h); a: 22 joint
-// angles; wrist: root-to-world transform.
-__device__ inline void skin_landmarks_dev(const float* __restrict__ hm, const float* __restrict__ a, const M34& wrist,
-                                          float* __restrict__ o) {
-  const float* axes = hm;
-  const float* rest = hm + 66;
+// Landmark l of one pose into o[0..2]: linear blend skinning over the pose's 17 frames (in LDS, from skinning_frames_lds),
+// frames visited in ascending order like the dense reference sum.  hm: packed hand model (321 floats, see
+// include/umetrack_hip.h).
+__device__ inline void blend_landmark(const float* __restrict__ hm, int l, const float (&frames)[17][12],
+                                      float* __restrict__ o) {
   const float* lm = hm + 132;
   const float* wts = hm + 195;
   const float* idx = hm + 258;
-  M34 frames[17];
-  frames[0] = wrist;
-  frames[1] = wrist;
-#pragma unroll
-  for (int f = 0; f < 5; ++f) {
-    M34 t = wrist;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int q = 4 * f + j;
-      t = mul34(t, joint_local(axes + 3 * q, rest + 3 * q, a[q]));
-      if (j >= 1) frames[2 + 3 * f + (j - 1)] = t;
+  const float px = lm[3 * l], py = lm[3 * l + 1], pz = lm[3 * l + 2];
+  const float w0 = wts[3 * l], w1 = wts[3 * l + 1], w2 = wts[3 * l + 2];
+  const int i0 = (int)idx[3 * l], i1 = (int)idx[3 * l + 1], i2 = (int)idx[3 * l + 2];
+  float ax = 0.f, ay = 0.f, az = 0.f;
+  for (int f = 0; f < 17; ++f) {
+    // dense skinning weight of frame f: the last non-zero entry naming it wins
+    float w = 0.f;
+    if (w0 != 0.f && i0 == f) w = w0;
+    if (w1 != 0.f && i1 == f) w = w1;
+    if (w2 != 0.f && i2 == f) w = w2;
+    if (w != 0.f) {
+      const float* t = frames[f];
+      const float qx = px * w, qy = py * w, qz = pz * w;   // (p,1) * w, as the reference scales first
+      ax += t[0] * qx + t[1] * qy + t[2] * qz + t[3] * w;
+      ay += t[4] * qx + t[5] * qy + t[6] * qz + t[7] * w;
+      az += t[8] * qx + t[9] * qy + t[10] * qz + t[11] * w;
     }
   }
-  for (int l = 0; l < 21; ++l) {
-    const float px = lm[3 * l], py = lm[3 * l + 1], pz = lm[3 * l + 2];
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    for (int f = 0; f < 17; ++f) {
-      // dense skinning weight of frame f: the last non-zero entry naming it wins
-      float w = 0.f;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (wts[3 * l + k] != 0.f && (int)idx[3 * l + k] == f) w = wts[3 * l + k];
-      if (w != 0.f) {
-        const M34& t = frames[f];
-        const float qx = px * w, qy = py * w, qz = pz * w;   // (p,1) * w, as the reference scales first
-        ax += t.m[0] * qx + t.m[1] * qy + t.m[2] * qz + t.m[3] * w;
-        ay += t.m[4] * qx + t.m[5] * qy + t.m[6] * qz + t.m[7] * w;
-        az += t.m[8] * qx + t.m[9] * qy + t.m[10] * qz + t.m[11] * w;
-      }
-    }
-    o[3 * l] = ax; o[3 * l + 1] = ay; o[3 * l + 2] = az;
-  }
+  o[0] = ax; o[1] = ay; o[2] = az;
 }
 
 }  // namespace ut

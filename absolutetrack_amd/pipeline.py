@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native, arch, geometry
-from .hand import HandModel, device_mesh
+from .hand import HandModel, device_blob, device_mesh
 from .tracker import (HandTrackerOpts, MAX_VIEW_NUM, SingleHandPose, gen_crop_cameras_from_pose,
                       network_camera_inputs)
 
@@ -156,25 +156,29 @@ def crop_plan_on_device(lab: Dict[str, np.ndarray], hand_model: HandModel, frame
     dev = torch.device(device)
     c = label_candidates(lab, frame_ids, hands)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    blob = torch.from_numpy(_native.hand_model_blob(
-        hand_model.joint_rotation_axes, hand_model.joint_rest_positions, hand_model.landmark_rest_positions,
-        hand_model.landmark_rest_bone_weights, hand_model.landmark_rest_bone_indices)).reshape(1, 321).to(dev)
     cam_params, hand_idx, frame_idx = t(c["cam_params"]), t(c["hand_idx"]), t(c["frame_idx"])
-    g = _native.gen_crop_cameras(cam_params, t(c["camera_angles"]), blob, hand_model.joint_limits.float().to(dev),
-                                 t(c["joint_angles"]), t(c["wrist_xf"]), frame_idx, hand_idx, c["n_cams"], c["src_wh"],
-                                 max_views=MAX_VIEW_NUM, min_vis=opts.min_required_vis_landmarks, crop_size=arch.CROP,
+    g = _native.gen_crop_cameras(cam_params, t(c["camera_angles"]), device_blob(hand_model, dev),
+                                 hand_model.joint_limits.float().to(dev), t(c["joint_angles"]), t(c["wrist_xf"]),
+                                 frame_idx, hand_idx, c["n_cams"], c["src_wh"], max_views=MAX_VIEW_NUM,
+                                 min_vis=opts.min_required_vis_landmarks, crop_size=arch.CROP,
                                  focal_multiplier=opts.hand_ratio_in_crop)
+    return _compact_plan(g, cam_params, hand_idx, frame_idx.long()[:, None] * c["n_cams"] + g["cam_index"].long())
+
+
+def _compact_plan(g: Dict[str, torch.Tensor], cam_params: torch.Tensor, hand_idx: torch.Tensor, src_index: torch.Tensor
+                  ) -> Dict[str, torch.Tensor]:
+    """The padded [n,V] output `g` of a crop-camera launch as a crop plan: the used view slots in row order, the
+    candidates without a view dropped.  src_index [n,V]: the source image of every slot (read where the slot is used).
+    Raises where the reference would ("Unable to create crop camera")."""
     if bool((g["status"] != 0).any()):
         raise ValueError("Unable to create crop camera")
     nv = g["n_views"].long()
     keep = nv > 0
     used = g["cam_index"] >= 0                                           # [n,V], view slots are filled front to back
     ends = torch.cumsum(nv, 0)
-    ranges = torch.stack([ends - nv, ends], 1)[keep]
-    src_index = (frame_idx.long()[:, None] * c["n_cams"] + g["cam_index"].long())[used].int()
-    return {"cam_params": cam_params, "crop_params": g["crop_params"][used], "src_index": src_index,
-            "intrinsics": g["intrinsics"][used], "extrinsics": g["extrinsics"][used], "sample_range": ranges,
-            "hand_idx": hand_idx[keep]}
+    return {"cam_params": cam_params, "crop_params": g["crop_params"][used], "src_index": src_index[used].int(),
+            "intrinsics": g["intrinsics"][used], "extrinsics": g["extrinsics"][used],
+            "sample_range": torch.stack([ends - nv, ends], 1)[keep], "hand_idx": hand_idx[keep]}
 
 
 def crop_plan_from_window_points(cam_params, keypoints, src_row, hand_idx, device,
@@ -191,15 +195,7 @@ def crop_plan_from_window_points(cam_params, keypoints, src_row, hand_idx, devic
     cam_params, hand_idx = t(cam_params).double(), t(hand_idx).long()
     g = _native.gen_crop_cameras_from_window_points(cam_params, t(keypoints), t(src_row), hand_idx, crop_size=arch.CROP,
                                                     focal_multiplier=opts.hand_ratio_in_crop)
-    if bool((g["status"] != 0).any()):
-        raise ValueError("Unable to create crop camera")
-    nv = g["n_views"].long()
-    keep = nv > 0
-    used = g["cam_index"] >= 0                                           # [n,V], view slots are filled front to back
-    ends = torch.cumsum(nv, 0)
-    return {"cam_params": cam_params, "crop_params": g["crop_params"][used], "src_index": g["cam_index"][used],
-            "intrinsics": g["intrinsics"][used], "extrinsics": g["extrinsics"][used],
-            "sample_range": torch.stack([ends - nv, ends], 1)[keep], "hand_idx": hand_idx[keep]}
+    return _compact_plan(g, cam_params, hand_idx, g["cam_index"])
 
 
 def project_keypoints(points: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor, src_wh: Tuple[int, int],
@@ -241,9 +237,7 @@ class DeviceCropPlanner:
         self.cam_params, self.camera_angles = t(c["cam_params"]), t(c["camera_angles"])
         self.joint_angles, self.wrist_xf = t(c["joint_angles"]), t(c["wrist_xf"])
         self.frame_idx, self.hand_idx = t(c["frame_idx"]), t(c["hand_idx"])
-        self.blob = torch.from_numpy(_native.hand_model_blob(
-            hand_model.joint_rotation_axes, hand_model.joint_rest_positions, hand_model.landmark_rest_positions,
-            hand_model.landmark_rest_bone_weights, hand_model.landmark_rest_bone_indices)).reshape(1, 321).to(dev)
+        self.blob = device_blob(hand_model, dev)
         self.limits = hand_model.joint_limits.float().to(dev)
         if int(self.frame_idx.max()) * self.n_cams + self.n_cams > self.cam_params.shape[0]:
             raise ValueError("frame_idx points past cam_params")
@@ -308,9 +302,7 @@ class HotPath:
         self.mode = _native.UT_MODE_KNOWN if known_skeleton else _native.UT_MODE_UNKNOWN
         self.remap_mode = remap_mode
         dev = engine.device
-        self.hand_blob = torch.from_numpy(_native.hand_model_blob(
-            hand_model_mm.joint_rotation_axes, hand_model_mm.joint_rest_positions, hand_model_mm.landmark_rest_positions,
-            hand_model_mm.landmark_rest_bone_weights, hand_model_mm.landmark_rest_bone_indices)).reshape(1, 321).to(dev)
+        self.hand_blob = device_blob(hand_model_mm, dev)
         self.skel = None
         if known_skeleton:   # mm -> m (lib/tracker/tracker.py:361-367)
             self.skel = torch.stack([hand_model_mm.joint_rotation_axes.float(),

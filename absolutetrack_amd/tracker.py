@@ -18,7 +18,7 @@ import torch
 from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
-from .hand import fk_device, render_mesh as _render_mesh
+from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
 
 logger = logging.getLogger(__name__)
@@ -132,11 +132,16 @@ def _visible_counts(cameras: List[CameraModel], landmarks_world: np.ndarray) -> 
     return counts
 
 
-def rank_hand_visibility_in_cameras(cameras, hand_model, hand_pose, hand_idx, min_required_vis_landmarks) -> List[int]:
-    counts = _visible_counts(cameras, landmarks_from_hand_pose(hand_model, hand_pose, hand_idx))
+def _rank_by_visibility(counts: List[int], min_required_vis_landmarks: int) -> List[int]:
+    """The cameras that see enough landmarks, most first; equal counts keep index order (perspective_crop.py:78-86)."""
     keep = [i for i, n in enumerate(counts) if n >= min_required_vis_landmarks]
     keep.sort(reverse=True, key=lambda i: counts[i])
     return keep
+
+
+def rank_hand_visibility_in_cameras(cameras, hand_model, hand_pose, hand_idx, min_required_vis_landmarks) -> List[int]:
+    counts = _visible_counts(cameras, landmarks_from_hand_pose(hand_model, hand_pose, hand_idx))
+    return _rank_by_visibility(counts, min_required_vis_landmarks)
 
 
 def _pose_stack_landmarks(hand_model: HandModel, poses: List[np.ndarray], wrist_xform: np.ndarray, hand_idx: int
@@ -166,9 +171,7 @@ def gen_crop_cameras_from_pose(cameras, camera_angles, hand_model, hand_pose, ha
     (lib/tracker/perspective_crop.py:136-180).  The first 21 crop points are the landmarks of the pose
     itself, so the visibility ranking re-uses them instead of running FK again."""
     crop_points = _get_crop_points_from_hand_pose(hand_model, hand_pose, hand_idx, num_crop_points)
-    counts = _visible_counts(cameras, crop_points[:21])
-    order = [i for i, n in enumerate(counts) if n >= min_required_vis_landmarks]
-    order.sort(reverse=True, key=lambda i: counts[i])
+    order = _rank_by_visibility(_visible_counts(cameras, crop_points[:21]), min_required_vis_landmarks)
     if sort_camera_index:
         order = sorted(order)
     out: Dict[int, PinholePlaneCameraModel] = {}
@@ -229,6 +232,29 @@ def _crop_camera_from_row(row: np.ndarray, k: np.ndarray, ext: np.ndarray, size:
     return cam
 
 
+# What both crop-camera kernels return per candidate, under the keys of their `out=` dict: (key, dtype, shape).
+_CROP_OUT_FIELDS = (("crop_params", np.float64, (MAX_VIEW_NUM, 24)), ("intrinsics", np.float32, (MAX_VIEW_NUM, 9)),
+                    ("extrinsics", np.float32, (MAX_VIEW_NUM, 16)), ("cam_index", np.int32, (MAX_VIEW_NUM,)),
+                    ("n_views", np.int32, ()), ("status", np.int32, ()))
+
+
+def _crop_out_stage_fields(*extra):
+    """_Stage output fields of NUM_HANDS candidates: _CROP_OUT_FIELDS (and `extra`, same form), one row per candidate."""
+    return [(key, dtype, (NUM_HANDS,) + shape) for key, dtype, shape in _CROP_OUT_FIELDS + extra]
+
+
+def _crop_out_dict(stage: "_Stage", n: int) -> Dict[str, torch.Tensor]:
+    """The `out=` dict of a crop-camera launch of n candidates: the first n rows of every staged output field."""
+    return {key: t[:n] for key, t in stage.t_out.items()}
+
+
+def _crop_cameras_from_rows(o: Dict[str, np.ndarray], i: int, size: int) -> Dict[int, PinholePlaneCameraModel]:
+    """{source camera: crop camera} of candidate i from the read-back rows `o` (keys of _CROP_OUT_FIELDS), slot order."""
+    return {int(o["cam_index"][i, k]): _crop_camera_from_row(o["crop_params"][i, k].copy(), o["intrinsics"][i, k].copy(),
+                                                             o["extrinsics"][i, k].copy(), size)
+            for k in range(int(o["n_views"][i]))}
+
+
 # ----------------------------------------------------------------------------- tracker.py
 @dataclass
 class ViewData:
@@ -272,6 +298,56 @@ def _net_inputs(crop_camera: PinholePlaneCameraModel):
 
 
 # ----------------------------------------------------------------------------- per-frame staging
+_TORCH_DTYPE = {np.dtype(k): v for k, v in ((np.uint8, torch.uint8), (np.int32, torch.int32), (np.int64, torch.int64),
+                                            (np.float32, torch.float32), (np.float64, torch.float64))}
+
+
+def _stage_layout(fields):
+    """({name: (byte offset, dtype, shape)}, total bytes) of `fields` = [(name, dtype, shape)] laid out in order, every
+    field starting on a 16-byte boundary."""
+    layout, off = {}, 0
+    for name, dtype, shape in fields:
+        layout[name] = (off, dtype, shape)
+        off += (int(np.prod(shape)) * np.dtype(dtype).itemsize + 15) // 16 * 16
+    return layout, off
+
+
+def _stage_views(buf, layout):
+    """{name: typed view of the field's bytes} over a flat uint8 buffer, a numpy array or a tensor."""
+    views = {}
+    for name, (off, dtype, shape) in layout.items():
+        raw = buf[off: off + int(np.prod(shape)) * np.dtype(dtype).itemsize]
+        views[name] = raw.view(dtype if isinstance(buf, np.ndarray) else _TORCH_DTYPE[np.dtype(dtype)]).reshape(shape)
+    return views
+
+
+_MAX_CAMS = 8       # source cameras the gen_crop_cameras staging holds
+
+
+def _crop_stage_fields():
+    """(inputs, outputs) of gen_crop_cameras' staging."""
+    return ([("cam", np.float64, (_MAX_CAMS, 32)), ("angles", np.float64, (_MAX_CAMS,)), ("ja", np.float32, (NUM_HANDS, 22)),
+             ("xf", np.float32, (NUM_HANDS, 16)), ("frame", np.int32, (NUM_HANDS,)), ("hand", np.int64, (NUM_HANDS,))],
+            _crop_out_stage_fields(("landmarks", np.float32, (21, 3))))
+
+
+def _window_stage_fields():
+    """(inputs, outputs) of the window-keypoint crop cameras' staging."""
+    return ([("cam", np.float64, (2, 32)), ("kp", np.float64, (NUM_HANDS, MAX_VIEW_NUM, 21, 2)),
+             ("src_row", np.int32, (NUM_HANDS, MAX_VIEW_NUM)), ("hand", np.int64, (NUM_HANDS,))], _crop_out_stage_fields())
+
+
+def _frame_stage_fields(hgt: int, wid: int):
+    """(inputs, outputs) of track_frame's staging for source images of hgt x wid; the images come last, so that an
+    upload can stop after the ones in use."""
+    nc, ns = NUM_HANDS * MAX_VIEW_NUM, NUM_HANDS
+    return ([("cam", np.float64, (4, 32)), ("crop", np.float64, (nc, 24)), ("src_index", np.int32, (nc,)),
+             ("k", np.float32, (nc, 3, 3)), ("ext", np.float32, (nc, 4, 4)), ("range", np.int64, (ns, 2)),
+             ("mem", np.int64, (ns,)), ("hand", np.int64, (ns,)), ("use", np.uint8, (ns,)),
+             ("skel", np.float32, (1, 2, 22, 3)), ("img", np.uint8, (4, hgt, wid))],
+            [("pose", np.float32, (ns, 60)), ("kp", np.float32, (ns, 21, 3)), ("status", np.int32, (2,))])
+
+
 class _Stage:
     """One pinned host buffer + its device mirror with a fixed layout: everything a call needs goes up in ONE
     host->device copy and everything it returns comes back in ONE device->host copy (the per-frame API otherwise
@@ -279,34 +355,14 @@ class _Stage:
 
     def __init__(self, dev: torch.device, fields_in, fields_out):
         self.dev = dev
-        self.in_off, self.out_off = {}, {}
-        off = 0
-        for name, dtype, shape in fields_in:
-            n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-            self.in_off[name] = (off, dtype, shape)
-            off += (n + 15) // 16 * 16
-        self.in_bytes = off
-        off = 0
-        for name, dtype, shape in fields_out:
-            n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-            self.out_off[name] = (off, dtype, shape)
-            off += (n + 15) // 16 * 16
-        self.out_bytes = off
+        self.in_off, self.in_bytes = _stage_layout(fields_in)
+        self.out_off, self.out_bytes = _stage_layout(fields_out)
         self.h_in = torch.empty(self.in_bytes, dtype=torch.uint8).pin_memory()
         self.d_in = torch.empty(self.in_bytes, dtype=torch.uint8, device=dev)
         self.h_out = torch.empty(self.out_bytes, dtype=torch.uint8).pin_memory()
         self.d_out = torch.empty(self.out_bytes, dtype=torch.uint8, device=dev)
-        hin, hout = self.h_in.numpy(), self.h_out.numpy()
-        self.np_in = {k: hin[o: o + int(np.prod(sh)) * np.dtype(dt).itemsize].view(dt).reshape(sh)
-                      for k, (o, dt, sh) in self.in_off.items()}
-        self.np_out = {k: hout[o: o + int(np.prod(sh)) * np.dtype(dt).itemsize].view(dt).reshape(sh)
-                       for k, (o, dt, sh) in self.out_off.items()}
-        tdt = {np.dtype(k): v for k, v in ((np.uint8, torch.uint8), (np.int32, torch.int32), (np.int64, torch.int64),
-                                           (np.float32, torch.float32), (np.float64, torch.float64))}
-        self.t_in = {k: self.d_in[o: o + int(np.prod(sh)) * np.dtype(dt).itemsize].view(tdt[np.dtype(dt)]).reshape(sh)
-                     for k, (o, dt, sh) in self.in_off.items()}
-        self.t_out = {k: self.d_out[o: o + int(np.prod(sh)) * np.dtype(dt).itemsize].view(tdt[np.dtype(dt)]).reshape(sh)
-                      for k, (o, dt, sh) in self.out_off.items()}
+        self.np_in, self.t_in = _stage_views(self.h_in.numpy(), self.in_off), _stage_views(self.d_in, self.in_off)
+        self.np_out, self.t_out = _stage_views(self.h_out.numpy(), self.out_off), _stage_views(self.d_out, self.out_off)
 
     def upload(self, n_bytes: Optional[int] = None):
         n = self.in_bytes if n_bytes is None else n_bytes
@@ -405,27 +461,17 @@ class HandTracker:
                 and len({(c.width, c.height) for c in cameras}) == 1
                 and hand_model.joint_limits is not None and hand_model.joint_rest_positions.dim() == 2)
 
-    _MAX_CAMS = 8
-
     def _gen_crop_cameras_batched(self, cameras, camera_angles, hand_model, hands, min_num_crops):
         """All hands of the frame through one ut_gen_crop_cameras launch (lib/tracker/tracker.py:222-260): one
         staged upload (camera rows + poses), one launch, one read-back.  The launch also returns the landmarks of
         every pose; they are remembered for landmarks_from_hand_pose (the eval scripts ask for them next)."""
-        from .hand import device_blob
         dev = torch.device("cuda", torch.cuda.current_device())
         n, nc, v = len(hands), len(cameras), MAX_VIEW_NUM
-        if n > NUM_HANDS or nc > self._MAX_CAMS:
+        if n > NUM_HANDS or nc > _MAX_CAMS:
             return None
         st = self._crop_stage
         if st is None or st.dev != dev:
-            c = self._MAX_CAMS
-            st = self._crop_stage = _Stage(dev, [("cam", np.float64, (c, 32)), ("angles", np.float64, (c,)),
-                                                 ("ja", np.float32, (NUM_HANDS, 22)), ("xf", np.float32, (NUM_HANDS, 16)),
-                                                 ("frame", np.int32, (NUM_HANDS,)), ("hand", np.int64, (NUM_HANDS,))],
-                                           [("crop", np.float64, (NUM_HANDS, v, 24)), ("k", np.float32, (NUM_HANDS, v, 9)),
-                                            ("ext", np.float32, (NUM_HANDS, v, 16)), ("cam_index", np.int32, (NUM_HANDS, v)),
-                                            ("n_views", np.int32, (NUM_HANDS,)), ("status", np.int32, (NUM_HANDS,)),
-                                            ("landmarks", np.float32, (NUM_HANDS, 21, 3))])
+            st = self._crop_stage = _Stage(dev, *_crop_stage_fields())
             st.np_in["frame"][:] = 0
         a = st.np_in
         for ci, cam in enumerate(cameras):
@@ -440,16 +486,14 @@ class HandTracker:
         if self._limits_dev is None or self._limits_dev[0] is not lim:
             self._limits_dev = (lim, lim.float().contiguous().to(dev))
         blob = device_blob(hand_model, dev)
-        ti, to = st.t_in, st.t_out
+        ti = st.t_in
         # (the staged frame index is always 0 and the hands come from the caller's dict: no index read-back)
         _native.gen_crop_cameras(
             ti["cam"][:nc], ti["angles"][:nc], blob, self._limits_dev[1], ti["ja"][:n], ti["xf"][:n], ti["frame"][:n],
             ti["hand"][:n], nc, (cameras[0].width, cameras[0].height), max_views=v,
             min_vis=self._min_required_vis_landmarks, crop_size=int(self._input_size[0]),
             focal_multiplier=self._hand_ratio_in_crop, check_indices=False, want_landmarks=True,
-            out={"crop_params": to["crop"][:n], "intrinsics": to["k"][:n], "extrinsics": to["ext"][:n],
-                 "cam_index": to["cam_index"][:n], "n_views": to["n_views"][:n], "status": to["status"][:n],
-                 "landmarks": to["landmarks"][:n]})
+            out=_crop_out_dict(st, n))
         st.download()                                                         # one read-back
         o = st.np_out
         crop_cameras: Dict[int, Dict[int, PinholePlaneCameraModel]] = {}
@@ -458,10 +502,7 @@ class HandTracker:
             if int(o["status"][i]) != 0:
                 raise ValueError("Unable to create crop camera")
             _landmark_memo.put(hand_model, hand_idx, pose.joint_angles, pose.wrist_xform, o["landmarks"][i])
-            per_hand = {}
-            for k in range(int(o["n_views"][i])):
-                per_hand[int(o["cam_index"][i, k])] = _crop_camera_from_row(
-                    o["crop"][i, k].copy(), o["k"][i, k].copy(), o["ext"][i, k].copy(), size)
+            per_hand = _crop_cameras_from_rows(o, i, size)
             if per_hand and len(per_hand) >= min_num_crops:
                 crop_cameras[hand_idx] = per_hand
         return crop_cameras
@@ -492,15 +533,9 @@ class HandTracker:
 
     def _gen_crop_cameras_from_window_batched(self, camera_left, camera_right, left, right, hands):
         dev = torch.device("cuda", torch.cuda.current_device())
-        v = MAX_VIEW_NUM
         st = self._window_stage
         if st is None or st.dev != dev:
-            st = self._window_stage = _Stage(
-                dev, [("cam", np.float64, (2, 32)), ("kp", np.float64, (NUM_HANDS, v, 21, 2)),
-                      ("src_row", np.int32, (NUM_HANDS, v)), ("hand", np.int64, (NUM_HANDS,))],
-                [("crop", np.float64, (NUM_HANDS, v, 24)), ("k", np.float32, (NUM_HANDS, v, 9)),
-                 ("ext", np.float32, (NUM_HANDS, v, 16)), ("cam_index", np.int32, (NUM_HANDS, v)),
-                 ("n_views", np.int32, (NUM_HANDS,)), ("status", np.int32, (NUM_HANDS,))])
+            st = self._window_stage = _Stage(dev, *_window_stage_fields())
         a = st.np_in
         a["cam"][0] = geometry.pack_camera_model(camera_left)
         a["cam"][1] = geometry.pack_camera_model(camera_right)
@@ -513,23 +548,17 @@ class HandTracker:
                 else:
                     a["src_row"][i, view] = -1
         st.upload()
-        ti, to = st.t_in, st.t_out
-        n = len(hands)
+        ti, n = st.t_in, len(hands)
         # (_window_cropgen_ok vetted the hands and the rows are 0 / 1 / -1; the C entry checks the indices again itself)
         _native.gen_crop_cameras_from_window_points(
             ti["cam"], ti["kp"][:n], ti["src_row"][:n], ti["hand"][:n], crop_size=int(self._input_size[0]),
-            focal_multiplier=self._hand_ratio_in_crop, check_indices=False,
-            out={"crop_params": to["crop"][:n], "intrinsics": to["k"][:n], "extrinsics": to["ext"][:n],
-                 "cam_index": to["cam_index"][:n], "n_views": to["n_views"][:n], "status": to["status"][:n]})
+            focal_multiplier=self._hand_ratio_in_crop, check_indices=False, out=_crop_out_dict(st, n))
         st.download()                                                         # one read-back
         o = st.np_out
         if (o["status"][:n] != 0).any():
             raise ValueError("Unable to create crop camera")
         size = int(self._input_size[0])
-        return {h: {int(o["cam_index"][i, k]): _crop_camera_from_row(o["crop"][i, k].copy(), o["k"][i, k].copy(),
-                                                                     o["ext"][i, k].copy(), size)
-                    for k in range(int(o["n_views"][i]))}
-                for i, h in enumerate(hands)}
+        return {h: _crop_cameras_from_rows(o, i, size) for i, h in enumerate(hands)}
 
     # ------------------------------------------------------------------ network inputs
     def _make_inputs(self, sample: InputFrame, hand_model_mm: Optional[HandModel], crop_cameras):
@@ -592,16 +621,11 @@ class HandTracker:
         key = (str(dev), hgt, wid)
         st = self._frame_stage
         if st is None or self._frame_stage_key != key:
-            nc, ns = NUM_HANDS * MAX_VIEW_NUM, NUM_HANDS
-            st = self._frame_stage = _Stage(
-                dev, [("cam", np.float64, (4, 32)), ("crop", np.float64, (nc, 24)), ("src_index", np.int32, (nc,)),
-                      ("k", np.float32, (nc, 3, 3)), ("ext", np.float32, (nc, 4, 4)), ("range", np.int64, (ns, 2)),
-                      ("mem", np.int64, (ns,)), ("hand", np.int64, (ns,)), ("use", np.uint8, (ns,)),
-                      ("skel", np.float32, (1, 2, 22, 3)), ("img", np.uint8, (4, hgt, wid))],
-                [("pose", np.float32, (ns, 60)), ("kp", np.float32, (ns, 21, 3)), ("status", np.int32, (2,))])
+            nc = NUM_HANDS * MAX_VIEW_NUM
+            st = self._frame_stage = _Stage(dev, *_frame_stage_fields(hgt, wid))
             self._frame_stage_key = key
             self._feat = torch.empty(nc, 72, 6, 6, device=dev)
-            self._engine().reserve(nc, ns, NUM_HANDS)
+            self._engine().reserve(nc, NUM_HANDS, NUM_HANDS)
         a = st.np_in
         slot_of = {ci: i for i, ci in enumerate(used)}
         for i, ci in enumerate(used):
@@ -632,10 +656,7 @@ class HandTracker:
         all_multiview = all(len(v) == MAX_VIEW_NUM for v in crop_cameras.values())
         if calibrate and not all_multiview:
             raise AssertionError("Unsupported: found single-view samples when calibration scale")
-        blob = None
-        if hand_model is not None:
-            from .hand import device_blob
-            blob = device_blob(hand_model, dev)
+        blob = None if hand_model is None else device_blob(hand_model, dev)
         n_used, n_slots = len(used), max(hands) + 1
 
         # (Replaying the sequence as a captured hipGraph was measured in round 2: no gain - the loop is bound by the ~0.9 ms of
@@ -657,21 +678,14 @@ class HandTracker:
         o = st.np_out
         if o["status"][0] != 0:
             eng.poll_status()                                                 # raises for the failed check, clears it
-        hand_poses, num_views, predicted_scales = {}, {}, {}
-        for i, hand_idx in enumerate(hands):
-            rec = o["pose"][i]
-            xf = rec[22:38].reshape(4, 4).copy()
-            xf[:3, 3] *= np.float32(M_TO_MM)
-            pose_i = SingleHandPose(joint_angles=rec[:22].copy(), wrist_xform=xf, hand_confidence=1.0)
-            hand_poses[hand_idx] = pose_i
-            num_views[hand_idx] = len(crop_cameras[hand_idx])
-            if calibrate:
-                predicted_scales[hand_idx] = rec[38].copy()
-            elif hand_model is not None:
+        rec = o["pose"][:s]
+        res = self._tracking_result(hands, rec[:, :22].copy(), rec[:, 22:38].reshape(s, 4, 4).copy(),
+                                    rec[:, 38].copy() if calibrate else None, crop_cameras)
+        if not calibrate and hand_model is not None:
+            for i, hand_idx in enumerate(hands):
+                pose_i = res.hand_poses[hand_idx]
                 _landmark_memo.put(hand_model, hand_idx, pose_i.joint_angles, pose_i.wrist_xform, o["kp"][i])
-        for hand_idx in range(NUM_HANDS):
-            self._valid_tracking_history[hand_idx] = hand_idx in hand_poses
-        return TrackingResult(hand_poses=hand_poses, num_views=num_views, predicted_scales=predicted_scales)
+        return res
 
     def _run(self, sample, hand_model, crop_cameras, calibrate: bool) -> TrackingResult:
         if not crop_cameras:
@@ -708,13 +722,17 @@ class HandTracker:
 
     def _gen_tracking_result(self, regressor_output: RegressorOutput, hand_indices: np.ndarray, crop_cameras
                              ) -> TrackingResult:
-        """m -> mm, per-hand dicts, validity history (lib/tracker/tracker.py:370-412)."""
-        ja = regressor_output.joint_angles.to("cpu").numpy()
-        xf = regressor_output.wrist_xfs.to("cpu").numpy()
-        xf[..., :3, 3] *= M_TO_MM
         scales = None if regressor_output.skel_scales is None else regressor_output.skel_scales.to("cpu").numpy()
+        return self._tracking_result(hand_indices, regressor_output.joint_angles.to("cpu").numpy(),
+                                     regressor_output.wrist_xfs.to("cpu").numpy(), scales, crop_cameras)
+
+    def _tracking_result(self, hands, ja: np.ndarray, xf: np.ndarray, scales: Optional[np.ndarray], crop_cameras
+                         ) -> TrackingResult:
+        """m -> mm, per-hand dicts, validity history (lib/tracker/tracker.py:370-412).  Row i of ja [S,22], xf [S,4,4]
+        (metres; scaled in place, the caller hands over arrays of its own) and scales [S] (or None) belongs to hands[i]."""
+        xf[..., :3, 3] *= M_TO_MM
         hand_poses, num_views, predicted_scales = {}, {}, {}
-        for i, hand_idx in enumerate(hand_indices):
+        for i, hand_idx in enumerate(hands):
             hand_poses[hand_idx] = SingleHandPose(joint_angles=ja[i], wrist_xform=xf[i], hand_confidence=1.0)
             num_views[hand_idx] = len(crop_cameras[hand_idx])
             if scales is not None:

@@ -163,6 +163,33 @@ def test_landmarks_output_equals_fk(labels, hand_model):
     assert g["landmarks"].shape == want.shape and torch.equal(g["landmarks"], want)
 
 
+def test_per_candidate_models_equal_fk_and_single_launches(labels, hand_model):
+    """n_models == n: three candidates (hands 0, 1, 1), each with a model and joint limits of its own.  The landmarks are
+    ut_fk of the same blobs and poses (right hands mirrored), bit for bit, and every output row is what a launch of that
+    candidate alone (its model as the launch's only one) writes."""
+    c = pipeline.label_candidates(labels, [0, 1])
+    sel = [0, 1, 3]
+    assert c["hand_idx"][sel].tolist() == [0, 1, 1]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    blobs = t(np.stack([_native.hand_model_blob(
+        hand_model.joint_rotation_axes, hand_model.joint_rest_positions * s, hand_model.landmark_rest_positions * s,
+        hand_model.landmark_rest_bone_weights, hand_model.landmark_rest_bone_indices) for s in (0.95, 1.0, 1.05)]))
+    lim = hand_model.joint_limits.float()
+    limits = torch.stack([lim, lim * 0.8, lim * 1.2]).to(DEV)
+    cam, ang = t(c["cam_params"]), t(c["camera_angles"])
+    ja, xf, frame, hand = (t(c[k][sel]) for k in ("joint_angles", "wrist_xf", "frame_idx", "hand_idx"))
+    g = _native.gen_crop_cameras(cam, ang, blobs, limits, ja, xf, frame, hand, c["n_cams"], c["src_wh"], want_landmarks=True)
+    assert g["status"].tolist() == [0, 0, 0] and bool((g["n_views"] > 0).all())
+    assert torch.equal(g["landmarks"], _native.fk_stateless(blobs, ja, xf, mirror=hand))
+    for i in range(3):
+        r = slice(i, i + 1)
+        one = _native.gen_crop_cameras(cam, ang, blobs[r], limits[r], ja[r], xf[r], frame[r], hand[r], c["n_cams"],
+                                       c["src_wh"], want_landmarks=True)
+        assert sorted(one) == sorted(g)
+        for k, v in g.items():
+            assert torch.equal(v[r], one[k]), (i, k)
+
+
 @pytest.mark.parametrize("n", [1, 2])
 def test_out_buffers_equal_allocation(labels, hand_model, n):
     """out=: leading-row views of buffers sized for 2 hands (the per-frame tracker's staging layout: intrinsics [2,V,9],

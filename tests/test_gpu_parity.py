@@ -495,6 +495,29 @@ def test_fk_per_pose_models_and_empty(engine):
     assert engine.fk(_dev(blobs[:1]), torch.empty(0, 22, device=DEV), torch.empty(0, 4, 4, device=DEV)).shape == (0, 21, 3)
 
 
+def test_fk_tail_block_equals_single_pose_launches():
+    """13 poses are one full block of 12 and a one-pose tail.  With per-pose models, mixed mirror flags and t_scale 1000
+    every pose comes out bit for bit as a launch of that pose alone gives it: neither its place in a block nor the
+    block's other poses enter."""
+    hm = scenarios.hand_model_mm()
+    lab = scenarios.labels()
+    n = 13
+    ja = _dev(lab["joint_angles"][:n, 0].astype(np.float32))
+    xf = lab["wrist_transforms"][:n, 0].astype(np.float32)
+    xf[:, :3, 3] *= np.float32(0.001)                                      # metres: t_scale brings them back to mm
+    xf = _dev(xf)
+    blobs = _dev(np.stack([_native.hand_model_blob(hm["joint_rotation_axes"], hm["joint_rest_positions"] * s,
+                                                   hm["landmark_rest_positions"] * s, hm["landmark_rest_bone_weights"],
+                                                   hm["landmark_rest_bone_indices"])
+                           for s in np.linspace(0.8, 1.2, n).astype(np.float32)]))
+    mirror = _dev((np.arange(n) % 3 == 0).astype(np.int64))               # 1 0 0 1 ... and 1 for the tail pose
+    got = _native.fk_stateless(blobs, ja, xf, mirror=mirror, t_scale=1000.0)
+    assert got.shape == (n, 21, 3) and bool(torch.isfinite(got).all())
+    for i in range(n):
+        one = _native.fk_stateless(blobs[i:i + 1], ja[i:i + 1], xf[i:i + 1], mirror=mirror[i:i + 1], t_scale=1000.0)
+        assert torch.equal(got[i:i + 1], one), i
+
+
 def test_fk_multi_bone_blend_and_duplicate_bone_entries(engine, golden_dir):
     """Linear blend skinning with 2-3 non-zero bone weights per landmark (lib/common/hand_skinning.py:56-97).
     In every model the reference ships, landmark 20 (palm centre) blends three bones (weights .887/.077/.036 on

@@ -529,3 +529,40 @@ def test_pack_time_channel_canonicalisation_is_exact_and_invariant(spread):
     got = F.conv2d(x, proj[0], proj[1])
     want = ref_model.backbone(ref_model.to_torch_state_dict(sd), crops)
     assert (got - want).abs().max().item() < 2e-5 * max(1.0, want.abs().max().item())
+
+
+# ----------------------------------------------------------------------------- tracker staging layout
+@pytest.mark.parametrize("fields", [tracker._crop_stage_fields(), tracker._window_stage_fields(),
+                                    tracker._frame_stage_fields(480, 636), tracker._frame_stage_fields(7, 5)],
+                         ids=["crop", "window", "frame", "frame_odd_image"])
+def test_stage_layout_is_aligned_disjoint_and_typed_alike(fields):
+    """The per-frame tracker's staging buffers (tracker._Stage is these two helpers plus a pinned and a device buffer):
+    every field starts on a 16-byte boundary, fields follow each other without overlap, the total is the sum of the sizes
+    rounded up to 16, and the numpy view and the tensor view of a field have one shape and one dtype and cover the same
+    bytes."""
+    for side in fields:
+        layout, total = tracker._stage_layout(side)
+        assert list(layout) == [name for name, _, _ in side]
+        end, rounded = 0, 0
+        for name, dtype, shape in side:
+            off, dt, sh = layout[name]
+            size = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            assert (dt, sh) == (dtype, shape)
+            assert off % 16 == 0 and off >= end, name
+            end = off + size
+            rounded += (size + 15) // 16 * 16
+        assert total == rounded and end <= total
+        host = np.zeros(total, np.uint8)
+        dev = torch.from_numpy(host)                 # a tensor over the same bytes stands in for the device mirror
+        np_views, t_views = tracker._stage_views(host, layout), tracker._stage_views(dev, layout)
+        assert list(np_views) == list(t_views) == list(layout)
+        for name, dtype, shape in side:
+            a, t = np_views[name], t_views[name]
+            assert a.shape == tuple(t.shape) == tuple(shape), name
+            assert a.dtype == np.dtype(dtype) and t.numpy().dtype == a.dtype, name
+            size = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            a.reshape(-1).view(np.uint8)[:] = 255    # a write through one view fills the field's bytes and no others ...
+            off = layout[name][0]
+            assert int((host == 255).sum()) == size and bool((host[off: off + size] == 255).all()), name
+            assert bool((t.reshape(-1).view(torch.uint8) == 255).all()), name      # ... and shows in the other view
+            host[:] = 0
