@@ -1,6 +1,6 @@
-// C ABI of libumetrack_hip.so (include/umetrack_hip.h): handle, weight folding/packing, workspace,
-// temporal state and the launch sequences of the hot path.  Host-only logic; kernels live in the
-// other translation units.
+// C ABI of libumetrack_hip.so (include/umetrack_hip.h): handle, weight upload, workspace, temporal state
+// and the launch sequences of the hot path.  Host-only logic; kernels live in the other translation
+// units, weight folding and packing in ut_weights.cpp.
 #include "../../include/umetrack_hip.h"
 
 #include <math.h>
@@ -16,21 +16,19 @@
 #include <vector>
 
 #include "ut_kernels.h"
+#include "ut_weights.h"
 
 namespace {
 
 thread_local std::string g_create_error;
 
-struct ConvW {
+struct ConvW : ut::ConvGeom {
   float* w = nullptr;     // device [cout_pad][k_pad]
   void* w_split = nullptr;   // device: the two fp16 planes of w * 2^k in fragment order (conv_split.hip), eligible layers only
   float split_unscale = 0.f; // 2^-k
   float wsum_rows = 0.f;     // max over output channels of sum_k |w| (folded), rounded up: bounds |conv(x)| by wsum_rows * max|x|
   float bias_max = 0.f;      // max |bias| (folded)
   float* bias = nullptr;  // device [cout_pad]
-  int cin = 0, cin_pad = 0, cout = 0, cout_pad = 0, cout_store = 0;
-  int taps = 1, ksize = 1, stride = 1, pad = 0, k_total = 0, k_pad = 0, cslice = 0;
-  double flops_per_pixel = 0;   // 2 * taps * cin * cout, un-padded
 };
 
 struct Block {
@@ -143,8 +141,6 @@ int fail(ut_handle h, int code, const char* what, hipError_t e = hipSuccess) {
     if (e_ != hipSuccess) return fail(h, UT_E_HIP, #x, e_);     \
   } while (0)
 
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // Every entry that allocates or launches runs on the handle's device whatever the caller's current device is,
 // and leaves the caller's current device as it found it.
 struct DeviceScope {
@@ -225,309 +221,45 @@ int check_status(ut_handle h, int* dev, int* host, hipStream_t s, const char* wh
   return UT_OK;
 }
 
-struct Cursor {
-  const float* p;
-  size_t left;
-  const float* take(size_t n) {
-    if (n > left) { left = 0; ok = false; return nullptr; }
-    const float* r = p; p += n; left -= n; return r;
-  }
-  bool ok = true;
-};
-
-struct BN { const float *g = nullptr, *b = nullptr, *m = nullptr, *v = nullptr; };
-
-BN take_bn(Cursor& c, int ch) {
-  BN bn;
-  bn.g = c.take(ch); bn.b = c.take(ch); bn.m = c.take(ch); bn.v = c.take(ch);
-  c.take(1);   // num_batches_tracked
-  return bn;
+int upload_bytes(ut_handle h, const void* host, size_t bytes, void** dev) {
+  void* d = nullptr;
+  HIPCHK(h, hipMalloc(&d, bytes));
+  h->allocs.push_back(d);
+  HIPCHK(h, hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+  *dev = d;
+  return UT_OK;
 }
 
 int upload(ut_handle h, const std::vector<float>& host, float** dev) {
-  void* d = nullptr;
-  HIPCHK(h, hipMalloc(&d, host.size() * sizeof(float)));
-  h->allocs.push_back(d);
-  HIPCHK(h, hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  *dev = (float*)d;
-  return UT_OK;
+  return upload_bytes(h, host.data(), host.size() * sizeof(float), (void**)dev);
 }
 
-// One convolution with eval-mode BatchNorm (eps 1e-5) folded in, as the reference's tensors lay it out:
-//   y = s*(conv(x)+b-mean)+beta,  s = gamma/sqrt(var+eps)   ->   w[o][c][t] * s[o],  bias[o] = (b-mean)*s+beta
-// (fold in double, one rounding to fp32).
-struct Folded {
-  std::vector<float> w;      // [cout][cin][taps]
-  std::vector<float> b;      // [cout]
-  int cin = 0, cout = 0, taps = 0;
-};
-
-Folded fold_conv(const float* w, const float* conv_bias, const BN* bn, int cin, int cout, int taps) {
-  Folded f;
-  f.cin = cin; f.cout = cout; f.taps = taps;
-  f.w.resize((size_t)cout * cin * taps);
-  f.b.resize(cout);
-  for (int o = 0; o < cout; ++o) {
-    double s = 1.0, shift = conv_bias ? (double)conv_bias[o] : 0.0;
-    if (bn) {
-      s = (double)bn->g[o] / sqrt((double)bn->v[o] + 1e-5);
-      shift = (shift - (double)bn->m[o]) * s + (double)bn->b[o];
-    }
-    f.b[o] = (float)shift;
-    for (size_t i = (size_t)o * cin * taps; i < (size_t)(o + 1) * cin * taps; ++i) f.w[i] = (float)((double)w[i] * s);
-  }
-  return f;
+// The weights arrive folded and laid out (ut_weights.h); everything below only copies them to the device.
+int upload_conv(ut_handle h, ConvW& cw, const ut::PackedConv& pc) {
+  static_cast<ut::ConvGeom&>(cw) = pc;
+  cw.split_unscale = pc.split_unscale; cw.wsum_rows = pc.wsum_rows; cw.bias_max = pc.bias_max;
+  int rc = upload(h, pc.wp, &cw.w);
+  if (!rc && !pc.planes.empty()) rc = upload_bytes(h, pc.planes.data(), pc.planes.size() * sizeof(uint16_t), &cw.w_split);
+  return rc ? rc : upload(h, pc.bp, &cw.bias);
 }
 
-// ---- channel canonicalisation (exact: powers of two only) --------------------------------------------------------------
-// relu(bn(conv)) commutes with a positive per-channel factor, and a power of two commutes with every fp32 rounding
-// (lib/models/backbone_resnet.py:56-72): scaling output channel c of a producer (its folded weight row and bias) by 2^k
-// and input channel c of every consumer (its weight column) by 2^-k leaves every later fp32 value bit for bit as it was.
-// A checkpoint fixes the scale of an inner channel only up to that freedom (a near-dead BatchNorm channel and the large
-// consumer weights that compensate it are the same function as a well-scaled pair), while the split-fp16 arithmetic keeps
-// ONE power-of-two scale per activation tensor and ONE per weight tensor: a channel 2^-18 below its tensor's largest has a
-// subnormal second piece.  So every channel is brought to a canonical scale at pack time: 2^k_c puts the largest magnitude
-// among the channel's producer rows (weights and bias) into [1, 2).  Two networks that differ by per-channel powers of two
-// pack to the same tensors, in both arithmetics.
-float row_max(const Folded& f, int o) {
-  float m = fabsf(f.b[o]);
-  const size_t n = (size_t)f.cin * f.taps;
-  for (size_t i = 0; i < n; ++i) {
-    const float a = fabsf(f.w[(size_t)o * n + i]);
-    m = a > m ? a : m;          // (a NaN never raises m: such a row keeps its scale)
-  }
-  return m;
-}
-int octave_shift(float m) {       // k with m * 2^k in [1, 2); 0 when the row is all zeros or not finite
-  if (!(m > 0.f) || !(m < INFINITY)) return 0;
-  return -ilogbf(m);
-}
-void scale_row(Folded& f, int o, int k) {
-  if (!k) return;
-  const size_t n = (size_t)f.cin * f.taps;
-  for (size_t i = 0; i < n; ++i) f.w[(size_t)o * n + i] = ldexpf(f.w[(size_t)o * n + i], k);
-  f.b[o] = ldexpf(f.b[o], k);
-}
-void scale_col(Folded& f, int c, int k) {
-  if (!k) return;
-  for (int o = 0; o < f.cout; ++o)
-    for (int t = 0; t < f.taps; ++t) {
-      float& v = f.w[((size_t)o * f.cin + c) * f.taps + t];
-      v = ldexpf(v, k);
-    }
-}
-// Channel c of one activation tensor: `keys` (a subset of its producers) define 2^k_c, every producer's row c is scaled by it
-// and every consumer's column c by its inverse.
-void canonicalise_channels(const std::vector<Folded*>& keys, const std::vector<Folded*>& producers,
-                           const std::vector<Folded*>& consumers) {
-  const int ch = keys[0]->cout;
-  for (int c = 0; c < ch; ++c) {
-    float m = 0.f;
-    for (Folded* p : keys) { const float r = row_max(*p, c); m = r > m ? r : m; }
-    const int k = octave_shift(m);
-    for (Folded* p : producers) scale_row(*p, c, k);
-    for (Folded* q : consumers) scale_col(*q, c, -k);
-  }
-}
-
-// Pack folded weights to [cout_pad][k_pad] with k = slice*(taps*cslice) + tap*cslice + c (see ut_kernels.h).
-int pack_conv(ut_handle h, ConvW& cw, const Folded& f, int ksize, int stride, int cout_store) {
-  const int cin = f.cin, cout = f.cout;
-  cw.cin = cin; cw.cout = cout; cw.ksize = ksize; cw.stride = stride;
-  cw.pad = ksize == 3 ? 1 : 0;
-  cw.taps = ksize * ksize;
-  cw.cin_pad = round_up(cin, 4);
-  cw.cout_store = cout_store;
-  cw.cout_pad = round_up(cout_store, 128);
-  cw.k_total = cw.taps * cw.cin_pad;
-  cw.cslice = cw.cin_pad % 32 == 0 ? 32 : cw.cin_pad;
-  cw.k_pad = round_up(cw.k_total, 32);
-  cw.flops_per_pixel = 2.0 * cw.taps * cin * cout;
-  std::vector<float> wp((size_t)cw.cout_pad * cw.k_pad, 0.f), bp(cw.cout_pad, 0.f);
-  for (int o = 0; o < cout; ++o) {
-    bp[o] = f.b[o];
-    for (int c = 0; c < cin; ++c)
-      for (int t = 0; t < cw.taps; ++t)
-        wp[(size_t)o * cw.k_pad + (c / cw.cslice) * (cw.taps * cw.cslice) + t * cw.cslice + c % cw.cslice] =
-            f.w[((size_t)o * cin + c) * cw.taps + t];
-  }
-  {
-    double ws = 0.0, bm = 0.0;
-    for (int o = 0; o < cout; ++o) {
-      double rs = 0.0;
-      for (int k = 0; k < cw.k_pad; ++k) rs += fabs((double)wp[(size_t)o * cw.k_pad + k]);
-      ws = rs > ws ? rs : ws;
-      bm = fabs((double)bp[o]) > bm ? fabs((double)bp[o]) : bm;
-    }
-    cw.wsum_rows = (float)(ws * 1.0001);
-    cw.bias_max = (float)(bm * 1.0001);
-  }
-  int rc = upload(h, wp, &cw.w);
-  if (rc) return rc;
-  // fp16 planes for the split-fp16 kernels: the layers they take (channel slice == chunk width, >= 6 chunks: the 3x3
-  // convolutions of the backbone; conv_split.hip from 64 channels out, conv_patch.hip's split instantiation for layer1)
-  // (and the 1x1 stride-2 shortcut of a 32-channel input: conv_c32s2.hip computes it beside the block's first convolution)
-  if (cw.cslice == 32 && (cw.k_pad / 32 >= 6 || (ksize == 1 && stride == 2 && cw.cin_pad == 32)) && cw.cout_store >= 32 && cw.cout_store % 4 == 0) {
-    std::vector<uint16_t> planes((size_t)2 * cw.cout_pad * cw.k_pad);
-    const float scale = ut::split_weight_scale(wp.data(), wp.size());
-    cw.split_unscale = 1.0f / scale;
-    ut::pack_split_weights(wp.data(), cw.cout_pad, cw.k_pad, scale, planes.data());
-    void* d = nullptr;
-    HIPCHK(h, hipMalloc(&d, planes.size() * sizeof(uint16_t)));
-    h->allocs.push_back(d);
-    HIPCHK(h, hipMemcpy(d, planes.data(), planes.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    cw.w_split = d;
-  }
-  return upload(h, bp, &cw.bias);
-}
-
-int pack_conv(ut_handle h, ConvW& cw, const float* w, const float* conv_bias, const BN* bn, int cin, int cout,
-              int ksize, int stride, int cout_store) {
-  return pack_conv(h, cw, fold_conv(w, conv_bias, bn, cin, cout, ksize * ksize), ksize, stride, cout_store);
-}
-
-constexpr int kRegSplitCh = 128;   // channels of the regressor's tensors when its convolutions run in split-fp16 (zero padded)
-
-// the same convolution with zero rows / columns up to cout x cin channels
-Folded pad_channels(const Folded& f, int cin, int cout) {
-  Folded g;
-  g.cin = cin; g.cout = cout; g.taps = f.taps;
-  g.w.assign((size_t)cout * cin * f.taps, 0.f);
-  g.b.assign(cout, 0.f);
-  for (int o = 0; o < f.cout; ++o) {
-    g.b[o] = f.b[o];
-    for (int c = 0; c < f.cin; ++c)
-      for (int t = 0; t < f.taps; ++t) g.w[((size_t)o * cin + c) * f.taps + t] = f.w[((size_t)o * f.cin + c) * f.taps + t];
-  }
-  return g;
-}
-
-// A BasicBlock's folded convolutions.
-struct FoldedBlock {
-  Folded conv1, conv2, ds;
-  bool has_ds = false;
-  int stride = 1;
-};
-
-bool fold_block(Cursor& c, FoldedBlock& fb, int cin, int cout, int stride, bool ds) {
-  const float* w1 = c.take((size_t)cout * cin * 9);
-  BN bn1 = take_bn(c, cout);
-  const float* w2 = c.take((size_t)cout * cout * 9);
-  BN bn2 = take_bn(c, cout);
-  const float* wd = nullptr;
-  BN bnd;
-  if (ds) { wd = c.take((size_t)cout * cin); bnd = take_bn(c, cout); }
-  if (!c.ok) return false;
-  fb.stride = stride; fb.has_ds = ds;
-  fb.conv1 = fold_conv(w1, nullptr, &bn1, cin, cout, 9);
-  fb.conv2 = fold_conv(w2, nullptr, &bn2, cout, cout, 9);
-  if (ds) fb.ds = fold_conv(wd, nullptr, &bnd, cin, cout, 1);
-  return true;
-}
-
-// the block's inner channels: conv1 writes them, conv2 reads them (conv1's input channels must have their final scale)
-void canonicalise_inner(FoldedBlock& fb) { canonicalise_channels({&fb.conv1}, {&fb.conv1}, {&fb.conv2}); }
-
-int pack_block(ut_handle h, Block& b, const FoldedBlock& fb) {
+int upload_block(ut_handle h, Block& b, const ut::FoldedBlock& fb) {
   int rc;
-  const int cs = round_up(fb.conv1.cout, 4);
-  if ((rc = pack_conv(h, b.conv1, fb.conv1, 3, fb.stride, cs))) return rc;
-  if ((rc = pack_conv(h, b.conv2, fb.conv2, 3, 1, cs))) return rc;
+  const int cs = ut::round_up(fb.conv1.cout, 4);
+  if ((rc = upload_conv(h, b.conv1, ut::pack_conv_host(fb.conv1, 3, fb.stride, cs)))) return rc;
+  if ((rc = upload_conv(h, b.conv2, ut::pack_conv_host(fb.conv2, 3, 1, cs)))) return rc;
   b.has_ds = fb.has_ds;
-  if (fb.has_ds && (rc = pack_conv(h, b.ds, fb.ds, 1, fb.stride, cs))) return rc;
+  if (fb.has_ds && (rc = upload_conv(h, b.ds, ut::pack_conv_host(fb.ds, 1, fb.stride, cs)))) return rc;
   return UT_OK;
 }
 
-// stem + ResNet "2352" + projection, folded, with canonical channel scales
-struct FoldedBackbone {
-  Folded stem, proj;
-  FoldedBlock fb[12];
-};
-
-bool fold_backbone(Cursor& c, FoldedBackbone& out) {
-  // stem (lib/models/model_utils.py:119-124)
-  const float* sw = c.take(32 * 9);
-  const float* sb = c.take(32);
-  BN sbn = take_bn(c, 32);
-  if (!c.ok) return false;
-  Folded& stem = out.stem;
-  Folded& proj = out.proj;
-  FoldedBlock* fb = out.fb;
-  stem = fold_conv(sw, sb, &sbn, 1, 32, 9);
-  // ResNet layers "2352", planes 32/64/128/256, strides 1/2/2/2 (lib/models/backbone_resnet.py:168-192)
-  const int nb[4] = {2, 3, 5, 2}, planes[4] = {32, 64, 128, 256}, strides[4] = {1, 2, 2, 2};
-  int first_of_layer[5] = {0, 0, 0, 0, 12};
-  int cin = 32, bi = 0;
-  for (int l = 0; l < 4; ++l) {
-    first_of_layer[l] = bi;
-    for (int k = 0; k < nb[l]; ++k) {
-      int st = k == 0 ? strides[l] : 1;
-      bool ds = k == 0 && (st != 1 || cin != planes[l]);
-      if (!fold_block(c, fb[bi++], cin, planes[l], st, ds)) return false;
-      cin = planes[l];
-    }
-  }
-  const float* pw = c.take(72 * 256); const float* pb = c.take(72);
-  if (!c.ok) return false;
-  proj = fold_conv(pw, pb, nullptr, 256, 72, 1);
-  // Canonical channel scales, fixed in network order so that each one is defined by tensors whose input side is final
-  // already (two checkpoints that differ by per-channel powers of two then arrive at the same tensors):
-  //  - the TRUNK of a layer (the tensor its identity shortcuts carry through the blocks): channel c is written by conv2 of
-  //    every block of the layer and by the first block's shortcut convolution (layer1: by the stem) and read by conv1 of the
-  //    layer's later blocks and by whatever enters the next layer (its first block's conv1 and shortcut convolution; after
-  //    layer4: the projection, whose 72 outputs are the features of the ABI and keep their scale).  Its scale comes from the
-  //    rows that write the trunk's FIRST tensor: the stem's, or the first block's shortcut and conv2 rows;
-  //  - the inner channels of every block, once the block's input has its scale.
-  for (int l = 0; l < 4; ++l) {
-    const int b0 = first_of_layer[l], b1 = l < 3 ? first_of_layer[l + 1] : 12;
-    std::vector<Folded*> keys, prod, cons;
-    if (fb[b0].has_ds) {
-      canonicalise_inner(fb[b0]);             // its input is the previous layer's trunk: final
-      keys = {&fb[b0].ds, &fb[b0].conv2};
-      prod = {&fb[b0].ds};
-    } else {
-      keys = {&stem};
-      prod = {&stem};
-      cons.push_back(&fb[b0].conv1);
-    }
-    for (int b = b0; b < b1; ++b) {
-      prod.push_back(&fb[b].conv2);
-      if (b > b0) cons.push_back(&fb[b].conv1);
-    }
-    if (l < 3) { cons.push_back(&fb[b1].conv1); cons.push_back(&fb[b1].ds); }
-    else cons.push_back(&proj);
-    canonicalise_channels(keys, prod, cons);
-    for (int b = fb[b0].has_ds ? b0 + 1 : b0; b < b1; ++b) canonicalise_inner(fb[b]);
-  }
-  return true;
-}
-
-int take_block(ut_handle h, Cursor& c, Block& b, int cin, int cout, int stride, bool ds) {
-  FoldedBlock fb;
-  if (!fold_block(c, fb, cin, cout, stride, ds)) return fail(h, UT_E_WEIGHTS, "weight blob too short");
-  canonicalise_inner(fb);
-  return pack_block(h, b, fb);
-}
-
-int take_regressor(ut_handle h, Cursor& c, Regressor& r, int ch, int d) {
-  r.c = ch; r.d = d;
+int upload_regressor(ut_handle h, Regressor& r, const ut::FoldedRegressor& fr) {
+  r.c = fr.c; r.d = fr.d;
   int rc;
-  for (int i = 0; i < 2; ++i) {
-    FoldedBlock fb;
-    if (!fold_block(c, fb, ch, ch, 1, false)) return fail(h, UT_E_WEIGHTS, "weight blob too short");
-    canonicalise_inner(fb);
-    if ((rc = pack_block(h, r.blocks[i], fb))) return rc;
-    FoldedBlock wide;
-    wide.stride = 1; wide.has_ds = false;
-    wide.conv1 = pad_channels(fb.conv1, kRegSplitCh, kRegSplitCh);
-    wide.conv2 = pad_channels(fb.conv2, kRegSplitCh, kRegSplitCh);
-    if ((rc = pack_block(h, r.blocks_split[i], wide))) return rc;
-  }
-  const float* w = c.take((size_t)d * ch);
-  const float* b = c.take(d);
-  if (!c.ok) return fail(h, UT_E_WEIGHTS, "weight blob too short");
-  if ((rc = upload(h, std::vector<float>(w, w + (size_t)d * ch), &r.w_out))) return rc;
-  return upload(h, std::vector<float>(b, b + d), &r.b_out);
+  for (int i = 0; i < 2; ++i)
+    if ((rc = upload_block(h, r.blocks[i], fr.blocks[i])) || (rc = upload_block(h, r.blocks_split[i], fr.wide[i]))) return rc;
+  if ((rc = upload(h, fr.w_out, &r.w_out))) return rc;
+  return upload(h, fr.b_out, &r.b_out);
 }
 
 int dev_alloc(ut_handle h, float** p, size_t n_floats) {
@@ -573,7 +305,7 @@ int ensure_phase_b_ws(ut_handle h, int crops) {
 
 int ensure_head_ws(ut_handle h, int samples, int n_skel) {
   ut::HeadBuffers& b = h->hb;
-  const size_t r = 36 * kRegSplitCh;
+  const size_t r = 36 * ut::kRegSplitCh;
   int rc = regrow(h, &h->ws_samples, samples, {{&b.cat144, 36 * 144}, {&b.f108, 36 * 108}, {&b.f72a, 36 * 72}, {&b.f72b, 36 * 72},
                                                 {&b.fused, 36 * 72}, {&b.t92a, 36 * 92}, {&b.t92b, 36 * 92}, {&b.regin, r},
                                                 {&b.rega, r}, {&b.regb, r}});
@@ -834,21 +566,21 @@ const char* ut_last_error(ut_handle h) { return h ? h->err.c_str() : g_create_er
 int ut_canonical_backbone_weights(const float* blob, size_t n_floats, float* out, size_t out_floats, size_t* n_out) {
   if (!blob || !n_out) return fail(nullptr, UT_E_INVALID, "ut_canonical_backbone_weights: null argument");
   if (n_floats != UT_WEIGHT_BLOB_FLOATS) return fail(nullptr, UT_E_WEIGHTS, "ut_canonical_backbone_weights: weight blob has the wrong length");
-  Cursor c{blob, n_floats};
-  FoldedBackbone fbb;
-  if (!fold_backbone(c, fbb)) return fail(nullptr, UT_E_WEIGHTS, "weight blob too short");
-  std::vector<const Folded*> all = {&fbb.stem};
-  for (const FoldedBlock& b : fbb.fb) {
+  ut::FoldedNetwork net;
+  if (!ut::fold_network(blob, n_floats, net)) return fail(nullptr, UT_E_WEIGHTS, "weight blob length does not match the architecture");
+  const ut::FoldedBackbone& fbb = net.backbone;
+  std::vector<const ut::Folded*> all = {&fbb.stem};
+  for (const ut::FoldedBlock& b : fbb.fb) {
     all.push_back(&b.conv1); all.push_back(&b.conv2);
     if (b.has_ds) all.push_back(&b.ds);
   }
   all.push_back(&fbb.proj);
   size_t n = 0;
-  for (const Folded* f : all) n += f->w.size() + f->b.size();
+  for (const ut::Folded* f : all) n += f->w.size() + f->b.size();
   *n_out = n;
   if (!out) return UT_OK;
   if (out_floats < n) return fail(nullptr, UT_E_INVALID, "ut_canonical_backbone_weights: output too small");
-  for (const Folded* f : all) {
+  for (const ut::Folded* f : all) {
     memcpy(out, f->w.data(), f->w.size() * sizeof(float)); out += f->w.size();
     memcpy(out, f->b.data(), f->b.size() * sizeof(float)); out += f->b.size();
   }
@@ -858,6 +590,8 @@ int ut_canonical_backbone_weights(const float* blob, size_t n_floats, float* out
 int ut_create(int device, const float* blob, size_t n_floats, ut_handle* out) {
   if (!blob || !out) return fail(nullptr, UT_E_INVALID, "ut_create: null argument");
   if (n_floats != UT_WEIGHT_BLOB_FLOATS) return fail(nullptr, UT_E_WEIGHTS, "ut_create: weight blob has the wrong length");
+  ut::FoldedNetwork net;      // the whole blob, folded on the host, before the handle owns any device memory
+  if (!ut::fold_network(blob, n_floats, net)) return fail(nullptr, UT_E_WEIGHTS, "weight blob length does not match the architecture");
   DeviceScope scope(device);          // the caller's current device is restored on return
   if (scope.err != hipSuccess) return fail(nullptr, UT_E_HIP, "hipSetDevice", scope.err);
   ut_handle h = new ut_context();
@@ -866,7 +600,6 @@ int ut_create(int device, const float* blob, size_t n_floats, ut_handle* out) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->num_cu = cus;
   }
-  Cursor c{blob, n_floats};
   int rc = UT_OK;
   do {
     { float* cnt = nullptr; if ((rc = dev_alloc(h, &cnt, 2 * kMaxCounters + 64))) break; h->counters = (unsigned*)cnt;
@@ -878,44 +611,21 @@ int ut_create(int device, const float* blob, size_t n_floats, ut_handle* out) {
       hipError_t e2 = hipMemset(h->status, 0, 2 * sizeof(int));
       if (e2 == hipSuccess) e2 = hipHostMalloc((void**)&h->status_host, 2 * sizeof(int), hipHostMallocDefault);
       if (e2 != hipSuccess) { rc = fail(h, UT_E_HIP, "status words", e2); break; } }
-    FoldedBackbone fbb;
-    if (!fold_backbone(c, fbb)) { rc = fail(h, UT_E_WEIGHTS, "weight blob too short"); break; }
-    const Folded& stem = fbb.stem;
-    const Folded& proj = fbb.proj;
-    const FoldedBlock* fb = fbb.fb;
-    if ((rc = upload(h, stem.w, &h->stem_w)) || (rc = upload(h, stem.b, &h->stem_b))) break;
-    for (int b = 0; b < 12 && !rc; ++b) rc = pack_block(h, h->bb[b], fb[b]);
+    const ut::FoldedBackbone& fbb = net.backbone;
+    if ((rc = upload(h, fbb.stem.w, &h->stem_w)) || (rc = upload(h, fbb.stem.b, &h->stem_b))) break;
+    for (int b = 0; b < 12 && !rc; ++b) rc = upload_block(h, h->bb[b], fbb.fb[b]);
     if (rc) break;
-    if ((rc = pack_conv(h, h->proj, proj, 1, 1, 72))) break;
-    // fusion 144 -> 108 -> 72 -> 72 (lib/models/model_utils.py:141-163)
-    { const float* w0 = c.take(108 * 144); const float* b0 = c.take(108); BN bn0 = take_bn(c, 108);
-      const float* w1 = c.take(72 * 108); const float* b1 = c.take(72); BN bn1 = take_bn(c, 72);
-      const float* w2 = c.take(72 * 72); const float* b2 = c.take(72);
-      if (!c.ok) { rc = fail(h, UT_E_WEIGHTS, "weight blob too short"); break; }
-      if ((rc = pack_conv(h, h->fus0, w0, b0, &bn0, 144, 108, 1, 1, 108)) ||
-          (rc = pack_conv(h, h->fus1, w1, b1, &bn1, 108, 72, 1, 1, 72)) ||
-          (rc = pack_conv(h, h->fus2, w2, b2, nullptr, 72, 72, 1, 1, 72))) break; }
-    // temporal 90 -> 90 x3 on a 92-channel padded layout (lib/models/temporal.py:31-38)
-    for (int i = 0; i < 3 && !rc; ++i) {
-      const float* tw = c.take(90 * 90); const float* tb = c.take(90);
-      if (!c.ok) { rc = fail(h, UT_E_WEIGHTS, "weight blob too short"); break; }
-      rc = pack_conv(h, h->tmp[i], tw, tb, nullptr, 90, 90, 1, 1, 92);
-    }
+    if ((rc = upload_conv(h, h->proj, ut::pack_conv_host(fbb.proj, 1, 1, 72)))) break;
+    if ((rc = upload_conv(h, h->fus0, ut::pack_conv_host(net.fusion[0], 1, 1, 108))) ||
+        (rc = upload_conv(h, h->fus1, ut::pack_conv_host(net.fusion[1], 1, 1, 72))) ||
+        (rc = upload_conv(h, h->fus2, ut::pack_conv_host(net.fusion[2], 1, 1, 72)))) break;
+    // the temporal block's 90 channels live on a 92-channel padded layout
+    for (int i = 0; i < 3 && !rc; ++i) rc = upload_conv(h, h->tmp[i], ut::pack_conv_host(net.temporal[i], 1, 1, 92));
     if (rc) break;
-    // skeleton encoder (lib/models/skeleton_encoder.py:36-41)
-    { const float* lw = c.take(144 * 132); const float* lb = c.take(144); BN bn = take_bn(c, 4);
-      if (!c.ok) { rc = fail(h, UT_E_WEIGHTS, "weight blob too short"); break; }
-      std::vector<float> sc(4), sh(4);
-      for (int k = 0; k < 4; ++k) {
-        double s = (double)bn.g[k] / sqrt((double)bn.v[k] + 1e-5);
-        sc[k] = (float)s; sh[k] = (float)((double)bn.b[k] - (double)bn.m[k] * s);
-      }
-      if ((rc = upload(h, std::vector<float>(lw, lw + 144 * 132), &h->skel_w)) ||
-          (rc = upload(h, std::vector<float>(lb, lb + 144), &h->skel_b)) ||
-          (rc = upload(h, sc, &h->skel_scale)) || (rc = upload(h, sh, &h->skel_shift))) break; }
-    if ((rc = take_regressor(h, c, h->reg_k, 76, 62))) break;
-    if ((rc = take_regressor(h, c, h->reg_u, 72, 63))) break;
-    if (!c.ok || c.left != 0) { rc = fail(h, UT_E_WEIGHTS, "weight blob length does not match the architecture"); break; }
+    if ((rc = upload(h, net.skel_w, &h->skel_w)) || (rc = upload(h, net.skel_b, &h->skel_b)) ||
+        (rc = upload(h, net.skel_scale, &h->skel_scale)) || (rc = upload(h, net.skel_shift, &h->skel_shift))) break;
+    if ((rc = upload_regressor(h, h->reg_k, net.reg_k))) break;
+    rc = upload_regressor(h, h->reg_u, net.reg_u);
   } while (0);
   if (rc) {
     g_create_error = h->err;
@@ -1297,7 +1007,7 @@ static int run_head(ut_handle h, const ut::HeadArgs& a, const float* skel, int n
   // 8 samples per CU and wave set), with calibrated scales only once the head has been calibrated
   const bool head_split = !h->latency_mode && (h->calibrating || h->scale_mode == UT_SPLIT_SCALE_DYNAMIC || h->head_calibrated) &&
                           (h->conv_arith == UT_CONV_SPLIT_F16_ALWAYS || (h->conv_arith == UT_CONV_SPLIT_F16 && S >= 4 * h->num_cu));
-  const int stride = head_split ? kRegSplitCh : reg.c;
+  const int stride = head_split ? ut::kRegSplitCh : reg.c;
   const int tid0 = mode == UT_MODE_KNOWN_SKELETON ? 25 : 29;
   unsigned* in_word = nullptr;
   if (head_split) {

@@ -1,7 +1,9 @@
-// Internal launch interface between the host orchestration (ut_api.cpp) and the gfx950 kernels.
+// Internal launch interface between the host orchestration (ut_api.hip; weights: ut_weights.cpp) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "ut_split_pack.h"   // pack_split_weights, split_weight_scale
 
 namespace ut {
 
@@ -85,8 +87,6 @@ hipError_t launch_conv_w4(const ConvLaunch& c, hipStream_t s);
 // 3x3 stride-1 64 -> 64 channels with the weights resident in registers, K split across the two waves of a SIMD (conv_c64k.hip)
 bool conv_c64k_applicable(const ConvLaunch& c);
 hipError_t launch_conv_c64k(const ConvLaunch& c, hipStream_t s);
-size_t pack_split_weights(const float* w, int cout_pad, int k_pad, float scale, uint16_t* out);
-float split_weight_scale(const float* w, size_t n);
 // One 32 -> 32 -> 32 channel BasicBlock (stride 1, no shortcut convolution) in one launch, split-fp16 arithmetic
 // (conv_block32.hip): out = relu(conv2(relu(conv1(in) + bias1)) + bias2 + in), BatchNorm folded into weights and biases.
 struct BlockLaunch {

@@ -249,7 +249,7 @@ def test_split_f16_per_channel_rescale_invariance(engine, split_engine, spread):
     """The split arithmetic keeps ONE power-of-two scale per activation tensor and one per weight tensor, so a channel far below
     its tensor's largest (a near-dead BatchNorm channel whose consumer weights compensate: the same fp32 function) would lose its
     second fp16 piece.  ut_create therefore brings every inner and trunk channel to a canonical power-of-two scale before packing
-    (exact; csrc/ut_api.hip::fold_backbone).  Here every inner AND trunk channel of the backbone is rescaled by its own random
+    (exact; csrc/ut_weights.cpp::fold_backbone).  Here every inner AND trunk channel of the backbone is rescaled by its own random
     2^k, k in [-spread, spread] (channel spread up to 2^48): the fp32 kernels give the same bits (powers of two commute with every
     rounding), the split kernels give the same bits as on the original network (both pack to the same tensors), and the
     reference's own goldens hold at the path's tolerances."""

@@ -502,7 +502,7 @@ def _parse_canonical(flat):
 @pytest.mark.parametrize("spread", [8, 24])
 def test_pack_time_channel_canonicalisation_is_exact_and_invariant(spread):
     """ut_create brings every inner and trunk channel of the backbone to a canonical power-of-two scale before packing
-    (csrc/ut_api.hip::fold_backbone; host only, so it is checked here without a GPU through ut_canonical_backbone_weights):
+    (csrc/ut_weights.cpp::fold_backbone; host only, so it is checked here without a GPU through ut_canonical_backbone_weights):
     (i) checkpoints that differ by per-channel powers of two - up to 2^48 between two channels of one tensor here - pack to the
     same tensors bit for bit, which is what makes the split-fp16 arithmetic (one scale per tensor) see the same network whatever
     a checkpoint's per-channel scales; (ii) the packed network is the checkpoint's function (torch CPU fp32 on the folded,
