@@ -666,7 +666,9 @@ class HipEngine:
         self._check(self.lib.ut_set_backbone_lanes(self._h, int(lanes)), "ut_set_backbone_lanes")
 
     def set_block_fusion(self, on: bool):
-        """Split-fp16 mode: layer1's BasicBlocks as one launch each (default) or as two convolution launches (A/B tests)."""
+        """Split-fp16 mode: layer1's BasicBlocks as one launch each (default) or as two convolution launches (A/B tests).  Both
+        arithmetics: the fp32 1x1 convolutions (layer4's shortcut, the projection, the head's two chains) as streaming
+        launches with the chains' intermediates in registers (default; same bits), or one conv_igemm launch per layer."""
         self._check(self.lib.ut_set_block_fusion(self._h, int(bool(on))), "ut_set_block_fusion")
 
     def set_resident_weights(self, kind=1):

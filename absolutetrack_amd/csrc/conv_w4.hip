@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
   const int fr = lane & 31, fh = lane >> 5;
 
   const int M = p.n_img * HW;
-  const int n_slices = p.cin / (S2 ? 16 : SCH);      // S2: 16-channel slices of nine k-steps
+  // S2: 16-channel slices of nine k-steps.  Stride 1: the slices behind k_cin hold zeros on both sides and are not walked
+  const int n_slices = (!S2 && p.k_cin > 0 ? p.k_cin : p.cin) / (S2 ? 16 : SCH);
   const int n_chunks = p.k_pad / 32;           // 9 per 32 input channels
 
   const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -591,6 +592,7 @@ bool conv_w4_applicable(const ConvLaunch& c) {
     return !(c.no_resident & 8) && c.cin >= 64 /* (what the tests cover: 64 and 128; two-slice tiles are untested) */ && c.cout_store % 128 == 0 && c.H == 2 * c.Ho && c.W == 2 * c.Wo && !c.res &&
            ((c.Wo == 12 && c.Ho == 12) || (c.Wo == 6 && c.Ho == 6));
   if (c.stride != 1 || c.cin < 64 || c.H != c.Ho || c.W != c.Wo) return false;
+  if (c.k_cin != 0 && (c.k_cin % 32 != 0 || c.k_cin < 64 || c.k_cin > c.cin)) return false;
   if (c.cout_store % 128 == 0) return (c.W == 12 && c.H == 12) || (c.W == 6 && c.H == 6);
   return !(c.no_resident & 4) && c.cout_store == 64 && c.W == 24 && c.H == 24;
 }

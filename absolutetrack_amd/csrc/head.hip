@@ -1,5 +1,6 @@
 // Glue kernels of the regression head (everything between the backbone and the pose record that
-// is not a convolution).  The 1x1 / 3x3 convolutions of the head run on conv_igemm.hip.
+// is not a convolution).  The head's 1x1 chains run on conv_pw.hip (or layer by layer on conv_igemm.hip), its 3x3 convolutions
+// on conv_igemm.hip / conv_w4.hip.
 // Feature maps are 6x6; in the workspace they are NHWC [S,36,C].
 //
 //  ftl_in_kernel              lib/models/model_utils.py:57-104,166-192, lib/models/feature_extractor.py:61-94,96-129
@@ -43,11 +44,25 @@ __global__ __launch_bounds__(256) void validate_desc_kernel(HeadArgs a) {
 // One workgroup per sample.  Two-view samples: both views are moved to the canonical space with
 // A_v = S_0^-1 X_0 X_v^-1 S_v and written side by side (144 channels).  One-view samples: FTL
 // with S_v only, written straight to the fused buffer (the fusion convs are skipped for them).
+// STAGED (the product form; ut_set_block_fusion(h, 0) selects the other, which the tests compare it with bit for bit): the
+// features are NCHW, so consecutive threads take consecutive PIXELS (coalesced reads), and the outputs are NHWC, where those are
+// 576 (288) bytes apart - the sample's values go through LDS and leave with consecutive threads on consecutive channels.  Rows
+// of 145 (73) floats: a wave's 32 pixels of one channel on 32 banks.  !STAGED: every thread stores its three values where they
+// belong.  One expression per element in both forms (ftl_rows).
+__device__ __forceinline__ void ftl_rows(const float* m, float x, float y, float z, float* o, int c) {
+  o[c] = m[0] * x + m[1] * y + m[2] * z + m[3];
+  o[24 + c] = m[4] * x + m[5] * y + m[6] * z + m[7];
+  o[48 + c] = m[8] * x + m[9] * y + m[10] * z + m[11];
+}
+template <bool STAGED>
 __global__ __launch_bounds__(256) void ftl_in_kernel(HeadArgs a, HeadBuffers b) {
   UT_RETURN_IF_INVALID(a);
   const int s = blockIdx.x;
   const int r0 = (int)a.sample_range[2 * s], r1 = (int)a.sample_range[2 * s + 1];
   const int nv = r1 - r0;
+  // xf and tile below hold two views.  A range of another size has been flagged by validate_desc_kernel, which runs first, and
+  // the check above then returns; this guard bounds the indices here whatever ran before: such a sample's rows stay unwritten.
+  if (nv < 1 || nv > 2) return;
   __shared__ float xf[2][12];
   if (threadIdx.x < nv) {
     const int v = threadIdx.x;
@@ -71,31 +86,29 @@ __global__ __launch_bounds__(256) void ftl_in_kernel(HeadArgs a, HeadBuffers b) 
       for (int j = 0; j < 4; ++j) xf[v][4 * i + j] = (float)out[4 * i + j];
   }
   __syncthreads();
+  constexpr int ROW2 = 2 * FC + 1, ROW1 = FC + 1;
+  __shared__ float tile[STAGED ? PIX * ROW2 : 1];
+  float* o144 = b.cat144 + (size_t)s * PIX * 144;
+  float* ofused = b.fused + (size_t)s * PIX * FC;
+  // where pixel p's first channel goes: the LDS tile, or the output itself
+  const int row = !STAGED ? (nv == 2 ? 144 : FC) : nv == 2 ? ROW2 : ROW1;
+  float* dst = STAGED ? tile : nv == 2 ? o144 : ofused;
   // 24 channel triples x 36 pixels per view
-  for (int it = threadIdx.x; it < 2 * 24 * PIX; it += 256) {
+  for (int it = threadIdx.x; it < nv * 24 * PIX; it += 256) {
     const int v = it / (24 * PIX);
     const int rem = it - v * 24 * PIX;
     const int c = rem / PIX, p = rem - c * PIX;
+    const float* f = a.feat + (size_t)(r0 + v) * FC * PIX;
+    ftl_rows(xf[v], f[c * PIX + p], f[(24 + c) * PIX + p], f[(48 + c) * PIX + p], dst + p * row + v * FC, c);
+  }
+  if (nv == 1)
+    for (int i = threadIdx.x; i < PIX * 144; i += 256) o144[i] = 0.f;   // keep the unused GEMM rows finite
+  if constexpr (STAGED) {
+    __syncthreads();
     if (nv == 2) {
-      const float* f = a.feat + (size_t)(r0 + v) * FC * PIX;
-      const float x = f[c * PIX + p], y = f[(24 + c) * PIX + p], z = f[(48 + c) * PIX + p];
-      const float* m = xf[v];
-      float* o = b.cat144 + ((size_t)s * PIX + p) * 144 + v * FC;
-      o[c] = m[0] * x + m[1] * y + m[2] * z + m[3];
-      o[24 + c] = m[4] * x + m[5] * y + m[6] * z + m[7];
-      o[48 + c] = m[8] * x + m[9] * y + m[10] * z + m[11];
+      for (int i = threadIdx.x; i < PIX * 144; i += 256) o144[i] = tile[(i / 144) * ROW2 + i % 144];
     } else {
-      float* o144 = b.cat144 + ((size_t)s * PIX + p) * 144 + v * FC;
-      o144[c] = 0.f; o144[24 + c] = 0.f; o144[48 + c] = 0.f;   // keep the unused GEMM rows finite
-      if (v == 0) {
-        const float* f = a.feat + (size_t)r0 * FC * PIX;
-        const float* m = xf[0];
-        const float x = f[c * PIX + p], y = f[(24 + c) * PIX + p], z = f[(48 + c) * PIX + p];
-        float* o = b.fused + ((size_t)s * PIX + p) * FC;
-        o[c] = m[0] * x + m[1] * y + m[2] * z + m[3];
-        o[24 + c] = m[4] * x + m[5] * y + m[6] * z + m[7];
-        o[48 + c] = m[8] * x + m[9] * y + m[10] * z + m[11];
-      }
+      for (int i = threadIdx.x; i < PIX * FC; i += 256) ofused[i] = tile[(i / FC) * ROW1 + i % FC];
     }
   }
 }
@@ -305,8 +318,9 @@ hipError_t launch_validate_desc(const HeadArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(validate_desc_kernel, dim3((a.n_samples + 255) / 256), dim3(256), 0, s, a);
   return hipGetLastError();
 }
-hipError_t launch_ftl_in(const HeadArgs& a, const HeadBuffers& b, hipStream_t s) {
-  hipLaunchKernelGGL(ftl_in_kernel, dim3(a.n_samples), dim3(256), 0, s, a, b);
+hipError_t launch_ftl_in(const HeadArgs& a, const HeadBuffers& b, bool staged, hipStream_t s) {
+  if (staged) hipLaunchKernelGGL(ftl_in_kernel<true>, dim3(a.n_samples), dim3(256), 0, s, a, b);
+  else hipLaunchKernelGGL(ftl_in_kernel<false>, dim3(a.n_samples), dim3(256), 0, s, a, b);
   return hipGetLastError();
 }
 hipError_t launch_ftl_out_temporal_in(const HeadArgs& a, const HeadBuffers& b, hipStream_t s) {

@@ -24,11 +24,13 @@ thread_local std::string g_create_error;
 
 struct ConvW : ut::ConvGeom {
   float* w = nullptr;     // device [cout_pad][k_pad]
+  float* w_frag = nullptr;   // device, only the 1x1 convolutions conv_pw.hip takes: the same matrix in its fragment order (PackedConv::wfrag)
   void* w_split = nullptr;   // device: the two fp16 planes of w * 2^k in fragment order (conv_split.hip), eligible layers only
   float split_unscale = 0.f; // 2^-k
   float wsum_rows = 0.f;     // max over output channels of sum_k |w| (folded), rounded up: bounds |conv(x)| by wsum_rows * max|x|
   float bias_max = 0.f;      // max |bias| (folded)
   float* bias = nullptr;  // device [cout_pad]
+  int k_cin = 0;          // > 0: input channels behind k_cin are zero padding in activations and weights (ConvLaunch::k_cin)
 };
 
 struct Block {
@@ -99,7 +101,8 @@ struct ut_context {
   bool head_calibrated = false;     // ... including the regressor's tensors (needs at least two calibration crops)
   bool calibrating = false;         // the running backbone call is a calibration pass: dynamic scales, maxima merged into calib
   unsigned word_gen = 0;            // bumped by every zeroing of the words: a max word kept across launches is stale after it
-  bool block_fusion = true;         // split-fp16 mode: layer1's BasicBlocks as one launch each (ut_set_block_fusion)
+  bool block_fusion = true;         // ut_set_block_fusion: split-fp16 mode - layer1's BasicBlocks and layer2's entry as one launch each, the
+                                    // regressor's zero K slice skipped; both arithmetics - the fp32 1x1 convolutions on conv_pw.hip (run_pw)
   int resident_weights = 1;         // split-fp16 mode (ut_set_resident_weights): 1 conv_w4 wherever it applies, 0 the chunked kernels, 2 .. 6 A/B mixes
   bool call_split = false;          // the running backbone call uses the split-fp16 kernels (decided once per call)
   // index checks: device status words ([0] sticky errors, [1] per call), their pinned host mirror, the duplicate-slot
@@ -239,17 +242,19 @@ int upload_conv(ut_handle h, ConvW& cw, const ut::PackedConv& pc) {
   static_cast<ut::ConvGeom&>(cw) = pc;
   cw.split_unscale = pc.split_unscale; cw.wsum_rows = pc.wsum_rows; cw.bias_max = pc.bias_max;
   int rc = upload(h, pc.wp, &cw.w);
+  if (!rc && !pc.wfrag.empty()) rc = upload(h, pc.wfrag, &cw.w_frag);
   if (!rc && !pc.planes.empty()) rc = upload_bytes(h, pc.planes.data(), pc.planes.size() * sizeof(uint16_t), &cw.w_split);
   return rc ? rc : upload(h, pc.bp, &cw.bias);
 }
 
-int upload_block(ut_handle h, Block& b, const ut::FoldedBlock& fb) {
+// pw_ds: the shortcut also in conv_pw.hip's fragment order (layer4's entry)
+int upload_block(ut_handle h, Block& b, const ut::FoldedBlock& fb, bool pw_ds = false) {
   int rc;
   const int cs = ut::round_up(fb.conv1.cout, 4);
   if ((rc = upload_conv(h, b.conv1, ut::pack_conv_host(fb.conv1, 3, fb.stride, cs)))) return rc;
   if ((rc = upload_conv(h, b.conv2, ut::pack_conv_host(fb.conv2, 3, 1, cs)))) return rc;
   b.has_ds = fb.has_ds;
-  if (fb.has_ds && (rc = upload_conv(h, b.ds, ut::pack_conv_host(fb.ds, 1, fb.stride, cs)))) return rc;
+  if (fb.has_ds && (rc = upload_conv(h, b.ds, ut::pack_conv_host(fb.ds, 1, fb.stride, cs, pw_ds)))) return rc;
   return UT_OK;
 }
 
@@ -258,6 +263,11 @@ int upload_regressor(ut_handle h, Regressor& r, const ut::FoldedRegressor& fr) {
   int rc;
   for (int i = 0; i < 2; ++i)
     if ((rc = upload_block(h, r.blocks[i], fr.blocks[i])) || (rc = upload_block(h, r.blocks_split[i], fr.wide[i]))) return rc;
+  // the wide form's real channels (76 or 72 of 128): its fourth 32-channel slice of K is zeros
+  for (int i = 0; i < 2; ++i) {
+    r.blocks_split[i].conv1.k_cin = ut::round_up(fr.blocks[i].conv1.cin, 32);
+    r.blocks_split[i].conv2.k_cin = ut::round_up(fr.blocks[i].conv2.cin, 32);
+  }
   if ((rc = upload(h, fr.w_out, &r.w_out))) return rc;
   return upload(h, fr.b_out, &r.b_out);
 }
@@ -410,6 +420,7 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
   c.Wo = (W + 2 * cw.pad - cw.ksize) / cw.stride + 1;
   c.cout_store = cw.cout_store; c.cout_pad = cw.cout_pad;
   c.k_total = cw.k_total; c.k_pad = cw.k_pad; c.cslice = cw.cslice;
+  c.k_cin = h->block_fusion && cw.k_cin < cw.cin_pad ? cw.k_cin : 0;     // (the switch off: every convolution walks its whole K)
   c.ksize = cw.ksize; c.stride = cw.stride; c.pad = cw.pad;
   c.relu = relu; c.out_nchw = nchw;
   c.device = h->device; c.num_cu = h->num_cu; { static const int kMask[7] = {15, 0, 14, 9, 12, 13, 8}; c.no_resident = kMask[h->resident_weights]; }      // (ut_kernels.h::ConvLaunch::no_resident)
@@ -460,6 +471,32 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
   return bracket_launch(h, s, kind ? in_tid : -1, in_max, cw.flops_per_pixel * (double)n_img * c.Ho * c.Wo, kind,
                         split ? "launch_conv_split" : "launch_conv_igemm",
                         [&] { return split ? ut::launch_conv_split(c, s) : ut::launch_conv_igemm(c, s); });
+}
+
+// 1x1 convolutions without residual, alone or as a chain whose intermediates nothing else reads, in one streaming launch
+// (conv_pw.hip): the bits of the same layers through run_conv, in either convolution arithmetic (these layers are fp32 in both).
+// Taken while the handle's fusion switch is on and outside latency mode (whose split-K path stays as it is); *done = false:
+// not taken, the caller launches the layers one by one.
+int run_pw(ut_handle h, std::initializer_list<const ConvW*> layers, std::initializer_list<bool> relus, const float* in, float* out,
+           int n_img, int H, int W, bool nchw, hipStream_t s, bool* done) {
+  *done = false;
+  if (!h->block_fusion || h->latency_mode) return UT_OK;
+  ut::PwLaunch c{};
+  double flops = 0;
+  const ConvW& first = **layers.begin();
+  c.in = in; c.out = out; c.n_img = n_img; c.H = H; c.W = W; c.cin = first.cin_pad; c.stride = first.stride;
+  c.Ho = (H - 1) / first.stride + 1; c.Wo = (W - 1) / first.stride + 1;
+  c.out_nchw = nchw; c.num_cu = h->num_cu;
+  auto relu = relus.begin();
+  for (const ConvW* cw : layers) {
+    if (cw->ksize != 1 || cw->pad != 0 || !cw->w_frag || (c.n_layers > 0 && cw->stride != 1)) return UT_OK;
+    c.layer[c.n_layers++] = ut::PwLayer{cw->w_frag, cw->bias, cw->k_pad, cw->cout_store, cw->cout_pad, *relu++ ? 1 : 0};
+    c.cout_store = cw->cout_store;
+    flops += cw->flops_per_pixel * (double)n_img * c.Ho * c.Wo;
+  }
+  if (!ut::conv_pw_applicable(c)) return UT_OK;
+  *done = true;
+  return bracket_launch(h, s, -1, nullptr, flops, 0, "launch_conv_pw", [&] { return ut::launch_conv_pw(c, s); });
 }
 
 // relu(bn2(conv2(relu(bn1(conv1 x)))) + (downsample(x) | x))   lib/models/backbone_resnet.py:56-72
@@ -528,7 +565,9 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
   const int Ho = (H + 2 - 3) / b.conv1.stride + 1, Wo = (W + 2 - 3) / b.conv1.stride + 1;
   const float* res = x;
   if (b.has_ds) {
-    if ((rc = run_conv(h, b.ds, x, nullptr, dsbuf, n_img, H, W, false, false, s))) return rc;
+    bool streamed = false;
+    if ((rc = run_pw(h, {&b.ds}, {false}, x, dsbuf, n_img, H, W, false, s, &streamed))) return rc;
+    if (!streamed && (rc = run_conv(h, b.ds, x, nullptr, dsbuf, n_img, H, W, false, false, s))) return rc;
     res = dsbuf;
   }
   return run_conv(h, b.conv2, tmp, res, y, n_img, Ho, Wo, true, false, s, tmp_max, y_max, mid_tid);
@@ -613,14 +652,14 @@ int ut_create(int device, const float* blob, size_t n_floats, ut_handle* out) {
       if (e2 != hipSuccess) { rc = fail(h, UT_E_HIP, "status words", e2); break; } }
     const ut::FoldedBackbone& fbb = net.backbone;
     if ((rc = upload(h, fbb.stem.w, &h->stem_w)) || (rc = upload(h, fbb.stem.b, &h->stem_b))) break;
-    for (int b = 0; b < 12 && !rc; ++b) rc = upload_block(h, h->bb[b], fbb.fb[b]);
+    for (int b = 0; b < 12 && !rc; ++b) rc = upload_block(h, h->bb[b], fbb.fb[b], b == 10);
     if (rc) break;
-    if ((rc = upload_conv(h, h->proj, ut::pack_conv_host(fbb.proj, 1, 1, 72)))) break;
-    if ((rc = upload_conv(h, h->fus0, ut::pack_conv_host(net.fusion[0], 1, 1, 108))) ||
-        (rc = upload_conv(h, h->fus1, ut::pack_conv_host(net.fusion[1], 1, 1, 72))) ||
-        (rc = upload_conv(h, h->fus2, ut::pack_conv_host(net.fusion[2], 1, 1, 72)))) break;
+    if ((rc = upload_conv(h, h->proj, ut::pack_conv_host(fbb.proj, 1, 1, 72, true)))) break;
+    if ((rc = upload_conv(h, h->fus0, ut::pack_conv_host(net.fusion[0], 1, 1, 108, true))) ||
+        (rc = upload_conv(h, h->fus1, ut::pack_conv_host(net.fusion[1], 1, 1, 72, true))) ||
+        (rc = upload_conv(h, h->fus2, ut::pack_conv_host(net.fusion[2], 1, 1, 72, true)))) break;
     // the temporal block's 90 channels live on a 92-channel padded layout
-    for (int i = 0; i < 3 && !rc; ++i) rc = upload_conv(h, h->tmp[i], ut::pack_conv_host(net.temporal[i], 1, 1, 92));
+    for (int i = 0; i < 3 && !rc; ++i) rc = upload_conv(h, h->tmp[i], ut::pack_conv_host(net.temporal[i], 1, 1, 92, true));
     if (rc) break;
     if ((rc = upload(h, net.skel_w, &h->skel_w)) || (rc = upload(h, net.skel_b, &h->skel_b)) ||
         (rc = upload(h, net.skel_scale, &h->skel_scale)) || (rc = upload(h, net.skel_shift, &h->skel_shift))) break;
@@ -760,6 +799,8 @@ static int backbone_pass(ut_handle h, const float* crops, const uint8_t* crops_u
     float* t = y; y = other; other = t;
   }
   // projection 256 -> 72, written NCHW like the reference (lib/models/model_utils.py:134)
+  bool streamed = false;
+  if ((rc = run_pw(h, {&h->proj}, {false}, x, feat + (size_t)c0 * 72 * 36, n, 6, 6, true, s, &streamed)) || streamed) return rc;
   return run_conv(h, h->proj, x, nullptr, feat + (size_t)c0 * 72 * 36, n, 6, 6, false, true, s);
 }
 
@@ -992,14 +1033,23 @@ static int run_head(ut_handle h, const ut::HeadArgs& a, const float* skel, int n
   const ut::HeadBuffers& b = h->hb;
   const int S = a.n_samples;
   h->call_split = false;             // fusion and temporal block: 1x1 convolutions, on the fp32 matrix instruction
-  HIPCHK(h, ut::launch_ftl_in(a, b, s));
-  if ((rc = run_conv(h, h->fus0, b.cat144, nullptr, b.f108, S, 6, 6, true, false, s))) return rc;
-  if ((rc = run_conv(h, h->fus1, b.f108, nullptr, b.f72a, S, 6, 6, true, false, s))) return rc;
-  if ((rc = run_conv(h, h->fus2, b.f72a, nullptr, b.f72b, S, 6, 6, false, false, s))) return rc;
+  HIPCHK(h, ut::launch_ftl_in(a, b, h->block_fusion, s));
+  // fusion and temporal chain: one streaming launch each, which leaves the intermediates of the layer-by-layer form (f108 and
+  // f72a; t92b and t92a in turn) unwritten
+  bool chained = false;
+  if ((rc = run_pw(h, {&h->fus0, &h->fus1, &h->fus2}, {true, true, false}, b.cat144, b.f72b, S, 6, 6, false, s, &chained))) return rc;
+  if (!chained) {
+    if ((rc = run_conv(h, h->fus0, b.cat144, nullptr, b.f108, S, 6, 6, true, false, s))) return rc;
+    if ((rc = run_conv(h, h->fus1, b.f108, nullptr, b.f72a, S, 6, 6, true, false, s))) return rc;
+    if ((rc = run_conv(h, h->fus2, b.f72a, nullptr, b.f72b, S, 6, 6, false, false, s))) return rc;
+  }
   HIPCHK(h, ut::launch_ftl_out_temporal_in(a, b, s));
-  if ((rc = run_conv(h, h->tmp[0], b.t92a, nullptr, b.t92b, S, 6, 6, true, false, s))) return rc;
-  if ((rc = run_conv(h, h->tmp[1], b.t92b, nullptr, b.t92a, S, 6, 6, true, false, s))) return rc;
-  if ((rc = run_conv(h, h->tmp[2], b.t92a, nullptr, b.t92b, S, 6, 6, false, false, s))) return rc;
+  if ((rc = run_pw(h, {&h->tmp[0], &h->tmp[1], &h->tmp[2]}, {true, true, false}, b.t92a, b.t92b, S, 6, 6, false, s, &chained))) return rc;
+  if (!chained) {
+    if ((rc = run_conv(h, h->tmp[0], b.t92a, nullptr, b.t92b, S, 6, 6, true, false, s))) return rc;
+    if ((rc = run_conv(h, h->tmp[1], b.t92b, nullptr, b.t92a, S, 6, 6, true, false, s))) return rc;
+    if ((rc = run_conv(h, h->tmp[2], b.t92a, nullptr, b.t92b, S, 6, 6, false, false, s))) return rc;
+  }
   const Regressor& reg = mode == UT_MODE_KNOWN_SKELETON ? h->reg_k : h->reg_u;
   if (mode == UT_MODE_KNOWN_SKELETON)
     HIPCHK(h, ut::launch_skeleton(skel, h->skel_w, h->skel_b, h->skel_scale, h->skel_shift, b.skel, n_skel, s));

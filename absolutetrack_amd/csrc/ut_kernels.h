@@ -36,6 +36,9 @@ struct ConvLaunch {
   int cout_store;      // channels written per pixel (== channel stride of out / res)
   int cout_pad;        // rows of Wp (multiple of 128)
   int k_total;         // taps * cin
+  int k_cin;           // conv_w4.hip, stride 1: input channels that K walks, a multiple of 32 in [64, cin] (0: cin).  Channels k_cin ..
+                       // cin - 1 of `in` and their weight columns hold zeros (the regressor's tensors, padded to the kernel's shape):
+                       // their products are exact zeros.  Strides, descriptors and the weight planes keep the padded sizes
   int cslice;          // channel slice width of the k order (32 or cin)
   int k_pad;           // row stride of Wp (multiple of 32)
   int ksize, stride, pad;
@@ -55,6 +58,28 @@ hipError_t launch_conv_igemm(const ConvLaunch& c, hipStream_t s);
 // latency mode: out = act(bias + res + sum of the split-K slabs, in slab order)
 hipError_t launch_splitk_finish(const float* slabs, int n_splits, int m, int cout_store, const float* bias,
                                 const float* res, float* out, int relu, hipStream_t s);
+// One to three chained 1x1 convolutions (the first may have a stride; no padding) on the fp32 matrix instruction, a wave per 32
+// output pixels, the intermediates of a chain in registers (conv_pw.hip): out = act_n(W_n ... act_0(W_0 in + b_0) ... + b_n),
+// the bits of the same layers as consecutive conv_igemm launches.  Layer l + 1's k_pad must be 32 * ceil(cout_store_l / 32).
+struct PwLayer {
+  const float* w;      // ConvLaunch::w in fragment order: [cout_pad / 32][k_pad / 8][64 lanes][4], lane (fr = lane & 31, fh = lane >> 5)
+                       // holding row 32 n + fr at k = 8 s + 4 fh .. + 3 (ut_weights.h::PackedConv::wfrag)
+  const float* bias;   // [cout_pad]
+  int k_pad, cout_store, cout_pad;
+  int relu;
+};
+struct PwLaunch {
+  const float* in;     // [n_img, H, W, cin]
+  float* out;          // last layer: NHWC [n_img, Ho, Wo, cout_store] or NCHW [n_img, cout_store, Ho*Wo] (single layer only)
+  PwLayer layer[3];
+  int n_layers;
+  int n_img, H, W, cin, Ho, Wo, stride;
+  int cout_store;      // of the last layer
+  int out_nchw;
+  int num_cu;          // compute units of the device (grid sizing)
+};
+bool conv_pw_applicable(const PwLaunch& c);      // one of the shapes conv_pw.hip instantiates
+hipError_t launch_conv_pw(const PwLaunch& c, hipStream_t s);
 // the same convolution on the fp16 matrix cores from two-piece splits of both operands (conv_split.hip)
 bool conv_split_applicable(const ConvLaunch& c);
 hipError_t launch_conv_split(const ConvLaunch& c, hipStream_t s);
@@ -254,7 +279,9 @@ struct HeadArgs {
 // One pass over the frame descriptors before anything indexes with them (stream ordered).
 hipError_t launch_validate_desc(const HeadArgs& a, hipStream_t s);
 
-hipError_t launch_ftl_in(const HeadArgs& a, const HeadBuffers& b, hipStream_t s);
+// staged: the sample's values leave through LDS with consecutive lanes on consecutive channels; else every lane stores its own
+// pixel's values 576 (288) bytes apart.  Same expression per element: same bits.
+hipError_t launch_ftl_in(const HeadArgs& a, const HeadBuffers& b, bool staged, hipStream_t s);
 hipError_t launch_ftl_out_temporal_in(const HeadArgs& a, const HeadBuffers& b, hipStream_t s);
 // regin [S,36,reg_stride]: channels reg_c .. reg_stride - 1 are zeroed; out_max (optional, zero before the launch): max |regin|
 hipError_t launch_temporal_out(const HeadArgs& a, const float* t_out /*[S,36,92]*/, const float* skel,

@@ -235,7 +235,7 @@ bool fold_network(const float* blob, size_t n, FoldedNetwork& out) {
 }
 
 // Pack folded weights to [cout_pad][k_pad] with k = slice*(taps*cslice) + tap*cslice + c (see ut_kernels.h).
-PackedConv pack_conv_host(const Folded& f, int ksize, int stride, int cout_store) {
+PackedConv pack_conv_host(const Folded& f, int ksize, int stride, int cout_store, bool pw_fragments) {
   PackedConv cw;
   const int cin = f.cin, cout = f.cout;
   cw.cin = cin; cw.cout = cout; cw.ksize = ksize; cw.stride = stride;
@@ -278,6 +278,19 @@ PackedConv pack_conv_host(const Folded& f, int ksize, int stride, int cout_store
     const float scale = split_weight_scale(wp.data(), wp.size());
     cw.split_unscale = 1.0f / scale;
     pack_split_weights(wp.data(), cw.cout_pad, cw.k_pad, scale, cw.planes.data());
+  }
+  // 1x1 convolutions that run on conv_pw.hip: the same matrix in the order conv_pw.hip's lanes consume it - [32-row block][8-wide k step][lane][4]
+  // with lane (fr = lane & 31, fh = lane >> 5) holding row 32 n + fr, k = 8 s + 4 fh .. + 3 -, so that a wave's fragment of a step
+  // is one contiguous kilobyte
+  if (pw_fragments && ksize == 1) {
+    cw.wfrag.resize(wp.size());
+    const int steps = cw.k_pad / 8;
+    for (int n = 0; n < cw.cout_pad / 32; ++n)
+      for (int st = 0; st < steps; ++st)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int c = 0; c < 4; ++c)
+            cw.wfrag[(((size_t)n * steps + st) * 64 + lane) * 4 + c] =
+                wp[(size_t)(32 * n + (lane & 31)) * cw.k_pad + 8 * st + 4 * (lane >> 5) + c];
   }
   return cw;
 }

@@ -63,12 +63,14 @@ struct ConvGeom {
 struct PackedConv : ConvGeom {
   std::vector<float> wp;          // [cout_pad][k_pad], k = slice*(taps*cslice) + tap*cslice + c (see ut_kernels.h)
   std::vector<float> bp;          // [cout_pad]
+  std::vector<float> wfrag;       // on request, 1x1 only: wp as [cout_pad / 32][k_pad / 8][64 lanes][4], conv_pw.hip's fragment order; else empty
   std::vector<uint16_t> planes;   // the two fp16 planes of wp * 2^k in fragment order (conv_split.hip); empty: not a split-fp16 layer
   float split_unscale = 0.f;      // 2^-k
   float wsum_rows = 0.f;          // max over output channels of sum_k |w| (folded), rounded up: bounds |conv(x)| by wsum_rows * max|x|
   float bias_max = 0.f;           // max |bias| (folded)
 };
 
-PackedConv pack_conv_host(const Folded& f, int ksize, int stride, int cout_store);
+// pw_fragments (1x1 only): also fill wfrag, for the convolutions that conv_pw.hip takes
+PackedConv pack_conv_host(const Folded& f, int ksize, int stride, int cout_store, bool pw_fragments = false);
 
 }  // namespace ut

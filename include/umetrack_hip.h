@@ -189,7 +189,15 @@ int ut_get_split_calibration(ut_handle h, float* out33);
  * (1 = default).  Same arithmetic; the intermediate's power-of-two scale comes from a bound instead of the measured maximum,
  * so the two forms agree to the split arithmetic's rounding (~1e-7 relative), not bit for bit.  The same switch covers layer2's
  * entry (csrc/conv_c32s2.hip: the block's stride-2 3x3 convolution and its 1x1 shortcut as one launch instead of a split-fp16 and
- * an fp32 launch; the shortcut then runs in the split arithmetic too).  0 is for A/B tests. */
+ * an fp32 launch; the shortcut then runs in the split arithmetic too).  0 is for A/B tests.
+ * In BOTH convolution arithmetics (not in latency mode) the switch also selects the streaming form of the fp32 1x1 convolutions
+ * (csrc/conv_pw.hip): the 1x1 shortcut of layer4 and the projection as one wave-per-32-pixels launch each, and the head's
+ * fusion chain (144 -> 108 -> 72 -> 72) and temporal chain (90 -> 90 x 3) as ONE launch each whose intermediates stay in
+ * registers.  These have the bits of the separate launches: same operands, same order, on the same matrix instruction.  With the
+ * switch on the split-fp16 regressor also skips the all-zero fourth 32-channel slice of its 128-channel padded K (0: walked; the
+ * dropped products are exact zeros), and ftl_in writes a sample's canonical-space features through LDS with consecutive lanes on
+ * consecutive channels (0: every lane stores its own pixel's values; same bits).  With 0 every convolution is its own launch over
+ * its whole K. */
 int ut_set_block_fusion(ut_handle h, int on);
 
 /* Split-fp16 mode only: which kernels take the 3x3 convolutions of layer2 .. layer4 (A/B switch for tests; 1 = default).

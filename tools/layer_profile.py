@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer view of a rocprofv3 --kernel-trace CSV of `bench.py` (known-skeleton mode):
-maps the convolution launches (conv_igemm / conv_split / halo patch) of the LAST step to the network's convolutions by launch order and
+maps the convolution launches (conv_igemm / conv_pw / conv_split / halo patch) of the LAST step to the network's convolutions by launch order and
 prints duration, FLOPs and TFLOP/s of each - and the launch's COMPULSORY bytes (input once, output once, the residual where there is one;
 fp32 tensors) over its duration: the HBM side of the same launch -, plus totals of every other kernel in that step.
     python tools/layer_profile.py <kernel_trace.csv> <n_crops> <chunk>"""
@@ -48,13 +48,18 @@ s = n_crops // 2
 head = [("fus0 144->108", 144 * 108, 144 + 108), ("fus1 108->72", 108 * 72, 108 + 72), ("fus2 72->72", 72 * 72, 72 + 72), ("tmp0 90->90", 8100, 180),
         ("tmp1 90->90", 8100, 180), ("tmp2 90->90", 8100, 180), ("reg0.conv1 76", 9 * 76 * 76, 2 * 76), ("reg0.conv2 76", 9 * 76 * 76, 3 * 76),
         ("reg1.conv1 76", 9 * 76 * 76, 2 * 76), ("reg1.conv2 76", 9 * 76 * 76, 3 * 76)]
+if any("conv_pw" in r["Kernel_Name"] for r in rows):               # the two 1x1 chains are one streaming launch each (conv_pw.hip)
+    head = [("fus0-2 144->108->72->72", sum(h[1] for h in head[:3]), 144 + 72), ("tmp0-2 90->90 x3", sum(h[1] for h in head[3:6]), 180)] + head[6:]
 seq += [(nm, 2 * mac * 36 * s, 4 * ch * 36 * s) for nm, mac, ch in head]
 
-is_conv = lambda r: any(k in r["Kernel_Name"] for k in ("conv_igemm", "conv3x3_c32_patch", "conv_split", "conv_block32", "conv_c64r", "conv_c64k", "conv_c32s2", "conv_w4"))
+is_conv = lambda r: any(k in r["Kernel_Name"] for k in ("conv_igemm", "conv_pw", "conv3x3_c32_patch", "conv_split", "conv_block32", "conv_c64r", "conv_c64k", "conv_c32s2", "conv_w4"))
 
 
 def label(name):
     args = name.split("<")[1].split(">")[0] if "<" in name else ""
+    if "conv_pw" in name:
+        a = args.split(", ")
+        return f"fp32 streaming 1x1, {sum(x != '0' for x in a[1:4])} layer(s)"
     if "conv_split" in name:
         return "split f16 " + "x".join(args.split(", ")[:2])
     if "conv_w4" in name:
