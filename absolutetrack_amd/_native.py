@@ -1,4 +1,4 @@
-"""ctypes binding of libumetrack_hip.so (include/umetrack_hip.h).
+"""ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension header include/umetrack_hip_fit.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, every entry point raises.  PyTorch-ROCm is used for device memory and
@@ -68,6 +68,13 @@ _PROTOTYPES = {
     "ut_profile_end_by_kind": (_i32, [_vp, _vp, _P(_f64), _P(ctypes.c_int64), _P(_f64)]),
 }
 EXPORTS = tuple(_PROTOTYPES)
+# The entries of the extension headers (include/umetrack_hip_fit.h): umetrack_hip.h's list is closed, later entries have a
+# header and a table of their own.  load_library() declares these as well.
+_EXTENSION_PROTOTYPES = {
+    "ut_fit_pose": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _vp, _i32, _vp, _i32,
+                           _vp, _vp]),
+}
+EXTENSION_EXPORTS = tuple(_EXTENSION_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -91,7 +98,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _PROTOTYPES.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -251,6 +258,67 @@ def fk_stateless(hand_model: torch.Tensor, joint_angles: torch.Tensor, wrist_xf:
     d = _hip_device(joint_angles, "fk_stateless")
     with torch.cuda.device(d):
         return _fk(load_library(), None, d, "stateless", hand_model, joint_angles, wrist_xf, mirror, t_scale)
+
+
+UT_FIT_CONVERGED, UT_FIT_AT_MAX_ITERS, UT_FIT_REFUSED = 1, 2, 4
+
+
+def fit_pose(hand_model: torch.Tensor, targets: torch.Tensor, weights: Optional[torch.Tensor] = None,
+             limits: Optional[torch.Tensor] = None, init_angles: Optional[torch.Tensor] = None,
+             init_wrist_xf: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+             max_iters: int = 32, *, n: Optional[int] = None, target_stride: int = 63, init_ja_stride: int = 22,
+             init_xf_stride: int = 16, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22,
+             xf_stride: int = 16, info: Optional[torch.Tensor] = None, engine: Optional["HipEngine"] = None):
+    """ut_fit_pose, the inverse of ut_fk: (joint_angles, wrist_xf, info [n,4]: weighted rms residual, worst residual,
+    iterations, status bits UT_FIT_*).  hand_model [1|n,321]; targets [n,21,3]; weights [n,21] or None; limits [1|n,20,2] (one
+    row per model row) or None; init_angles / init_wrist_xf [n,22] / [n,4,4], both or neither (cold start); mirror [n] or
+    None.  Packed tensors by default, outputs fresh [n,22] / [n,4,4].  With n given, targets / init_* / out are fp32 views
+    used in place with the strides given in floats - keypoints and poses inside record buffers, `out` may be the init's
+    own views.  All tensors on one HIP device; `engine` only lends its handle for error reporting."""
+    lib = load_library()
+    d = _hip_device(targets, "fit_pose")
+    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
+    if (init_angles is None) != (init_wrist_xf is None):
+        raise ValueError("init_angles and init_wrist_xf go together")
+    if n is None:
+        targets = _need(targets, torch.float32, d, "targets").reshape(-1, 63)
+        n = targets.shape[0]
+        if init_angles is not None:
+            init_angles = _need(init_angles, torch.float32, d, "init_angles").reshape(-1, 22)
+            init_wrist_xf = _need(init_wrist_xf, torch.float32, d, "init_wrist_xf").reshape(-1, 16)
+            if init_angles.shape[0] != n or init_wrist_xf.shape[0] != n:
+                raise ValueError("init_angles / init_wrist_xf batch mismatch")
+        if out is not None:
+            out = (_out(out[0], (n, 22), torch.float32, d, "out[0]"), _out(out[1], (n, 4, 4), torch.float32, d, "out[1]"))
+    else:
+        views = [targets] + ([] if init_angles is None else [init_angles, init_wrist_xf]) + list(out or ())
+        if out is None or any(v.device != d or v.dtype != torch.float32 for v in views):
+            raise ValueError(f"strided views must be fp32 on {d}, and `out` must be given with them")
+    if out is None:
+        out = (torch.empty(n, 22, dtype=torch.float32, device=d), torch.empty(n, 4, 4, dtype=torch.float32, device=d))
+    if hand_model.shape[0] not in (1, n) and n:
+        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
+    if weights is not None:
+        weights = _need(weights, torch.float32, d, "weights")
+        if tuple(weights.shape) != (n, 21):
+            raise ValueError(f"weights must be [{n},21], got {tuple(weights.shape)}")
+    if limits is not None:
+        limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
+        if limits.shape[0] != hand_model.shape[0]:
+            raise ValueError(f"limits has {limits.shape[0]} rows for {hand_model.shape[0]} model rows")
+    if mirror is not None:
+        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
+        if mirror.shape[0] != n:
+            raise ValueError("mirror batch mismatch")
+    info = _out(info, (n, 4), torch.float32, d, "info")
+    h = engine._h if engine is not None else None
+    with torch.cuda.device(d):
+        rc = lib.ut_fit_pose(h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights), _ptr(limits),
+                             _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror),
+                             ctypes.c_float(t_scale), int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride,
+                             _ptr(info), _stream(d))
+    _check_rc(lib, h, rc, "ut_fit_pose", "points")
+    return out[0], out[1], info
 
 
 class Mesh:

@@ -1,0 +1,434 @@
+// Batched inverse kinematics, fp32: the pose (20 joint angles + a rigid wrist) whose 21 landmarks - fk.hip's function,
+// lib/common/hand_skinning.py:189-209 - meet given targets.  The reference has no counterpart; the yardstick is the float64
+// restatement in tests/fit_cases.py, whose constants and decisions this file follows line by line.
+//
+// Levenberg-Marquardt on 26 parameters (20 angle increments, a wrist rotation about the weighted centroid of the targets,
+// a wrist translation) and 63 residual rows, Marquardt's diagonal scaling with a floor, Cholesky solve, a trial accepted
+// only when the weighted cost goes down.  ~60 kFLOP per iteration and pose: latency bound like fk.hip, not a matrix-core
+// shape.  One wave per pose, FIT_P poses per workgroup, every wave in an LDS region of its own: trip counts differ per pose,
+// so there is NO workgroup barrier anywhere in this file - waves order their own LDS traffic with wave_sync() - and a
+// pose's bits cannot depend on its neighbours.  Every loop bound and branch on solver state is wave uniform (reductions
+// are butterflies, which leave the same bits in every lane, and go through uniform()).
+//
+// Phases of one iteration (lanes of the pose's wave):
+//  (1) linearise, only after an accepted step: joint axes in the world from the prefix frames (20 lanes), Jacobian rows
+//      scaled by sqrt(weight) with the residual as column 26 (one lane per landmark, sparse: a landmark moves with the
+//      joints of the frames that carry it), J^T J and J^T r as one lower triangle of 27 x 27 dot products (6 per lane)
+//  (2) factor A + lambda D right-looking with one lane per row and the row in registers (fully unrolled, cross-lane values by
+//      v_readlane on constant lanes, no LDS); forward solve the same way, backward solve on the factor transposed through LDS
+//  (3) trial state (angles clamped to the optional box, wrist <- exp(dr) about the centroid, + dt) and its forward
+//      function: joint transforms (20 lanes), finger chains (5 lanes), landmark blend and residual (21 lanes) - the code
+//      of fk.hip (ut_fk.h), so the residual is ut_fk's arithmetic
+//  (4) accept / reject, lambda, convergence.
+#include <math.h>
+
+#include "ut_fk.h"
+#include "ut_kernels.h"
+#include "ut_math.h"
+
+namespace ut {
+
+constexpr int FIT_P = 4;         // poses (waves) per workgroup
+constexpr int FIT_LD = 27;       // row stride of J (26 columns + residual) and of the 27 x 27 normal matrix: odd, so that lanes
+                                 // reading one column of consecutive rows hit distinct banks
+constexpr int FIT_NP = 26;       // parameters
+constexpr float FIT_LAMBDA_START = 1e-3f, FIT_LAMBDA_DOWN = 0.1f, FIT_LAMBDA_UP = 10.f, FIT_LAMBDA_MIN = 1e-9f;
+constexpr float FIT_LAMBDA_CONVERGED_MAX = 1.f;   // a small step under heavy damping is a stall, not convergence
+constexpr float FIT_DIAG_FLOOR = 1e-10f;          // relative to the largest diagonal entry of J^T W J
+constexpr float FIT_STEP_TOL = 1e-5f;             // rad (angles, wrist rotation); x the targets' extent (translation)
+constexpr float FIT_DECREASE_TOL = 1e-3f;         // relative cost decrease of an accepted step
+constexpr float FIT_FLAT_TOL = 1e-6f;             // a rejected trial this close (relative) to the accepted cost: the cost is flat to
+                                                  // fp32 resolution across the step; a stalled fit is rejected by more
+enum : int { FIT_CONVERGED = 1, FIT_AT_MAX_ITERS = 2, FIT_REFUSED = 4 };
+
+struct FitLds {                  // one wave's region, 15064 bytes: FIT_P of them stay inside the 64 KB a workgroup gets
+  float hm[321];                 // the pose's packed model
+  float local[20][12];           // joint transforms of the last evaluated state
+  float prefix[20][12];          // W L0 .. L(j-1) in front of joint 4 f + j
+  float frame[17][12];           // skinning frames
+  float omega[20][3], cw[20][3]; // joint axes and centres in the world (linearisation)
+  float jl[63 * FIT_LD];         // J while the normal matrix is formed, then the Cholesky factor L [26][FIT_LD]
+  float a[27][FIT_LD];           // lower triangle of [J r]^T [J r]: A = J^T J, row 26 = g = J^T r
+  float ang[20], ang_t[20];      // accepted and trial angles
+  float wrist[12], wrist_t[12];  // accepted and trial wrist frame (translation in target units, column 0 negated if mirrored)
+  float p[21][3];                // landmarks of the last evaluated state
+  float target[21][3], w[21];    // targets (0 where the weight is 0) and weights
+};
+static_assert(sizeof(FitLds) == 15064 && sizeof(FitLds) * FIT_P <= 65536, "a workgroup's static LDS");
+
+// Orders this wave's LDS accesses: what lanes wrote before is visible to the lanes that read after.  No other wave of the
+// workgroup takes part.
+__device__ inline void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+__device__ inline float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ inline float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return uniform(v);
+}
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ inline float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return uniform(v);
+}
+__device__ inline bool wave_any(bool b) { return __any(b); }
+
+// The forward function of (ang, wrist) into S.local / prefix / frame / p: the weighted cost, and the largest residual of
+// a weighted landmark in `worst`.  Called by the whole wave.
+__device__ inline float fit_eval(FitLds& S, const float* ang, const float* wrist, int lane, float& worst) {
+  if (lane < 20) {
+    const M34 l = joint_local(S.hm + 3 * lane, S.hm + 66 + 3 * lane, ang[lane]);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) S.local[lane][k] = l.m[k];
+  }
+  wave_sync();
+  if (lane < 6) {
+    M34 w;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) w.m[k] = wrist[k];
+    if (lane < 5) {
+      finger_chain_with_prefixes(w, S.local, lane, S.prefix, S.frame);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) { S.frame[0][k] = w.m[k]; S.frame[1][k] = w.m[k]; }
+    }
+  }
+  wave_sync();
+  float d2 = 0.f, wl = 0.f;
+  if (lane < 21) {
+    float o[3];
+    blend_landmark(S.hm, lane, S.frame, o);
+    S.p[lane][0] = o[0]; S.p[lane][1] = o[1]; S.p[lane][2] = o[2];
+    wl = S.w[lane];
+    if (wl > 0.f) {
+      const float rx = o[0] - S.target[lane][0], ry = o[1] - S.target[lane][1], rz = o[2] - S.target[lane][2];
+      d2 = rx * rx + ry * ry + rz * rz;
+    }
+  }
+  wave_sync();
+  // a NaN must not hide behind fmaxf: the sum carries it
+  const float cost = wave_sum(wl * d2);
+  worst = sqrtf(wave_max(d2));
+  return cost;
+}
+
+// exp(hat(v)) without the clamp of so3_exp_map (the wrist increment is the solver's own, not the model's)
+__device__ inline void rodrigues(float vx, float vy, float vz, float* r) {
+  const float n2 = vx * vx + vy * vy + vz * vz;
+  float f1, f2;
+  if (n2 < 1e-8f) {
+    f1 = 1.f - n2 / 6.f; f2 = 0.5f - n2 / 24.f;
+  } else {
+    const float th = sqrtf(n2);
+    f1 = sinf(th) / th; f2 = (1.f - cosf(th)) / n2;
+  }
+  r[0] = 1.f - f2 * (vy * vy + vz * vz); r[1] = -f1 * vz + f2 * (vx * vy);     r[2] = f1 * vy + f2 * (vx * vz);
+  r[3] = f1 * vz + f2 * (vx * vy);       r[4] = 1.f - f2 * (vx * vx + vz * vz); r[5] = -f1 * vx + f2 * (vy * vz);
+  r[6] = -f1 * vy + f2 * (vx * vz);      r[7] = f1 * vx + f2 * (vy * vz);       r[8] = 1.f - f2 * (vx * vx + vy * vy);
+}
+
+// (1): J (rows scaled by sqrt(weight), residual in column 26) into S.jl, then the lower triangle of [J r]^T [J r] into S.a.
+// Needs S.prefix / frame / p of the accepted state.  sign: determinant of the wrist's linear part.
+__device__ inline void fit_linearise(FitLds& S, int lane, float sign, float cx, float cy, float cz) {
+  for (int e = lane; e < 63 * FIT_LD; e += 64) S.jl[e] = 0.f;
+  if (lane < 20) joint_axis_in_world(S.prefix[lane], S.hm + 3 * lane, S.hm + 66 + 3 * lane, S.omega[lane], S.cw[lane]);
+  wave_sync();
+  if (lane < 21 && S.w[lane] > 0.f) {
+    const float sw = sqrtf(S.w[lane]);
+    float* row = S.jl + 3 * lane * FIT_LD;      // rows 3 l, 3 l + 1, 3 l + 2
+    const float* lm = S.hm + 132 + 3 * lane;
+    const float* wts = S.hm + 195 + 3 * lane;
+    const float* idx = S.hm + 258 + 3 * lane;
+    for (int e = 0; e < 3; ++e) {
+      const float we = wts[e];
+      const int f = (int)idx[e];
+      // the dense weight of frame f is the LAST non-zero entry naming it (blend_landmark): earlier ones are dead
+      bool live = we != 0.f && f >= 2 && f < 17;
+      for (int e2 = e + 1; e2 < 3; ++e2) live = live && !(wts[e2] != 0.f && (int)idx[e2] == f);
+      if (!live) continue;
+      const int c = (f - 2) / 3, m = (f - 2) - 3 * c + 1;     // the frame after joints 0 .. m of finger c
+      const float* t = S.frame[f];
+      const float yx = t[0] * lm[0] + t[1] * lm[1] + t[2] * lm[2] + t[3];
+      const float yy = t[4] * lm[0] + t[5] * lm[1] + t[6] * lm[2] + t[7];
+      const float yz = t[8] * lm[0] + t[9] * lm[1] + t[10] * lm[2] + t[11];
+      const float scale = sw * sign * we;
+      for (int j = 0; j <= m; ++j) {
+        const int k = 4 * c + j;
+        const float vx = yx - S.cw[k][0], vy = yy - S.cw[k][1], vz = yz - S.cw[k][2];
+        const float ox = S.omega[k][0], oy = S.omega[k][1], oz = S.omega[k][2];
+        row[k] += scale * (oy * vz - oz * vy);
+        row[FIT_LD + k] += scale * (oz * vx - ox * vz);
+        row[2 * FIT_LD + k] += scale * (ox * vy - oy * vx);
+      }
+    }
+    const float px = S.p[lane][0], py = S.p[lane][1], pz = S.p[lane][2];
+    const float vx = px - cx, vy = py - cy, vz = pz - cz;
+    // wrist rotation about the centroid: -hat(v); translation: I
+    row[21] = sw * vz;            row[22] = -sw * vy;
+    row[FIT_LD + 20] = -sw * vz;  row[FIT_LD + 22] = sw * vx;
+    row[2 * FIT_LD + 20] = sw * vy; row[2 * FIT_LD + 21] = -sw * vx;
+    row[23] = sw; row[FIT_LD + 24] = sw; row[2 * FIT_LD + 25] = sw;
+    row[26] = sw * (px - S.target[lane][0]);
+    row[FIT_LD + 26] = sw * (py - S.target[lane][1]);
+    row[2 * FIT_LD + 26] = sw * (pz - S.target[lane][2]);
+  }
+  wave_sync();
+  // 27 * 28 / 2 = 378 entries (i, j <= i), 6 per lane
+  for (int e = lane; e < 378; e += 64) {
+    int i = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
+    if (i * (i + 1) / 2 > e) --i;
+    if ((i + 1) * (i + 2) / 2 <= e) ++i;
+    const int j = e - i * (i + 1) / 2;
+    float s = 0.f;
+#pragma unroll 9
+    for (int r = 0; r < 63; ++r) s = fmaf(S.jl[r * FIT_LD + i], S.jl[r * FIT_LD + j], s);
+    S.a[i][j] = s;
+  }
+  wave_sync();
+}
+
+// (2): delta = -(A + lambda D)^-1 g on lane i < 26 (0 on the others); false when a pivot is not positive and finite or the
+// solution is not finite.  diag: D_i on lane i.  Lane i keeps row i of the matrix in registers: every loop below is fully
+// unrolled, so the row is indexed statically and a value of another lane is a v_readlane on a constant lane - the
+// right-looking factorisation and the forward solve touch no LDS at all.  The backward solve needs column i on lane i: the
+// factor goes through S.jl once (J is dead by then) and comes back transposed.
+__device__ inline float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+__device__ inline bool fit_solve(FitLds& S, int lane, float lambda, float diag, float& delta) {
+  const bool row = lane < FIT_NP;
+  float a[FIT_NP], inv_d[FIT_NP];
+#pragma unroll
+  for (int k = 0; k < FIT_NP; ++k) a[k] = (row && k <= lane) ? S.a[row ? lane : 0][k] + (k == lane ? lambda * diag : 0.f) : 0.f;
+#pragma unroll
+  for (int j = 0; j < FIT_NP; ++j) {
+    const float piv = lane_value(a[j], j);
+    if (!(piv > 0.f) || !(piv <= 3.0e38f)) return false;
+    inv_d[j] = 1.f / sqrtf(piv);
+    a[j] *= inv_d[j];                                 // L_ij on lanes i >= j (sqrt(piv) on lane j); unused above the diagonal
+#pragma unroll
+    for (int k = j + 1; k < FIT_NP; ++k) a[k] = fmaf(-a[j], lane_value(a[j], k), a[k]);      // A_ik -= L_ij L_kj, used for i >= k
+  }
+  float b = row ? -S.a[26][row ? lane : 0] : 0.f;
+#pragma unroll
+  for (int j = 0; j < FIT_NP; ++j) {                 // L y = -g
+    const float y = lane_value(b, j) * inv_d[j];
+    if (lane == j) b = y;
+    else if (row && lane > j) b = fmaf(-a[j], y, b);
+  }
+  float* L = S.jl;
+#pragma unroll
+  for (int k = 0; k < FIT_NP; ++k)
+    if (row && k <= lane) L[lane * FIT_LD + k] = a[k];
+  wave_sync();
+  float c[FIT_NP];                                    // c[j] = L_j,lane: column `lane` of the factor
+#pragma unroll
+  for (int j = 0; j < FIT_NP; ++j) c[j] = (row && j > lane) ? L[j * FIT_LD + lane] : 0.f;
+#pragma unroll
+  for (int j = FIT_NP - 1; j >= 0; --j) {            // L^T x = y
+    const float x = lane_value(b, j) * inv_d[j];
+    if (lane == j) b = x;
+    else if (lane < j) b = fmaf(-c[j], x, b);
+  }
+  wave_sync();                                        // the factor is read before anybody reuses S.jl
+  delta = b;
+  return !wave_any(!(fabsf(b) <= 3.0e38f));
+}
+
+__global__ __launch_bounds__(64 * FIT_P) void fit_pose_kernel(const FitArgs a) {
+  __shared__ FitLds s_all[FIT_P];
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * FIT_P + (threadIdx.x >> 6);
+  if (i >= a.n) return;                               // whole waves leave; nobody waits for them
+  FitLds& S = s_all[threadIdx.x >> 6];
+  const int mrow = a.n_models == 1 ? 0 : i;
+  const bool warm = a.init_ja != nullptr;
+  const bool mirrored = a.mirror && a.mirror[i] == 1;
+  const float sign = mirrored ? -1.f : 1.f;
+
+  // ---- inputs: the model, the targets of weighted landmarks (others are never read), the box, the start
+  for (int e = lane; e < 321; e += 64) S.hm[e] = a.hand_model[(size_t)mrow * 321 + e];
+  float wl = 0.f;
+  bool bad = false;
+  if (lane < 21) {
+    wl = a.weights ? a.weights[(size_t)i * 21 + lane] : 1.f;
+    bad = !(wl >= 0.f) || !(wl <= 3.0e38f);
+    float tx = 0.f, ty = 0.f, tz = 0.f;
+    if (!bad && wl > 0.f) {
+      const float* t = a.targets + (size_t)i * a.target_stride + 3 * lane;
+      tx = t[0]; ty = t[1]; tz = t[2];
+      bad = !(fabsf(tx) <= 3.0e38f) || !(fabsf(ty) <= 3.0e38f) || !(fabsf(tz) <= 3.0e38f);
+    }
+    if (bad) wl = 0.f;
+    S.w[lane] = wl;
+    S.target[lane][0] = tx; S.target[lane][1] = ty; S.target[lane][2] = tz;
+  }
+  const bool boxed = a.limits != nullptr;
+  float lo = 0.f, hi = 0.f, ang0 = 0.f;
+  if (lane < 20) {
+    if (boxed) { lo = a.limits[(size_t)mrow * 40 + 2 * lane]; hi = a.limits[(size_t)mrow * 40 + 2 * lane + 1]; }
+    if (warm) ang0 = a.init_ja[(size_t)i * a.init_ja_stride + lane];
+    if (boxed) ang0 = fminf(fmaxf(ang0, lo), hi);
+    S.ang[lane] = ang0;
+  }
+  float tail = 0.f;                                   // angles 20, 21 do not enter the skinning: copied through
+  if (warm && (lane == 20 || lane == 21)) tail = a.init_ja[(size_t)i * a.init_ja_stride + lane];
+  float init_w = 0.f;                                 // lanes 0..11: the start's wrist rows as given
+  if (lane < 12) {
+    init_w = warm ? a.init_xf[(size_t)i * a.init_xf_stride + lane] : ((lane == 0 || lane == 5 || lane == 10) ? 1.f : 0.f);
+    float v = init_w;
+    if ((lane & 3) == 3) v *= a.t_scale;
+    if ((lane & 3) == 0 && mirrored) v = -v;
+    S.wrist[lane] = v;
+  }
+  bool refused = wave_any(bad) || __popcll(__ballot(wl > 0.f)) < 3;
+  const float wsum = wave_sum(wl);
+  float cx = 0.f, cy = 0.f, cz = 0.f, extent = 0.f;
+  wave_sync();
+  if (!refused) {
+    const float tx = lane < 21 ? S.target[lane][0] : 0.f, ty = lane < 21 ? S.target[lane][1] : 0.f,
+                tz = lane < 21 ? S.target[lane][2] : 0.f;
+    cx = wave_sum(wl * tx) / wsum; cy = wave_sum(wl * ty) / wsum; cz = wave_sum(wl * tz) / wsum;
+    extent = sqrtf(wave_sum(wl * ((tx - cx) * (tx - cx) + (ty - cy) * (ty - cy) + (tz - cz) * (tz - cz))) / wsum);
+  }
+
+  float cost = 0.f, worst = 0.f;
+  bool keep_start = warm;                             // what a refused pose gives back
+  if (!refused && !warm) {
+    // ---- cold start: the rest pose (inside the box), aligned to the targets by a weighted Kabsch fit of its landmarks.
+    // H and the rotation in fp64 (ut_math.h), every lane the same values.
+    float unused;
+    fit_eval(S, S.ang, S.wrist, lane, unused);
+    const double w = wl, inv = 1.0 / (double)wsum;
+    const double qx = lane < 21 ? S.p[lane][0] : 0.0, qy = lane < 21 ? S.p[lane][1] : 0.0, qz = lane < 21 ? S.p[lane][2] : 0.0;
+    const double mx = wave_sum(w * qx) * inv, my = wave_sum(w * qy) * inv, mz = wave_sum(w * qz) * inv;
+    const double dx = lane < 21 ? S.target[lane][0] - (double)cx : 0.0, dy = lane < 21 ? S.target[lane][1] - (double)cy : 0.0,
+                 dz = lane < 21 ? S.target[lane][2] - (double)cz : 0.0;
+    double h[3][3], r[3][3];
+    h[0][0] = wave_sum(w * (qx - mx) * dx); h[0][1] = wave_sum(w * (qx - mx) * dy); h[0][2] = wave_sum(w * (qx - mx) * dz);
+    h[1][0] = wave_sum(w * (qy - my) * dx); h[1][1] = wave_sum(w * (qy - my) * dy); h[1][2] = wave_sum(w * (qy - my) * dz);
+    h[2][0] = wave_sum(w * (qz - mz) * dx); h[2][1] = wave_sum(w * (qz - mz) * dy); h[2][2] = wave_sum(w * (qz - mz) * dz);
+    kabsch_rotation(h, r);                            // target ~ r (q - mean) + centroid
+    wave_sync();
+    if (lane == 0) {
+      // q already carries the mirror: the frame is r diag(sign, 1, 1), and its translation takes the rest landmarks' mean there
+      const double t[3] = {cx - (r[0][0] * mx + r[0][1] * my + r[0][2] * mz), cy - (r[1][0] * mx + r[1][1] * my + r[1][2] * mz),
+                           cz - (r[2][0] * mx + r[2][1] * my + r[2][2] * mz)};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        S.wrist[4 * k] = (float)r[k][0] * sign; S.wrist[4 * k + 1] = (float)r[k][1]; S.wrist[4 * k + 2] = (float)r[k][2];
+        S.wrist[4 * k + 3] = (float)t[k];
+      }
+    }
+    wave_sync();
+  }
+  if (!refused) {
+    cost = fit_eval(S, S.ang, S.wrist, lane, worst);
+    if (!(cost <= 3.0e38f)) { refused = true; keep_start = false; }      // a start that is not finite
+  }
+
+  int iters = 0, status = refused ? FIT_REFUSED : 0;
+  if (!refused) {
+    float lambda = FIT_LAMBDA_START, diag = 0.f;
+    bool fresh = true, done = false;
+    for (; iters < a.max_iters && !done;) {
+      if (fresh) {
+        fit_linearise(S, lane, sign, cx, cy, cz);
+        const float d = lane < FIT_NP ? S.a[lane][lane] : 0.f;
+        diag = fmaxf(d, FIT_DIAG_FLOOR * wave_max(d));
+        fresh = false;
+      }
+      float delta = 0.f;
+      const bool ok = fit_solve(S, lane, lambda, diag, delta);
+      ++iters;
+      if (!ok) { lambda *= FIT_LAMBDA_UP; continue; }
+      // ---- trial state
+      float step = 0.f;
+      if (lane < 20) {
+        float t = S.ang[lane] + delta;
+        if (boxed) t = fminf(fmaxf(t, lo), hi);
+        S.ang_t[lane] = t;
+        step = fabsf(t - S.ang[lane]);
+      }
+      const float rx = lane_value(delta, 20), ry = lane_value(delta, 21), rz = lane_value(delta, 22);
+      const float ux = lane_value(delta, 23), uy = lane_value(delta, 24), uz = lane_value(delta, 25);
+      float e[9];
+      rodrigues(rx, ry, rz, e);
+      if (lane < 3) {                                 // row `lane` of [E R | E (t - c) + c + dt]
+        const float e0 = lane == 0 ? e[0] : (lane == 1 ? e[3] : e[6]), e1 = lane == 0 ? e[1] : (lane == 1 ? e[4] : e[7]),
+                    e2 = lane == 0 ? e[2] : (lane == 1 ? e[5] : e[8]);
+        const float* m = S.wrist;
+        S.wrist_t[4 * lane] = e0 * m[0] + e1 * m[4] + e2 * m[8];
+        S.wrist_t[4 * lane + 1] = e0 * m[1] + e1 * m[5] + e2 * m[9];
+        S.wrist_t[4 * lane + 2] = e0 * m[2] + e1 * m[6] + e2 * m[10];
+        const float cl = lane == 0 ? cx : (lane == 1 ? cy : cz), ul = lane == 0 ? ux : (lane == 1 ? uy : uz);
+        S.wrist_t[4 * lane + 3] = e0 * (m[3] - cx) + e1 * (m[7] - cy) + e2 * (m[11] - cz) + cl + ul;
+      }
+      const bool step_small = wave_max(step) <= FIT_STEP_TOL &&
+                              fmaxf(fabsf(rx), fmaxf(fabsf(ry), fabsf(rz))) <= FIT_STEP_TOL &&
+                              fmaxf(fabsf(ux), fmaxf(fabsf(uy), fabsf(uz))) <= FIT_STEP_TOL * extent;
+      wave_sync();
+      float worst_t;
+      const float cost_t = fit_eval(S, S.ang_t, S.wrist_t, lane, worst_t);
+      const bool accept = cost_t < cost;              // false for a NaN; +inf cannot be below a finite cost
+      const bool flat = !accept || cost - cost_t <= FIT_DECREASE_TOL * cost;
+      const bool stationary = !accept && fabsf(cost_t - cost) <= FIT_FLAT_TOL * cost;      // false for a NaN
+      done = (step_small && flat && lambda <= FIT_LAMBDA_CONVERGED_MAX) || stationary;
+      if (accept) {
+        if (lane < 20) S.ang[lane] = S.ang_t[lane];
+        if (lane < 12) S.wrist[lane] = S.wrist_t[lane];
+        cost = cost_t; worst = worst_t;
+        lambda = fmaxf(lambda * FIT_LAMBDA_DOWN, FIT_LAMBDA_MIN);
+        fresh = true;
+        wave_sync();
+      } else {
+        lambda *= FIT_LAMBDA_UP;
+      }
+    }
+    status = done ? FIT_CONVERGED : FIT_AT_MAX_ITERS;
+  }
+
+  // ---- outputs: a refused pose gives back its start - the rest pose at the identity on a cold start, and when the start
+  // itself is what was refused (its cost is not finite)
+  if (lane < 22) {
+    float v = refused && !keep_start ? 0.f : tail;
+    if (lane < 20) {
+      v = refused ? (keep_start ? a.init_ja[(size_t)i * a.init_ja_stride + lane] : 0.f) : S.ang[lane];
+      if (!refused && !boxed && fabsf(v) > 3.14159265358979f)
+        v -= 6.28318530717959f * ceilf((v - 3.14159265358979f) / 6.28318530717959f);      // into (-pi, pi]
+    }
+    a.ja[(size_t)i * a.ja_stride + lane] = v;
+  }
+  if (lane < 12) {
+    float v = keep_start ? init_w : ((lane == 0 || lane == 5 || lane == 10) ? 1.f : 0.f);
+    if (!refused) {
+      v = S.wrist[lane];
+      if ((lane & 3) == 3) v /= a.t_scale;
+      if ((lane & 3) == 0 && mirrored) v = -v;
+    }
+    a.xf[(size_t)i * a.xf_stride + lane] = v;
+  } else if (lane < 16 && a.xf_stride >= 16) {
+    a.xf[(size_t)i * a.xf_stride + lane] = lane == 15 ? 1.f : 0.f;
+  }
+  if (a.info && lane == 0) {
+    float* o = a.info + (size_t)i * 4;
+    o[0] = refused ? 0.f : sqrtf(cost / wsum);
+    o[1] = refused ? 0.f : worst;
+    o[2] = (float)iters;
+    o[3] = (float)status;
+  }
+}
+
+hipError_t launch_fit_pose(const FitArgs& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(fit_pose_kernel, dim3((a.n + FIT_P - 1) / FIT_P), dim3(64 * FIT_P), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace ut

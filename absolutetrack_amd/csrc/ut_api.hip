@@ -2,6 +2,7 @@
 // and the launch sequences of the hot path.  Host-only logic; kernels live in the other translation
 // units, weight folding and packing in ut_weights.cpp.
 #include "../../include/umetrack_hip.h"
+#include "../../include/umetrack_hip_fit.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -1161,6 +1162,27 @@ int ut_fk(ut_handle h, const float* hand_model, int n_models, const float* joint
   ON_DEVICE_IF(h);
   HIPCHK(h, ut::launch_fk(hand_model, n_models, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale, n, out,
                           (hipStream_t)stream));
+  return UT_OK;
+}
+
+int ut_fit_pose(ut_handle h, const float* hand_model, int n_models, const float* targets, int target_stride,
+                const float* weights, const float* limits, const float* init_angles, int init_ja_stride,
+                const float* init_wrist_xf, int init_xf_stride, const int64_t* mirror, float t_scale, int max_iters, int n,
+                float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride, float* info, void* stream) {
+  // stateless like ut_fk: h may be NULL
+  if (n == 0) return UT_OK;
+  if (!hand_model || !targets || !joint_angles || !wrist_xf || n < 0 || (n_models != 1 && n_models != n))
+    return fail(h, UT_E_INVALID, "ut_fit_pose: bad argument");
+  if ((init_angles == nullptr) != (init_wrist_xf == nullptr))
+    return fail(h, UT_E_INVALID, "ut_fit_pose: init_angles and init_wrist_xf must both be given or both be NULL");
+  if (target_stride < 63 || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
+    return fail(h, UT_E_INVALID, "ut_fit_pose: a stride is below 63 (targets) / 22 (angles) / 12 (wrist)");
+  if (max_iters < 1 || max_iters > 256) return fail(h, UT_E_INVALID, "ut_fit_pose: max_iters must be in 1..256");
+  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f)) return fail(h, UT_E_INVALID, "ut_fit_pose: t_scale must be positive and finite");
+  ON_DEVICE_IF(h);
+  const ut::FitArgs a{hand_model, n_models, targets, target_stride, weights, limits, init_angles, init_ja_stride, init_wrist_xf,
+                      init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride, info};
+  HIPCHK(h, ut::launch_fit_pose(a, (hipStream_t)stream));
   return UT_OK;
 }
 

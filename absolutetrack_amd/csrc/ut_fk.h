@@ -126,6 +126,40 @@ __device__ inline void skinning_frames_lds(float (&s_local)[P][20][12], float (&
   __syncthreads();
 }
 
+// What the pose fit (fit.hip) needs beyond the 17 frames: the chain of finger f as skinning_frames_lds multiplies it (same
+// products, same order, so the frames are the same bits), keeping the prefix frame in front of every joint as well -
+// prefix[4 f + j] = W L0 .. L(j-1), the frame joint j of the finger turns in - next to frame[2 + 3 f + (j - 1)] = W L0 .. Lj
+// for j >= 1.  local: the 20 joint transforms of the pose (joint_local), wrist: its wrist frame (slot 0).  One thread per
+// finger; the caller orders the LDS accesses around it.
+__device__ inline void finger_chain_with_prefixes(const M34& wrist, const float (&local)[20][12], int f,
+                                                  float (&prefix)[20][12], float (&frame)[17][12]) {
+  M34 t = wrist;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) prefix[4 * f + j][k] = t.m[k];
+    M34 l;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) l.m[k] = local[4 * f + j][k];
+    t = mul34(t, l);
+    if (j >= 1) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) frame[2 + 3 * f + (j - 1)][k] = t.m[k];
+    }
+  }
+}
+
+// Joint q in the world, from its prefix frame p (finger_chain_with_prefixes): omega = the frame's linear part times the
+// rotation axis, c_w = the frame applied to the joint's rest position.  d(T x)/d(angle q) = s * omega x (T x - c_w) for
+// every frame T whose product contains the joint, s = the determinant of the wrist's linear part.
+__device__ inline void joint_axis_in_world(const float* p, const float* axis, const float* rest, float* omega, float* c_w) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    omega[i] = p[4 * i] * axis[0] + p[4 * i + 1] * axis[1] + p[4 * i + 2] * axis[2];
+    c_w[i] = p[4 * i] * rest[0] + p[4 * i + 1] * rest[1] + p[4 * i + 2] * rest[2] + p[4 * i + 3];
+  }
+}
+
 // Landmark l of one pose into o[0..2]: linear blend skinning over the pose's 17 frames (in LDS, from skinning_frames_lds),
 // frames visited in ascending order like the dense reference sum.  hm: packed hand model (321 floats, see
 // include/umetrack_hip.h).

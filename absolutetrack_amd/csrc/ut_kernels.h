@@ -299,6 +299,23 @@ hipError_t launch_fk(const float* hand_model, int n_models, const float* ja, int
                      const float* xf, int xf_stride, const int64_t* mirror, float t_scale, int n,
                      float* out, hipStream_t s);
 
+// Poses from landmarks (fit.hip), the inverse of launch_fk: one wave per pose.  Pointers as ut_fit_pose documents them.
+struct FitArgs {
+  const float* hand_model; int n_models;
+  const float* targets; int target_stride;
+  const float* weights;                 // [n,21] or null
+  const float* limits;                  // [n_models,20,2] or null
+  const float* init_ja; int init_ja_stride;
+  const float* init_xf; int init_xf_stride;   // both init pointers null: cold start
+  const int64_t* mirror;
+  float t_scale;
+  int max_iters, n;
+  float* ja; int ja_stride;
+  float* xf; int xf_stride;
+  float* info;                          // [n,4] or null
+};
+hipError_t launch_fit_pose(const FitArgs& a, hipStream_t s);
+
 // Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
 //  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
 //           bone, unused slots weight 0 / bone 0

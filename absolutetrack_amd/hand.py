@@ -158,6 +158,44 @@ def skin_landmarks(hand_model: HandModel, joint_angles: torch.Tensor, wrist_tran
     return out.reshape(lead + (21, 3)).to(src_device)
 
 
+FIT_CONVERGED, FIT_AT_MAX_ITERS, FIT_REFUSED = _native.UT_FIT_CONVERGED, _native.UT_FIT_AT_MAX_ITERS, _native.UT_FIT_REFUSED
+
+
+def fit_landmarks(hand_model: HandModel, landmarks: torch.Tensor, weights: Optional[torch.Tensor] = None, init=None,
+                  limits: bool = False, mirror: Optional[torch.Tensor] = None, max_iters: int = 32):
+    """The inverse of skin_landmarks: [...,21,3] landmarks -> (joint_angles [...,22], wrist_transforms [...,4,4], info
+    [...,4]) with skin_landmarks(hand_model, joint_angles, wrist_transforms) ~ landmarks, on the HIP kernel csrc/fit.hip (no
+    CPU implementation; the reference has no such function).  Leading dims and devices as for skin_landmarks: the skeleton
+    fields are unbatched or carry the landmarks' leading dims, inputs on the CPU are moved to the GPU and the results come
+    back on the landmarks' device.  weights [...,21] >= 0: how much each landmark counts; the landmarks of weight 0 are
+    not read (they may be NaN).  init = (joint_angles [...,22], wrist_transforms [...,4,4]) warm-starts the fit, None
+    starts from the rest pose aligned to the landmarks.  limits=True keeps the angles inside hand_model.joint_limits
+    (fewer than half of the recorded label poses lie inside them, so this is off by default); otherwise angles come back
+    in (-pi, pi].  mirror [...] of 0 / 1 as for skin_mesh: where 1, the landmarks are those of a right hand and the
+    returned transform is the proper one a pose holds (column 0 is negated by the consumer).  info: weighted rms residual,
+    worst residual, iterations, status - FIT_CONVERGED | FIT_AT_MAX_ITERS | FIT_REFUSED (fewer than 3 weighted landmarks,
+    a bad weight or a non-finite weighted landmark: the pose is the init, or the rest pose)."""
+    lead = tuple(landmarks.shape[:-2])
+    n = int(np.prod(lead)) if lead else 1
+    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
+    if model_lead not in ((), lead):
+        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
+    if limits and hand_model.joint_limits is None:
+        raise ValueError("limits=True needs hand_model.joint_limits")
+    src_device = landmarks.device
+    dev = src_device if src_device.type == "cuda" else fk_device()
+
+    def dev32(t, tail):
+        return None if t is None else t.reshape((n,) + tail).to(dev, torch.float32)
+    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
+    ja, xf, info = _native.fit_pose(device_blob(hand_model, dev), dev32(landmarks, (21, 3)), dev32(weights, (21,)), box,
+                                    None if init is None else dev32(init[0], (22,)),
+                                    None if init is None else dev32(init[1], (4, 4)),
+                                    None if mirror is None else mirror.reshape(n).to(dev, torch.int64), max_iters=max_iters)
+    return (ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device),
+            info.reshape(lead + (4,)).to(src_device))
+
+
 _MESH_FIELDS = ("mesh_vertices", "mesh_triangles", "dense_bone_weights")
 _mesh_cache: list = []      # [(key, tensors kept alive, _native.Mesh)], most recent first
 

@@ -18,6 +18,7 @@ import torch
 from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
+from .hand import FIT_CONVERGED, fit_landmarks
 from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
 
@@ -70,6 +71,71 @@ def landmarks_from_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, h
     if hit is not None:
         return hit
     return skin_landmarks_np(hand_model, hand_pose.joint_angles, _left_handed(hand_pose.wrist_xform, hand_idx))
+
+
+def hand_pose_from_landmarks(hand_model: HandModel, landmarks: np.ndarray, hand_idx: int,
+                             init: Optional[SingleHandPose] = None) -> SingleHandPose:
+    """The pose whose world-space landmarks are `landmarks` [21,3] (mm): the inverse of landmarks_from_hand_pose, on the
+    HIP kernel csrc/fit.hip (hand.fit_landmarks).  The result goes straight into landmarks_from_hand_pose,
+    mesh_from_hand_pose, render_hand_pose and gen_crop_cameras: its wrist transform is the proper one, right hands are
+    mirrored by those consumers.  init: a pose to start from (e.g. last frame's); None starts from the rest pose aligned to
+    the landmarks.  hand_confidence is 1 when the fit converged and 0 when it stopped at its iteration limit or refused
+    the landmarks (not finite)."""
+    kp = torch.from_numpy(np.ascontiguousarray(landmarks, np.float32)).reshape(21, 3)
+    start = None if init is None else (torch.from_numpy(np.asarray(init.joint_angles, np.float32)),
+                                       torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
+    ja, xf, info = fit_landmarks(hand_model, kp, init=start, mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
+    return SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(),
+                          hand_confidence=1.0 if int(info[3]) & FIT_CONVERGED else 0.0)
+
+
+def hand_poses_from_keypoints(hand_model: HandModel, keypoints: np.ndarray, valid: np.ndarray
+                              ) -> List[Dict[int, SingleHandPose]]:
+    """Poses for a whole sequence of keypoints in the layout of the eval result files: keypoints [n_hands, n_frames, 21, 3]
+    (mm, world; hand 1 is the right hand), valid [n_hands, n_frames].  Returns one dict per frame, hand index ->
+    SingleHandPose, holding the hands that are valid in that frame.
+    A valid frame is warm-started from the latest earlier valid frame of the same hand and cold-started when there is
+    none, so frame t is fitted after frame t - 1; the hands of a frame share one launch per kind of start.  A warm start can
+    end in a local minimum when the hand moved far: a frame whose warm-started fit does not converge is fitted again from
+    the cold start, and the better of the two (lower residual) is kept."""
+    keypoints, valid = np.asarray(keypoints), np.asarray(valid, bool)
+    n_hands, n_frames = valid.shape
+    if keypoints.shape != (n_hands, n_frames, 21, 3):
+        raise ValueError(f"keypoints must be [{n_hands},{n_frames},21,3], got {keypoints.shape}")
+    dev = fk_device()
+    kp = torch.from_numpy(np.ascontiguousarray(keypoints, np.float32)).to(dev)
+    last: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+    out: List[Dict[int, SingleHandPose]] = []
+
+    def fit(hands, warm: bool):
+        start = (torch.stack([last[h][0] for h in hands]), torch.stack([last[h][1] for h in hands])) if warm else None
+        mirror = torch.tensor([1 if h == RIGHT_HAND_INDEX else 0 for h in hands], device=dev)
+        ja, xf, info = fit_landmarks(hand_model, kp[hands, t], init=start, mirror=mirror)
+        return ja, xf, info.cpu().numpy()
+
+    for t in range(n_frames):
+        found: Dict[int, Tuple[torch.Tensor, torch.Tensor, np.ndarray]] = {}
+        warm = [h for h in range(n_hands) if valid[h, t] and h in last]
+        cold = [h for h in range(n_hands) if valid[h, t] and h not in last]
+        if warm:
+            ja, xf, info = fit(warm, True)
+            for k, h in enumerate(warm):
+                found[h] = (ja[k], xf[k], info[k])
+                if not int(info[k, 3]) & FIT_CONVERGED:
+                    cold.append(h)
+        if cold:
+            ja, xf, info = fit(cold, False)
+            for k, h in enumerate(cold):
+                if h not in found or info[k, 0] < found[h][2][0]:
+                    found[h] = (ja[k], xf[k], info[k])
+        poses = {}
+        for h in sorted(found):
+            ja, xf, info = found[h]
+            last[h] = (ja, xf)
+            poses[h] = SingleHandPose(joint_angles=ja.cpu().numpy(), wrist_xform=xf.cpu().numpy(),
+                                      hand_confidence=1.0 if int(info[3]) & FIT_CONVERGED else 0.0)
+        out.append(poses)
+    return out
 
 
 def mesh_from_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, hand_idx: int, normals: bool = False):
