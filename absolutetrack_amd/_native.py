@@ -1,4 +1,5 @@
-"""ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension header include/umetrack_hip_fit.h).
+"""ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension headers include/umetrack_hip_fit.h and
+include/umetrack_hip_triangulate.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, every entry point raises.  PyTorch-ROCm is used for device memory and
@@ -75,6 +76,11 @@ _EXTENSION_PROTOTYPES = {
                            _vp, _vp]),
 }
 EXTENSION_EXPORTS = tuple(_EXTENSION_PROTOTYPES)
+# The entry of include/umetrack_hip_triangulate.h, in a table of its own like its header (tests/test_triangulate_host.py pins it).
+_TRIANGULATE_PROTOTYPES = {
+    "ut_triangulate_points": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+}
+TRIANGULATE_EXPORTS = tuple(_TRIANGULATE_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -98,7 +104,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -199,7 +205,7 @@ _ERROR_CLASSES = {
     # HipEngine methods: the reference asserts where the library says "unsupported" (umetrack_model.py:224-229), its tensor
     # indexing raises IndexError, and the split-fp16 backbone reports an infinity / a NaN among a layer's inputs
     "engine": (RuntimeError, AssertionError, {"index check:": IndexError, "range check:": FloatingPointError}),
-    "points": (ValueError, ValueError, {"index check:": IndexError}),        # project_points, render_mesh
+    "points": (ValueError, ValueError, {"index check:": IndexError}),        # project_points, render_mesh, triangulate_points
     "mesh": (ValueError, ValueError, {}),                                    # Mesh(...): the library refused the mesh
     "stateless": (RuntimeError, RuntimeError, {}),
 }
@@ -435,6 +441,63 @@ def project_points(points: torch.Tensor, cam_rows: torch.Tensor, table: torch.Te
                                    n, int(width), int(height), _ptr(window), _ptr(eye_z), _ptr(flags), _stream(d))
     _check_rc(lib, h, rc, "ut_project_points", "points")
     return window, eye_z, flags
+
+
+TRI_CONVERGED, TRI_AT_MAX_ITERS, TRI_REFUSED, TRI_DEGENERATE = 1, 2, 4, 8      # UT_TRI_*
+TRI_MAX_VIEWS = 8
+
+
+def triangulate_points(window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                       weights: Optional[torch.Tensor] = None, max_iters: int = 16,
+                       out: Optional[Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]] = None,
+                       engine: Optional["HipEngine"] = None, *, out_f32: Optional[torch.Tensor] = None,
+                       point_stride: Optional[int] = None):
+    """ut_triangulate_points, the inverse of project_points: window f64 [n,V,P,2] px (what project_points returns) ->
+    (points f64 [n,P,3], info f32 [n,P,4]: weighted rms reprojection residual px, sigma - model units per px of detection noise,
+    views used, status bits TRI_*, residual f32 [n,V,P] px per used view).  cam_rows i32 [n,V], -1 = unused view; table f64
+    [R,32] Fisheye62 source cameras or [R,24] pinhole crop cameras (told apart by the row length); weights f32 [n,V,P] >= 0 or
+    None = all 1 (a window of weight 0 is not read: it may be NaN); V <= TRI_MAX_VIEWS.  out: preallocated (points, info,
+    residual), any of them None.  out_f32 with point_stride: an fp32 view whose row i starts point_stride floats after row
+    i - 1 and begins with the pose's 3 P floats - keypoints inside records, written in place, or the targets of fit_pose; the
+    f64 result rounded once.  A cam_rows entry outside [-1, R) raises IndexError and writes nothing for its pose - at once,
+    or from engine.poll_status() when `engine` runs deferred checks (then nothing synchronises)."""
+    if window.dim() != 4 or window.shape[3] != 2 or window.dtype != torch.float64:
+        raise ValueError(f"window must be f64 [n,V,P,2], got {window.dtype} {tuple(window.shape)}")
+    n, v, n_points = window.shape[:3]
+    if not 1 <= v <= TRI_MAX_VIEWS or n_points < 1:
+        raise ValueError(f"window [n,V,P,2] needs 1 <= V <= {TRI_MAX_VIEWS} and P >= 1, got V = {v}, P = {n_points}")
+    if not 1 <= int(max_iters) <= 64:
+        raise ValueError(f"max_iters must be in 1..64, got {max_iters}")
+    if table.dim() != 2 or table.shape[1] not in (24, 32) or table.shape[0] < 1 or table.dtype != torch.float64:
+        raise ValueError(f"table must be f64 [R,32] source cameras or [R,24] crop cameras, got {table.dtype} {tuple(table.shape)}")
+    if cam_rows.dtype != torch.int32 or tuple(cam_rows.shape) != (n, v):
+        raise ValueError(f"cam_rows must be i32 [{n},{v}], got {cam_rows.dtype} {tuple(cam_rows.shape)}")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (n, v, n_points)):
+        raise ValueError(f"weights must be f32 [{n},{v},{n_points}], got {weights.dtype} {tuple(weights.shape)}")
+    if (out_f32 is None) != (point_stride is None):
+        raise ValueError("out_f32 and point_stride go together")
+    if out_f32 is not None and (out_f32.dtype != torch.float32 or point_stride < 3 * n_points
+                                or (n and out_f32.numel() and out_f32.stride(-1) != 1)):
+        raise ValueError(f"out_f32 must be an fp32 view with point_stride >= {3 * n_points}")
+    kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
+    lib = load_library()
+    d = _hip_device(window, "triangulate_points")
+    window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
+    if weights is not None:
+        weights = _need(weights, torch.float32, d, "weights")
+    if out_f32 is not None and out_f32.device != d:
+        raise ValueError(f"out_f32 must live on {d}")
+    points, info, residual = out if out is not None else (None, None, None)
+    points = _out(points, (n, n_points, 3), torch.float64, d, "out[0]")
+    info = _out(info, (n, n_points, 4), torch.float32, d, "out[1]")
+    residual = _out(residual, (n, v, n_points), torch.float32, d, "out[2]")
+    h = engine._h if engine is not None else None
+    with torch.cuda.device(d):
+        rc = lib.ut_triangulate_points(h, _ptr(window), _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind,
+                                       n_points, n, int(max_iters), _ptr(points), _ptr(out_f32), int(point_stride or 0),
+                                       _ptr(info), _ptr(residual), _stream(d))
+    _check_rc(lib, h, rc, "ut_triangulate_points", "points")
+    return points, info, residual
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

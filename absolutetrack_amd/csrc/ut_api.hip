@@ -3,6 +3,7 @@
 // units, weight folding and packing in ut_weights.cpp.
 #include "../../include/umetrack_hip.h"
 #include "../../include/umetrack_hip_fit.h"
+#include "../../include/umetrack_hip_triangulate.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -1355,6 +1356,42 @@ int ut_project_points(ut_handle h, const float* points, int point_stride, int n_
   g.n = n; g.width = width; g.height = height; g.window = window; g.eye_z = eye_z; g.flags = flags; g.status = st.dev;
   HIPCHK(h, ut::launch_project_points(g, s));
   return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, "ut_project_points") : UT_OK;
+}
+
+static_assert(UT_TRI_MAX_VIEWS == ut::TRI_MAX_VIEWS && UT_TRI_CONVERGED == ut::TRI_CONVERGED && UT_TRI_AT_MAX_ITERS == ut::TRI_AT_MAX_ITERS &&
+              UT_TRI_REFUSED == ut::TRI_REFUSED && UT_TRI_DEGENERATE == ut::TRI_DEGENERATE, "triangulation constants");
+
+int ut_triangulate_points(ut_handle h, const double* window, const float* weights, const int32_t* cam_rows, int max_views,
+                          const double* table, int n_rows, int table_kind, int n_points, int n, int max_iters,
+                          double* points, float* points_f32, int point_stride, float* info, float* residual, void* stream) {
+  if (!window || !cam_rows || !table) return fail(h, UT_E_INVALID, "ut_triangulate_points: null argument");
+  if (!points && !points_f32) return fail(h, UT_E_INVALID, "ut_triangulate_points: one of points and points_f32 must be given");
+  if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
+    return fail(h, UT_E_INVALID, "ut_triangulate_points: table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
+  if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS)
+    return fail(h, UT_E_INVALID, "ut_triangulate_points: max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
+  if (max_iters < 1 || max_iters > 64) return fail(h, UT_E_INVALID, "ut_triangulate_points: max_iters must be in 1..64");
+  if (n < 0 || n_points < 1 || n_rows < 1 || (points_f32 && point_stride < 3 * n_points))
+    return fail(h, UT_E_INVALID, "ut_triangulate_points: bad argument");
+  if (n == 0) return UT_OK;
+  if (h) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, window) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device != h->device)
+      return fail(h, UT_E_INVALID, "ut_triangulate_points: the windows live on another device than the handle");
+  }
+  StatusTarget st;
+  int rc = status_target(h, &st);
+  if (rc) return rc;
+  DeviceScope scope(st.device);
+  if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
+  hipStream_t s = (hipStream_t)stream;
+  ut::TriArgs g{};
+  g.window = window; g.weights = weights; g.cam_rows = cam_rows; g.max_views = max_views; g.table = table; g.n_rows = n_rows;
+  g.kind = table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE;
+  g.n_points = n_points; g.n = n; g.max_iters = max_iters; g.points = points; g.points_f32 = points_f32;
+  g.point_stride = point_stride; g.info = info; g.residual = residual; g.status = st.dev;
+  HIPCHK(h, ut::launch_triangulate(g, s));
+  return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, "ut_triangulate_points") : UT_OK;
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

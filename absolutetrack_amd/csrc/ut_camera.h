@@ -1,7 +1,8 @@
-// fp64 camera arithmetic shared by cropgen.hip (visibility gate) and render.hip (ut_project_points): world -> eye and the
-// forward Fisheye62 projection through a cam_params row (layout of ut_warp_crops).  Whether the compiler may contract
-// a * b + c follows the translation unit that includes this header: cropgen.hip keeps the default, render.hip turns
-// contraction off at file scope before the include so that every step rounds like numpy.
+// fp64 camera arithmetic shared by cropgen.hip (visibility gate, window keypoints), render.hip (ut_project_points) and
+// triangulate.hip (ut_triangulate_points): world -> eye, the forward Fisheye62 projection and the reference's unprojection
+// through a cam_params row (layout of ut_warp_crops).  Whether the compiler may contract a * b + c follows the translation
+// unit that includes this header: cropgen.hip keeps the default, render.hip and triangulate.hip turn contraction off at file
+// scope before the include so that every step rounds like numpy; window_to_world_d turns it off for itself.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,29 @@ __device__ inline void fisheye_project_d(const double* cam, const double* e, dou
   const double x2 = x * x, y2 = y * y, xy = x * y, rr = x2 + y2;
   win[0] = (x + (2 * p2 * xy + p1 * (rr + 2 * x2))) * cam[0] + cam[2];
   win[1] = (y + (2 * p1 * xy + p2 * (rr + 2 * y2))) * cam[1] + cam[3];
+}
+
+// window px -> world point through a cam_params row (Fisheye62CameraModel.window_to_eye, then eye_to_world)
+__device__ inline void window_to_world_d(const double* cam, const double* w, double* out) {
+#pragma clang fp contract(off)
+  const double qx = (w[0] - cam[2]) / cam[0], qy = (w[1] - cam[3]) / cam[1];
+  const double k1 = cam[4], k2 = cam[5], k3 = cam[6], k4 = cam[7], k5 = cam[10], k6 = cam[11];
+  double x = qx, y = qy;
+  for (int it = 0; it < 5; ++it) {          // camera.py:167-179
+    const double r2 = x * x + y * y;
+    const double rad = 1 + k1 * r2 + k2 * (r2 * r2) + k3 * pow(r2, 3.0) + k4 * pow(r2, 4.0) + k5 * pow(r2, 5.0) +
+                       k6 * pow(r2, 6.0);
+    x = qx / rad;
+    y = qy / rad;
+  }
+  const double r = sqrt(x * x + y * y);
+  const double xs = r / 3.141592653589793;                      // np.sinc(r / pi) = sin(y) / y, y = pi * x
+  const double ys = 3.141592653589793 * (xs == 0.0 ? 1.0e-20 : xs);
+  const double s = sin(ys) / ys;
+  const double e[3] = {x * s, y * s, cos(r)};
+  const double* rc = cam + 12;
+  const double* tc = cam + 21;
+  for (int i = 0; i < 3; ++i) out[i] = (rc[3 * i] * e[0] + rc[3 * i + 1] * e[1] + rc[3 * i + 2] * e[2]) + tc[i];
 }
 
 }  // namespace ut

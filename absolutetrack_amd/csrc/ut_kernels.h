@@ -348,6 +348,26 @@ struct ProjectArgs {
 };
 hipError_t launch_project_points(const ProjectArgs& g, hipStream_t s);
 
+// Window points back into the world (triangulate.hip), the inverse of launch_project_points: one thread per (pose, point).
+// Pointers as ut_triangulate_points documents them; kind is PROJECT_FISHEYE62 or PROJECT_PINHOLE.
+constexpr int TRI_MAX_VIEWS = 8;
+enum : int { TRI_CONVERGED = 1, TRI_AT_MAX_ITERS = 2, TRI_REFUSED = 4, TRI_DEGENERATE = 8 };
+struct TriArgs {
+  const double* window;         // [n,max_views,n_points,2]
+  const float* weights;         // [n,max_views,n_points] or null
+  const int32_t* cam_rows;      // [n,max_views] row of `table`, -1 = unused view
+  int max_views;
+  const double* table;          // [n_rows,32] or [n_rows,24]
+  int n_rows, kind, n_points, n, max_iters;
+  double* points;               // [n,n_points,3] or null
+  float* points_f32;            // [n] rows of point_stride floats, or null
+  int point_stride;
+  float* info;                  // [n,n_points,4] or null
+  float* residual;              // [n,max_views,n_points] or null
+  int* status;                  // sticky status word: UT_BAD_SRC_INDEX for a cam_rows entry outside [-1, n_rows)
+};
+hipError_t launch_triangulate(const TriArgs& a, hipStream_t s);
+
 // Posed meshes rasterised into 96x96 crop cameras (render.hip), one workgroup per (pose, view).
 //  tris int4 [nt]: (a, b, c, 0) per triangle.  The projected vertices of a pose (12 nv bytes, dynamic) share the workgroup's LDS
 //  with a 48 x 96 plane of 64-bit (depth, triangle) words (36864 bytes): RENDER_MAX_VERTICES is what fits the 64 KB a workgroup

@@ -211,6 +211,19 @@ def project_keypoints(points: torch.Tensor, cam_params: torch.Tensor, src_row: t
                                   point_stride=point_stride, n=n, engine=engine)
 
 
+def triangulate_keypoints(window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
+                          weights: Optional[torch.Tensor] = None, engine: Optional[_native.HipEngine] = None, max_iters: int = 16,
+                          out_f32: Optional[torch.Tensor] = None, point_stride: Optional[int] = None):
+    """Batched tracker.triangulate_landmarks, the inverse of project_keypoints: the window keypoints of n hand-samples in the
+    cameras that see them -> their world points, ONE ut_triangulate_points launch.  window f64 [n,V,P,2] px on the device
+    (what project_keypoints returns); cam_params f64 [R,32] (FrameBatch.cam_params) or [R,24] crop cameras; src_row i32
+    [n,V] rows of cam_params per view, -1 where unused; weights f32 [n,V,P] or None, e.g. (flags == 3).float() of
+    project_keypoints, or detection confidences.  out_f32 / point_stride: write the points as fp32 into records in place, e.g.
+    `records[:, POSE_REC:]` with point_stride=RECORD.  Returns (points f64 [n,P,3], info f32 [n,P,4], residual f32 [n,V,P])."""
+    return _native.triangulate_points(window, src_row, cam_params, weights=weights, max_iters=max_iters, engine=engine,
+                                      out_f32=out_f32, point_stride=point_stride)
+
+
 def view_rows(src_index: torch.Tensor, sample_range: torch.Tensor, max_views: int = MAX_VIEW_NUM) -> torch.Tensor:
     """[S,max_views] i32: the entries of a per-crop tensor (FrameBatch.src_index, or arange(n_crops) for the crop cameras
     themselves) that belong to each sample's views, -1 where the sample has fewer - the cam_rows of project_keypoints."""

@@ -187,6 +187,69 @@ def project_landmarks_host(cameras: List[CameraModel], landmarks_world: np.ndarr
     return np.stack([cam.eye_to_window(cam.world_to_eye(pts)) for cam in cameras]) if len(cameras) else np.zeros((0,) + pts.shape[:-1] + (2,))
 
 
+def _native_camera_table(cameras: List[CameraModel], who: str) -> np.ndarray:
+    """The cameras as rows of one kernel table: all Fisheye62, or all pinhole without distortion.  ValueError names any other
+    model (no host fallback)."""
+    kinds = {type(c) for c in cameras}
+    if len(cameras) == 0:
+        raise ValueError(f"{who}: no cameras")
+    if kinds != {geometry.Fisheye62CameraModel} and kinds != {PinholePlaneCameraModel}:
+        raise ValueError(f"{who}: cameras must all be Fisheye62CameraModel or all be PinholePlaneCameraModel, got "
+                         + ", ".join(sorted(k.__name__ for k in kinds)))
+    for c in cameras:
+        if isinstance(c, PinholePlaneCameraModel) and len(tuple(c.distort)) > 0:
+            raise ValueError(f"{who}: a PinholePlaneCameraModel with distortion coefficients is not served")
+    return np.stack([geometry.pack_camera_model(c) for c in cameras])
+
+
+def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weights: Optional[np.ndarray] = None
+                          ) -> Tuple[np.ndarray, np.ndarray]:
+    """The inverse of project_landmarks: window coordinates [n_cams,P,2] of P points in every camera -> (world points [P,3]
+    float64, info [P,4] float32: rms reprojection residual px, sigma - mm per px of detection noise -, views used, status
+    bits _native.TRI_*), one ut_triangulate_points launch (csrc/triangulate.hip).  weights [n_cams,P] >= 0: how much each
+    detection counts, 0 where the camera does not see the point (the window there is not read); None = all 1.  The cameras
+    must all be Fisheye62 or all be pinhole models without distortion: any other model raises ValueError naming it - there
+    is no host implementation."""
+    table = _native_camera_table(cameras, "triangulate_landmarks")
+    win = np.ascontiguousarray(window, np.float64)
+    if win.ndim != 3 or win.shape[0] != len(cameras) or win.shape[2] != 2:
+        raise ValueError(f"window must be [{len(cameras)},P,2], got {win.shape}")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float32)
+        if weights.shape != win.shape[:2]:
+            raise ValueError(f"weights must be {win.shape[:2]}, got {weights.shape}")
+    dev = fk_device()
+    rows = torch.arange(len(cameras), dtype=torch.int32, device=dev)[None]
+    pts, info, _ = _native.triangulate_points(torch.from_numpy(win)[None].to(dev), rows, torch.from_numpy(table).to(dev),
+                                              weights=None if weights is None else torch.from_numpy(weights)[None].to(dev))
+    return pts[0].cpu().numpy(), info[0].cpu().numpy()
+
+
+def hand_pose_from_window_keypoints(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray,
+                                    hand_idx: int, weights: Optional[np.ndarray] = None,
+                                    init: Optional[SingleHandPose] = None) -> Tuple[SingleHandPose, np.ndarray]:
+    """From 2-D detections to a pose: window_keypoints [n_cams,21,2] of one hand in the cameras -> (SingleHandPose, the
+    triangulation's info [21,4]).  triangulate_landmarks first, then the pose fit of hand_pose_from_landmarks with each
+    landmark weighted by (smallest finite sigma / its sigma)^2, in (0, 1]: a landmark the views pin down badly counts
+    less; refused and degenerate landmarks count 0.  weights [n_cams,21], init and hand_confidence as for
+    triangulate_landmarks / hand_pose_from_landmarks."""
+    pts, info = triangulate_landmarks(cameras, window_keypoints, weights)
+    if pts.shape[0] != 21:
+        raise ValueError(f"window_keypoints must be [{len(cameras)},21,2], got {np.shape(window_keypoints)}")
+    sigma = info[:, 1].astype(np.float64)
+    ok = np.isfinite(sigma) & (sigma > 0)
+    lw = np.zeros(21, np.float32)
+    if ok.any():
+        lw[ok] = (sigma[ok].min() / sigma[ok]) ** 2
+    start = None if init is None else (torch.from_numpy(np.asarray(init.joint_angles, np.float32)),
+                                       torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
+    ja, xf, fit_info = fit_landmarks(hand_model, torch.from_numpy(pts.astype(np.float32)), weights=torch.from_numpy(lw), init=start,
+                                     mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
+    pose = SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(),
+                          hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0)
+    return pose, info
+
+
 def _visible_counts(cameras: List[CameraModel], landmarks_world: np.ndarray) -> List[int]:
     counts = []
     for cam in cameras:
