@@ -1,5 +1,5 @@
-"""ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension headers include/umetrack_hip_fit.h and
-include/umetrack_hip_triangulate.h).
+"""ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension headers include/umetrack_hip_fit.h,
+include/umetrack_hip_triangulate.h and include/umetrack_hip_scale.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, every entry point raises.  PyTorch-ROCm is used for device memory and
@@ -81,6 +81,13 @@ _TRIANGULATE_PROTOTYPES = {
     "ut_triangulate_points": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
 }
 TRIANGULATE_EXPORTS = tuple(_TRIANGULATE_PROTOTYPES)
+# The entries of include/umetrack_hip_scale.h, in a table of their own like their header (tests/test_scale_host.py pins it).
+_SCALE_PROTOTYPES = {
+    "ut_fit_pose_scale": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _vp,
+                                 _i32, _vp, _i32, _vp, _vp, _vp]),
+    "ut_pool_scale": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+}
+SCALE_EXPORTS = tuple(_SCALE_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -104,7 +111,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -325,6 +332,95 @@ def fit_pose(hand_model: torch.Tensor, targets: torch.Tensor, weights: Optional[
                              _ptr(info), _stream(d))
     _check_rc(lib, h, rc, "ut_fit_pose", "points")
     return out[0], out[1], info
+
+
+UT_SCALE_FREE, UT_SCALE_FIXED = 0, 1
+UT_FITS_CONVERGED, UT_FITS_AT_MAX_ITERS, UT_FITS_REFUSED, UT_FITS_AT_BOUND = 1, 2, 4, 8
+UT_SCALE_MIN, UT_SCALE_MAX = 0.25, 4.0
+
+
+def fit_pose_scale(hand_model: torch.Tensor, targets: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                   limits: Optional[torch.Tensor] = None, init_scale: Optional[torch.Tensor] = None,
+                   scale_mode: int = UT_SCALE_FREE, init_angles: Optional[torch.Tensor] = None,
+                   init_wrist_xf: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                   max_iters: int = 32, *, n: Optional[int] = None, target_stride: int = 63, init_ja_stride: int = 22,
+                   init_xf_stride: int = 16, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22,
+                   xf_stride: int = 16, scale: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None,
+                   engine: Optional["HipEngine"] = None):
+    """ut_fit_pose_scale, fit_pose with the hand's scale as a parameter: (joint_angles, wrist_xf, scale [n], info [n,6]:
+    weighted rms residual, worst residual, iterations, status bits UT_FITS_*, scale information, 0).  init_scale [n] or None
+    (= 1); scale_mode UT_SCALE_FREE fits the scale, UT_SCALE_FIXED keeps init_scale.  Every other argument as for fit_pose,
+    strided views included; `scale` and `info` may be the caller's buffers."""
+    lib = load_library()
+    d = _hip_device(targets, "fit_pose_scale")
+    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
+    if (init_angles is None) != (init_wrist_xf is None):
+        raise ValueError("init_angles and init_wrist_xf go together")
+    if n is None:
+        targets = _need(targets, torch.float32, d, "targets").reshape(-1, 63)
+        n = targets.shape[0]
+        if init_angles is not None:
+            init_angles = _need(init_angles, torch.float32, d, "init_angles").reshape(-1, 22)
+            init_wrist_xf = _need(init_wrist_xf, torch.float32, d, "init_wrist_xf").reshape(-1, 16)
+            if init_angles.shape[0] != n or init_wrist_xf.shape[0] != n:
+                raise ValueError("init_angles / init_wrist_xf batch mismatch")
+        if out is not None:
+            out = (_out(out[0], (n, 22), torch.float32, d, "out[0]"), _out(out[1], (n, 4, 4), torch.float32, d, "out[1]"))
+    else:
+        views = [targets] + ([] if init_angles is None else [init_angles, init_wrist_xf]) + list(out or ())
+        if out is None or any(v.device != d or v.dtype != torch.float32 for v in views):
+            raise ValueError(f"strided views must be fp32 on {d}, and `out` must be given with them")
+    if out is None:
+        out = (torch.empty(n, 22, dtype=torch.float32, device=d), torch.empty(n, 4, 4, dtype=torch.float32, device=d))
+    if hand_model.shape[0] not in (1, n) and n:
+        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
+    if weights is not None:
+        weights = _need(weights, torch.float32, d, "weights")
+        if tuple(weights.shape) != (n, 21):
+            raise ValueError(f"weights must be [{n},21], got {tuple(weights.shape)}")
+    if limits is not None:
+        limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
+        if limits.shape[0] != hand_model.shape[0]:
+            raise ValueError(f"limits has {limits.shape[0]} rows for {hand_model.shape[0]} model rows")
+    if init_scale is not None:
+        init_scale = _need(init_scale, torch.float32, d, "init_scale").reshape(-1)
+        if init_scale.shape[0] != n:
+            raise ValueError("init_scale batch mismatch")
+    if mirror is not None:
+        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
+        if mirror.shape[0] != n:
+            raise ValueError("mirror batch mismatch")
+    scale = _out(scale, (n,), torch.float32, d, "scale")
+    info = _out(info, (n, 6), torch.float32, d, "info")
+    h = engine._h if engine is not None else None
+    with torch.cuda.device(d):
+        rc = lib.ut_fit_pose_scale(h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights),
+                                   _ptr(limits), _ptr(init_scale), int(scale_mode), _ptr(init_angles), init_ja_stride,
+                                   _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale), int(max_iters),
+                                   n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride, _ptr(scale), _ptr(info), _stream(d))
+    _check_rc(lib, h, rc, "ut_fit_pose_scale", "points")
+    return out[0], out[1], scale, info
+
+
+def pool_scale(scale: torch.Tensor, info: torch.Tensor, group_size: int, *, group: Optional[torch.Tensor] = None,
+               pose_scale: Optional[torch.Tensor] = None, broadcast: bool = True):
+    """ut_pool_scale on the outputs of a free fit_pose_scale: scale [G * group_size], info [G * group_size, 6] ->
+    (group [G,4]: pooled scale, sigma of ln scale per unit of target noise, scatter, poses used; pose_scale [G * group_size]:
+    the group's scale for each of its poses, or None with broadcast=False)."""
+    lib = load_library()
+    d = _hip_device(scale, "pool_scale")
+    scale = _need(scale, torch.float32, d, "scale").reshape(-1)
+    info = _need(info, torch.float32, d, "info").reshape(-1, 6)
+    if group_size < 1 or scale.shape[0] % group_size or info.shape[0] != scale.shape[0]:
+        raise ValueError(f"{scale.shape[0]} scales and {info.shape[0]} info rows do not make groups of {group_size}")
+    n_groups = scale.shape[0] // group_size
+    group = _out(group, (n_groups, 4), torch.float32, d, "group")
+    if broadcast or pose_scale is not None:
+        pose_scale = _out(pose_scale, (scale.shape[0],), torch.float32, d, "pose_scale")
+    with torch.cuda.device(d):
+        rc = lib.ut_pool_scale(None, _ptr(scale), _ptr(info), n_groups, int(group_size), _ptr(group), _ptr(pose_scale), _stream(d))
+    _check_rc(lib, None, rc, "ut_pool_scale", "points")
+    return group, pose_scale
 
 
 class Mesh:

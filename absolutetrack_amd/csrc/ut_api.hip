@@ -3,6 +3,7 @@
 // units, weight folding and packing in ut_weights.cpp.
 #include "../../include/umetrack_hip.h"
 #include "../../include/umetrack_hip_fit.h"
+#include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_triangulate.h"
 
 #include <math.h>
@@ -1184,6 +1185,46 @@ int ut_fit_pose(ut_handle h, const float* hand_model, int n_models, const float*
   const ut::FitArgs a{hand_model, n_models, targets, target_stride, weights, limits, init_angles, init_ja_stride, init_wrist_xf,
                       init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride, info};
   HIPCHK(h, ut::launch_fit_pose(a, (hipStream_t)stream));
+  return UT_OK;
+}
+
+static_assert(UT_SCALE_FREE == ut::FITS_MODE_FREE && UT_SCALE_FIXED == ut::FITS_MODE_FIXED && UT_SCALE_MIN == ut::FITS_SCALE_MIN &&
+              UT_SCALE_MAX == ut::FITS_SCALE_MAX && UT_SCALE_INFO_LAMBDA == ut::FITS_SCALE_INFO_LAMBDA &&
+              UT_FITS_CONVERGED == ut::FITS_CONVERGED && UT_FITS_AT_MAX_ITERS == ut::FITS_AT_MAX_ITERS &&
+              UT_FITS_REFUSED == ut::FITS_REFUSED && UT_FITS_AT_BOUND == ut::FITS_AT_BOUND, "umetrack_hip_scale.h and ut_kernels.h");
+
+int ut_fit_pose_scale(ut_handle h, const float* hand_model, int n_models, const float* targets, int target_stride,
+                      const float* weights, const float* limits, const float* init_scale, int scale_mode,
+                      const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
+                      const int64_t* mirror, float t_scale, int max_iters, int n, float* joint_angles, int ja_stride,
+                      float* wrist_xf, int xf_stride, float* scale, float* info, void* stream) {
+  // stateless like ut_fit_pose: h may be NULL
+  if (n == 0) return UT_OK;
+  if (!hand_model || !targets || !joint_angles || !wrist_xf || !scale || n < 0 || (n_models != 1 && n_models != n))
+    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: bad argument");
+  if (scale_mode != UT_SCALE_FREE && scale_mode != UT_SCALE_FIXED)
+    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED");
+  if ((init_angles == nullptr) != (init_wrist_xf == nullptr))
+    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: init_angles and init_wrist_xf must both be given or both be NULL");
+  if (target_stride < 63 || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
+    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: a stride is below 63 (targets) / 22 (angles) / 12 (wrist)");
+  if (max_iters < 1 || max_iters > 256) return fail(h, UT_E_INVALID, "ut_fit_pose_scale: max_iters must be in 1..256");
+  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f))
+    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: t_scale must be positive and finite");
+  ON_DEVICE_IF(h);
+  const ut::FitScaleArgs a{hand_model, n_models, targets, target_stride, weights, limits, init_scale, scale_mode, init_angles,
+                           init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride,
+                           wrist_xf, xf_stride, scale, info};
+  HIPCHK(h, ut::launch_fit_pose_scale(a, (hipStream_t)stream));
+  return UT_OK;
+}
+
+int ut_pool_scale(ut_handle h, const float* scale, const float* info, int n_groups, int group_size, float* group,
+                  float* pose_scale, void* stream) {
+  if (n_groups == 0) return UT_OK;
+  if (!scale || !info || !group || n_groups < 0 || group_size < 1) return fail(h, UT_E_INVALID, "ut_pool_scale: bad argument");
+  ON_DEVICE_IF(h);
+  HIPCHK(h, ut::launch_pool_scale(scale, info, n_groups, group_size, group, pose_scale, (hipStream_t)stream));
   return UT_OK;
 }
 

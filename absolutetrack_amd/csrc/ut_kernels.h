@@ -316,6 +316,33 @@ struct FitArgs {
 };
 hipError_t launch_fit_pose(const FitArgs& a, hipStream_t s);
 
+// Poses and the hand's scale from landmarks (fit_scale.hip): fit.hip's solver with ln(scale) as a 27th parameter, one wave per
+// pose, and the pool of per-pose scales, one wave per group.  Pointers as ut_fit_pose_scale / ut_pool_scale document them; the
+// constants are public as UT_SCALE_* / UT_FITS_*.
+constexpr int FITS_MODE_FREE = 0, FITS_MODE_FIXED = 1;
+constexpr float FITS_SCALE_MIN = 0.25f, FITS_SCALE_MAX = 4.0f, FITS_SCALE_INFO_LAMBDA = 1e-6f;
+enum : int { FITS_CONVERGED = 1, FITS_AT_MAX_ITERS = 2, FITS_REFUSED = 4, FITS_AT_BOUND = 8 };
+struct FitScaleArgs {
+  const float* hand_model; int n_models;
+  const float* targets; int target_stride;
+  const float* weights;                 // [n,21] or null
+  const float* limits;                  // [n_models,20,2] or null
+  const float* init_scale;              // [n] or null = 1
+  int scale_mode;
+  const float* init_ja; int init_ja_stride;
+  const float* init_xf; int init_xf_stride;   // both init pointers null: cold start
+  const int64_t* mirror;
+  float t_scale;
+  int max_iters, n;
+  float* ja; int ja_stride;
+  float* xf; int xf_stride;
+  float* scale;                         // [n]
+  float* info;                          // [n,6] or null
+};
+hipError_t launch_fit_pose_scale(const FitScaleArgs& a, hipStream_t s);
+hipError_t launch_pool_scale(const float* scale, const float* info, int n_groups, int group_size, float* group,
+                             float* pose_scale, hipStream_t s);
+
 // Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
 //  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
 //           bone, unused slots weight 0 / bone 0

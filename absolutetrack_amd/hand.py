@@ -196,6 +196,93 @@ def fit_landmarks(hand_model: HandModel, landmarks: torch.Tensor, weights: Optio
             info.reshape(lead + (4,)).to(src_device))
 
 
+FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FITS_CONVERGED, _native.UT_FITS_AT_MAX_ITERS,
+                                                                  _native.UT_FITS_REFUSED, _native.UT_FITS_AT_BOUND)
+
+
+def _scale_fit_inputs(hand_model: HandModel, landmarks, weights, init, init_scale, limits, mirror):
+    """What fit_landmarks_scale and calibrate_scale hand to _native.fit_pose_scale, flattened to n poses on the device."""
+    lead = tuple(landmarks.shape[:-2])
+    n = int(np.prod(lead)) if lead else 1
+    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
+    if model_lead not in ((), lead):
+        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
+    if limits and hand_model.joint_limits is None:
+        raise ValueError("limits=True needs hand_model.joint_limits")
+    src_device = landmarks.device
+    dev = src_device if src_device.type == "cuda" else fk_device()
+
+    def dev32(t, tail):
+        return None if t is None else torch.as_tensor(t).expand(lead + tail).reshape((n,) + tail).to(dev, torch.float32)
+    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
+    args = dict(hand_model=device_blob(hand_model, dev), targets=dev32(landmarks, (21, 3)), weights=dev32(weights, (21,)), limits=box,
+                init_scale=dev32(init_scale, ()), init_angles=None if init is None else dev32(init[0], (22,)),
+                init_wrist_xf=None if init is None else dev32(init[1], (4, 4)),
+                mirror=None if mirror is None else torch.as_tensor(mirror).expand(lead).reshape(n).to(dev, torch.int64))
+    return lead, src_device, args
+
+
+def fit_landmarks_scale(hand_model: HandModel, landmarks: torch.Tensor, weights: Optional[torch.Tensor] = None, init=None,
+                        init_scale=None, fixed: bool = False, limits: bool = False, mirror: Optional[torch.Tensor] = None,
+                        max_iters: int = 32):
+    """fit_landmarks with the hand's scale as a parameter, on the HIP kernel csrc/fit_scale.hip (no CPU implementation):
+    [...,21,3] landmarks -> (joint_angles [...,22], wrist_transforms [...,4,4], scale [...], info [...,6]) with
+    skin_landmarks(scaled_hand_model(hand_model, scale), joint_angles, wrist_transforms) ~ landmarks.  init_scale [...] (or a
+    number) is where the scale starts, 1 by default; fixed=True keeps it there, which fits the poses of a calibrated model
+    without building it.  info: weighted rms residual, worst residual, iterations, status - FITS_CONVERGED |
+    FITS_AT_MAX_ITERS | FITS_REFUSED | FITS_AT_BOUND -, scale information (1 / variance of ln scale per unit^2 of landmark
+    noise; 0 with fixed=True), 0.  Everything else as for fit_landmarks."""
+    lead, src_device, args = _scale_fit_inputs(hand_model, landmarks, weights, init, init_scale, limits, mirror)
+    ja, xf, scale, info = _native.fit_pose_scale(scale_mode=_native.UT_SCALE_FIXED if fixed else _native.UT_SCALE_FREE,
+                                                 max_iters=max_iters, **args)
+    return (ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device), scale.reshape(lead).to(src_device),
+            info.reshape(lead + (6,)).to(src_device))
+
+
+class ScaleCalibration(NamedTuple):
+    """What calibrate_scale returns.  scale [...]: one per group; stats [...,4]: the scale again, sigma - the standard
+    deviation of ln scale per unit of landmark noise -, scatter - the landmark noise that would explain how much the poses
+    disagree -, poses used; hand_model: scaled_hand_model(hand_model, scale) when there is one group and the model is
+    unbatched, else None; joint_angles [...,N,22], wrist_transforms [...,N,4,4], info [...,N,6]: the poses refitted at the
+    calibrated scale (refit=True), else those of the free pass with their own scales in pose_scale [...,N]."""
+    scale: torch.Tensor
+    stats: torch.Tensor
+    hand_model: Optional[HandModel]
+    joint_angles: torch.Tensor
+    wrist_transforms: torch.Tensor
+    info: torch.Tensor
+    pose_scale: torch.Tensor
+
+
+def calibrate_scale(hand_model: HandModel, landmarks: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                    mirror: Optional[torch.Tensor] = None, refit: bool = True, max_iters: int = 32) -> ScaleCalibration:
+    """One scale for each group of N poses of one person: landmarks [...,N,21,3] (weights [...,N,21], mirror [...,N]) ->
+    ScaleCalibration.  A free pass of fit_landmarks_scale over all poses, the information-weighted pool over the N axis
+    (ut_pool_scale: poses that did not converge, were refused or ended at a scale bound do not count), and with refit=True
+    a second pass at the pooled scale, warm-started from the first.  Three launches, no host work in between.  ValueError
+    when a group has no usable pose."""
+    if landmarks.dim() < 3:
+        raise ValueError(f"landmarks must be [...,N,21,3], got {tuple(landmarks.shape)}")
+    lead, src_device, args = _scale_fit_inputs(hand_model, landmarks, weights, None, None, False, mirror)
+    group_lead, n_per = lead[:-1], lead[-1]
+    ja, xf, scale, info = _native.fit_pose_scale(max_iters=max_iters, **args)
+    group, pose_scale = _native.pool_scale(scale, info, n_per)
+    if refit:
+        args.update(init_scale=pose_scale, init_angles=ja, init_wrist_xf=xf)
+        ja, xf, pose_scale, info = _native.fit_pose_scale(scale_mode=_native.UT_SCALE_FIXED, max_iters=max_iters, **args)
+    else:
+        pose_scale = scale
+    stats = group.reshape(group_lead + (4,)).to(src_device)
+    if bool((stats[..., 3] == 0).any()):
+        raise ValueError("calibrate_scale: a group has no usable pose (none converged away from the scale bounds)")
+    pooled = stats[..., 0]
+    model = None
+    if group_lead == () and hand_model.joint_rest_positions.dim() == 2:
+        model = scaled_hand_model(hand_model, float(pooled))
+    return ScaleCalibration(pooled, stats, model, ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device),
+                            info.reshape(lead + (6,)).to(src_device), pose_scale.reshape(lead).to(src_device))
+
+
 _MESH_FIELDS = ("mesh_vertices", "mesh_triangles", "dense_bone_weights")
 _mesh_cache: list = []      # [(key, tensors kept alive, _native.Mesh)], most recent first
 

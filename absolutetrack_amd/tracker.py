@@ -19,6 +19,7 @@ from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
 from .hand import FIT_CONVERGED, fit_landmarks
+from .hand import ScaleCalibration, calibrate_scale
 from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
 
@@ -248,6 +249,59 @@ def hand_pose_from_window_keypoints(hand_model: HandModel, cameras: List[CameraM
     pose = SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(),
                           hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0)
     return pose, info
+
+
+def calibrate_hand_model_from_keypoints(hand_model: HandModel, keypoints: np.ndarray, valid: np.ndarray,
+                                        n_calibration_samples: int = 0) -> Tuple[HandModel, float, np.ndarray]:
+    """A model scaled to the person whose 3-D keypoints these are: the keypoint twin of the reference's calibration pass
+    (run_eval_unknown_skeleton.py:55-76, which averages the network's predicted scales and applies scaled_hand_model).
+    keypoints [n_hands, n_frames, 21, 3] (mm, world; hand 1 is the right hand) and valid [n_hands, n_frames] in the layout
+    of the eval result files; hand_model e.g. the generic one.  Every valid hand-frame is fitted with a free scale, both
+    hands pool into one scale (hand.calibrate_scale) - samples in the reference's order, frame by frame and hand by hand,
+    only the first n_calibration_samples valid ones when that is not 0.  Invalid hand-frames get weight 0: the fit refuses
+    them and the pool leaves them out.  Returns (scaled_hand_model(hand_model, scale), scale, stats [4]: scale, sigma,
+    scatter, poses used - see hand.ScaleCalibration).  ValueError when no pose is usable."""
+    keypoints, valid = np.asarray(keypoints), np.asarray(valid, bool)
+    n_hands, n_frames = valid.shape
+    if keypoints.shape != (n_hands, n_frames, 21, 3):
+        raise ValueError(f"keypoints must be [{n_hands},{n_frames},21,3], got {keypoints.shape}")
+    use = valid.T.reshape(-1).copy()                                        # frame major, like the reference's sample list
+    if n_calibration_samples:
+        use &= np.cumsum(use) <= n_calibration_samples
+    kp = np.where(use[:, None, None], keypoints.transpose(1, 0, 2, 3).reshape(-1, 21, 3), 0).astype(np.float32)
+    w = np.repeat(use[:, None], 21, 1).astype(np.float32)
+    mirror = np.tile((np.arange(n_hands) == RIGHT_HAND_INDEX).astype(np.int64), n_frames)
+    cal = calibrate_scale(hand_model, torch.from_numpy(kp), torch.from_numpy(w), torch.from_numpy(mirror), refit=False)
+    return cal.hand_model, float(cal.scale), cal.stats.numpy()
+
+
+def calibrate_hand_model_from_window_keypoints(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray,
+                                               hand_idx: int, weights: Optional[np.ndarray] = None) -> ScaleCalibration:
+    """From 2-D detections to a calibrated model: window_keypoints [n_frames, n_cams, 21, 2] of one hand in the cameras,
+    weights [n_frames, n_cams, 21] as for triangulate_landmarks -> hand.ScaleCalibration (its hand_model is the calibrated
+    model, its poses are refitted at the calibrated scale).  One ut_triangulate_points launch for all frames, each
+    landmark weighted as in hand_pose_from_window_keypoints - (the frame's smallest finite sigma / its sigma)^2 -, then
+    hand.calibrate_scale over the frames."""
+    table = _native_camera_table(cameras, "calibrate_hand_model_from_window_keypoints")
+    win = np.ascontiguousarray(window_keypoints, np.float64)
+    if win.ndim != 4 or win.shape[1:] != (len(cameras), 21, 2):
+        raise ValueError(f"window_keypoints must be [n_frames,{len(cameras)},21,2], got {win.shape}")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float32)
+        if weights.shape != win.shape[:3]:
+            raise ValueError(f"weights must be {win.shape[:3]}, got {weights.shape}")
+    dev = fk_device()
+    n = win.shape[0]
+    rows = torch.arange(len(cameras), dtype=torch.int32, device=dev)[None].expand(n, -1).contiguous()
+    pts, info, _ = _native.triangulate_points(torch.from_numpy(win).to(dev), rows, torch.from_numpy(table).to(dev),
+                                              weights=None if weights is None else torch.from_numpy(weights).to(dev))
+    sigma = info[..., 1].double()
+    ok = torch.isfinite(sigma) & (sigma > 0)
+    best = torch.where(ok, sigma, torch.full_like(sigma, float("inf"))).amin(1, keepdim=True)
+    lw = torch.where(ok, (best / torch.where(ok, sigma, torch.ones_like(sigma))) ** 2, torch.zeros_like(sigma)).float()
+    mirror = torch.full((n,), 1 if hand_idx == RIGHT_HAND_INDEX else 0, dtype=torch.int64, device=dev)
+    cal = calibrate_scale(hand_model, pts.float(), lw, mirror)
+    return ScaleCalibration(*(t.cpu() if isinstance(t, torch.Tensor) else t for t in cal))
 
 
 def _visible_counts(cameras: List[CameraModel], landmarks_world: np.ndarray) -> List[int]:
