@@ -1,5 +1,5 @@
 """ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension headers include/umetrack_hip_fit.h,
-include/umetrack_hip_triangulate.h and include/umetrack_hip_scale.h).
+include/umetrack_hip_triangulate.h, include/umetrack_hip_scale.h and include/umetrack_hip_info.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, every entry point raises.  PyTorch-ROCm is used for device memory and
@@ -88,6 +88,14 @@ _SCALE_PROTOTYPES = {
     "ut_pool_scale": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
 }
 SCALE_EXPORTS = tuple(_SCALE_PROTOTYPES)
+# The entries of include/umetrack_hip_info.h, in a table of their own like their header (tests/test_info_host.py pins it).
+_INFO_PROTOTYPES = {
+    "ut_triangulate_points_info": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp,
+                                          _vp]),
+    "ut_fit_pose_info": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _vp, _i32, _vp,
+                                _i32, _vp, _vp]),
+}
+INFO_EXPORTS = tuple(_INFO_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -111,7 +119,8 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
+                                      **_INFO_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -288,8 +297,33 @@ def fit_pose(hand_model: torch.Tensor, targets: torch.Tensor, weights: Optional[
     None.  Packed tensors by default, outputs fresh [n,22] / [n,4,4].  With n given, targets / init_* / out are fp32 views
     used in place with the strides given in floats - keypoints and poses inside record buffers, `out` may be the init's
     own views.  All tensors on one HIP device; `engine` only lends its handle for error reporting."""
+    return _fit_pose("ut_fit_pose", hand_model, targets, weights, limits, init_angles, init_wrist_xf, mirror, t_scale, max_iters,
+                     n, target_stride, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride, info, engine)
+
+
+def fit_pose_info(hand_model: torch.Tensor, targets: torch.Tensor, sqrt_info: torch.Tensor,
+                  limits: Optional[torch.Tensor] = None, init_angles: Optional[torch.Tensor] = None,
+                  init_wrist_xf: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                  max_iters: int = 32, *, n: Optional[int] = None, target_stride: int = 63, init_ja_stride: int = 22,
+                  init_xf_stride: int = 16, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22,
+                  xf_stride: int = 16, info: Optional[torch.Tensor] = None, engine: Optional["HipEngine"] = None):
+    """ut_fit_pose_info: fit_pose with every landmark's residual whitened by the factor of its information, sqrt_info f32
+    [n,21,6] - (l00, l10, l11, l20, l21, l22) of the lower Cholesky factor, what triangulate_points_info returns - in place
+    of the weights; a landmark whose factor is all 0 is not used and its target not read.  Returns (joint_angles, wrist_xf,
+    info [n,4]: whitened rms residual, largest Euclidean residual, iterations, status bits UT_FIT_*).  Every other argument
+    as for fit_pose.  Without init_angles / init_wrist_xf this is the C entry's cold start, which can end in a local minimum
+    on the anisotropic cost: warm-start from fit_pose's result (hand.fit_landmarks_info does)."""
+    if sqrt_info is None:
+        raise ValueError("sqrt_info is required")
+    return _fit_pose("ut_fit_pose_info", hand_model, targets, sqrt_info, limits, init_angles, init_wrist_xf, mirror, t_scale,
+                     max_iters, n, target_stride, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride, info, engine)
+
+
+def _fit_pose(entry, hand_model, targets, weights, limits, init_angles, init_wrist_xf, mirror, t_scale, max_iters, n,
+              target_stride, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride, info, engine):
+    """fit_pose and fit_pose_info: `weights` is [n,21] for ut_fit_pose, the factors [n,21,6] for ut_fit_pose_info."""
     lib = load_library()
-    d = _hip_device(targets, "fit_pose")
+    d = _hip_device(targets, entry[3:])
     hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
     if (init_angles is None) != (init_wrist_xf is None):
         raise ValueError("init_angles and init_wrist_xf go together")
@@ -312,9 +346,10 @@ def fit_pose(hand_model: torch.Tensor, targets: torch.Tensor, weights: Optional[
     if hand_model.shape[0] not in (1, n) and n:
         raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
     if weights is not None:
-        weights = _need(weights, torch.float32, d, "weights")
-        if tuple(weights.shape) != (n, 21):
-            raise ValueError(f"weights must be [{n},21], got {tuple(weights.shape)}")
+        name, shape = ("weights", (n, 21)) if entry == "ut_fit_pose" else ("sqrt_info", (n, 21, 6))
+        weights = _need(weights, torch.float32, d, name)
+        if tuple(weights.shape) != shape:
+            raise ValueError(f"{name} must be [{','.join(map(str, shape))}], got {tuple(weights.shape)}")
     if limits is not None:
         limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
         if limits.shape[0] != hand_model.shape[0]:
@@ -326,11 +361,11 @@ def fit_pose(hand_model: torch.Tensor, targets: torch.Tensor, weights: Optional[
     info = _out(info, (n, 4), torch.float32, d, "info")
     h = engine._h if engine is not None else None
     with torch.cuda.device(d):
-        rc = lib.ut_fit_pose(h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights), _ptr(limits),
-                             _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror),
-                             ctypes.c_float(t_scale), int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride,
-                             _ptr(info), _stream(d))
-    _check_rc(lib, h, rc, "ut_fit_pose", "points")
+        rc = getattr(lib, entry)(h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights), _ptr(limits),
+                                 _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror),
+                                 ctypes.c_float(t_scale), int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride,
+                                 _ptr(info), _stream(d))
+    _check_rc(lib, h, rc, entry, "points")
     return out[0], out[1], info
 
 
@@ -557,6 +592,23 @@ def triangulate_points(window: torch.Tensor, cam_rows: torch.Tensor, table: torc
     i - 1 and begins with the pose's 3 P floats - keypoints inside records, written in place, or the targets of fit_pose; the
     f64 result rounded once.  A cam_rows entry outside [-1, R) raises IndexError and writes nothing for its pose - at once,
     or from engine.poll_status() when `engine` runs deferred checks (then nothing synchronises)."""
+    return _triangulate_points(window, cam_rows, table, weights, max_iters, out, engine, out_f32, point_stride, False)[:3]
+
+
+def triangulate_points_info(window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                            weights: Optional[torch.Tensor] = None, max_iters: int = 16,
+                            out: Optional[Tuple[Optional[torch.Tensor], ...]] = None, engine: Optional["HipEngine"] = None, *,
+                            out_f32: Optional[torch.Tensor] = None, point_stride: Optional[int] = None):
+    """ut_triangulate_points_info: triangulate_points, bit for bit, that also returns what the views know about each point -
+    (points, info, residual, sqrt_info f32 [n,P,6]): (l00, l10, l11, l20, l21, l22) of the lower Cholesky factor L of H = sum_v
+    w_v J_v^T J_v at the point, px per model unit; moving the point by d costs |L^T d|^2 px^2 to first order.  All 0 for refused
+    and degenerate points and where sigma is +inf.  The input of fit_pose_info.  out: preallocated (points, info, residual,
+    sqrt_info), any of them None."""
+    return _triangulate_points(window, cam_rows, table, weights, max_iters, out, engine, out_f32, point_stride, True)
+
+
+def _triangulate_points(window, cam_rows, table, weights, max_iters, out, engine, out_f32, point_stride, factor: bool):
+    """triangulate_points and, with factor=True, triangulate_points_info."""
     if window.dim() != 4 or window.shape[3] != 2 or window.dtype != torch.float64:
         raise ValueError(f"window must be f64 [n,V,P,2], got {window.dtype} {tuple(window.shape)}")
     n, v, n_points = window.shape[:3]
@@ -577,23 +629,27 @@ def triangulate_points(window: torch.Tensor, cam_rows: torch.Tensor, table: torc
         raise ValueError(f"out_f32 must be an fp32 view with point_stride >= {3 * n_points}")
     kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
     lib = load_library()
-    d = _hip_device(window, "triangulate_points")
+    d = _hip_device(window, "triangulate_points_info" if factor else "triangulate_points")
     window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
     if weights is not None:
         weights = _need(weights, torch.float32, d, "weights")
     if out_f32 is not None and out_f32.device != d:
         raise ValueError(f"out_f32 must live on {d}")
-    points, info, residual = out if out is not None else (None, None, None)
+    points, info, residual, sqrt_info = tuple(out) + (None,) * (4 - len(out)) if out is not None else (None,) * 4
     points = _out(points, (n, n_points, 3), torch.float64, d, "out[0]")
     info = _out(info, (n, n_points, 4), torch.float32, d, "out[1]")
     residual = _out(residual, (n, v, n_points), torch.float32, d, "out[2]")
+    sqrt_info = _out(sqrt_info, (n, n_points, 6), torch.float32, d, "out[3]") if factor else None
     h = engine._h if engine is not None else None
+    args = (h, _ptr(window), _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind, n_points, n, int(max_iters),
+            _ptr(points), _ptr(out_f32), int(point_stride or 0), _ptr(info), _ptr(residual))
     with torch.cuda.device(d):
-        rc = lib.ut_triangulate_points(h, _ptr(window), _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind,
-                                       n_points, n, int(max_iters), _ptr(points), _ptr(out_f32), int(point_stride or 0),
-                                       _ptr(info), _ptr(residual), _stream(d))
-    _check_rc(lib, h, rc, "ut_triangulate_points", "points")
-    return points, info, residual
+        if not factor:
+            rc = lib.ut_triangulate_points(*args, _stream(d))
+        else:
+            rc = lib.ut_triangulate_points_info(*args, _ptr(sqrt_info), _stream(d))
+    _check_rc(lib, h, rc, "ut_triangulate_points_info" if factor else "ut_triangulate_points", "points")
+    return points, info, residual, sqrt_info
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

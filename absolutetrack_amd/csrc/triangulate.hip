@@ -1,5 +1,6 @@
-// Points from views (ut_triangulate_points, include/umetrack_hip_triangulate.h): the inverse of ut_project_points.  Window
-// coordinates of one point in several cameras -> the world point, its reprojection residuals and its uncertainty.
+// Points from views (ut_triangulate_points, include/umetrack_hip_triangulate.h; ut_triangulate_points_info,
+// include/umetrack_hip_info.h): the inverse of ut_project_points.  Window coordinates of one point in several cameras -> the
+// world point, its reprojection residuals and its uncertainty - as one number, or as the factor of its 3 x 3 information.
 // One thread per (pose, point); fp64 throughout.  Per thread: a linear start from the views' rays, then Levenberg-Marquardt on
 // the reprojection error through the exact forward model (world_to_eye_d + fisheye_project_d of ut_camera.h, or the pinhole of
 // render.hip) with an analytic 2 x 3 Jacobian per view.  The views are visited in ascending order by a loop bounded by
@@ -193,7 +194,9 @@ __device__ inline void evaluate(const View<KIND>& vw, unsigned used, const doubl
 
 }  // namespace
 
-template <int KIND>
+// FACTOR: the instantiation behind ut_triangulate_points_info, which also writes the Cholesky factor of H that step 4 forms for
+// sigma (a.sqrt_info); everything else is the arithmetic of the other instantiation, in the same order.
+template <int KIND, bool FACTOR>
 __global__ __launch_bounds__(64) void triangulate_kernel(TriArgs a) {
   const long long idx = (long long)blockIdx.x * 64 + threadIdx.x;
   if (idx >= (long long)a.n * a.n_points) return;
@@ -305,15 +308,23 @@ __global__ __launch_bounds__(64) void triangulate_kernel(TriArgs a) {
     float* o = a.points_f32 + (size_t)i * a.point_stride + 3 * p;
     o[0] = (float)X[0]; o[1] = (float)X[1]; o[2] = (float)X[2];
   }
-  if (a.info) {
+  if (a.info || FACTOR) {
     double sigma = INFINITY, rms = 0.0;
+    Sym3 l{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (live) {
-      Sym3 l;
       if (chol3(cur.h, 0.0, l)) sigma = sqrt(chol3_trace_inverse(l));
       rms = sqrt(cur.cost / w_sum);
     }
-    float* o = a.info + (size_t)idx * 4;
-    o[0] = (float)rms; o[1] = (float)sigma; o[2] = (float)n_used; o[3] = (float)status;
+    if (a.info) {
+      float* o = a.info + (size_t)idx * 4;
+      o[0] = (float)rms; o[1] = (float)sigma; o[2] = (float)n_used; o[3] = (float)status;
+    }
+    if (FACTOR) {                       // 0 where the reported sigma is +inf: the point carries no information
+      const bool known = (float)sigma <= 3.0e38f;
+      float* o = a.sqrt_info + (size_t)idx * 6;
+      o[0] = known ? (float)l.a00 : 0.f; o[1] = known ? (float)l.a10 : 0.f; o[2] = known ? (float)l.a11 : 0.f;
+      o[3] = known ? (float)l.a20 : 0.f; o[4] = known ? (float)l.a21 : 0.f; o[5] = known ? (float)l.a22 : 0.f;
+    }
   }
   if (a.residual) {
     for (int v = 0; v < nv; ++v) {
@@ -335,8 +346,14 @@ hipError_t launch_triangulate(const TriArgs& a, hipStream_t s) {
   if (total <= 0) return hipSuccess;
   if (a.max_views < 1 || a.max_views > TRI_MAX_VIEWS || total > (1ll << 36)) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((total + 63) / 64)), block(64);
-  if (a.kind == PROJECT_FISHEYE62) hipLaunchKernelGGL(triangulate_kernel<PROJECT_FISHEYE62>, grid, block, 0, s, a);
-  else hipLaunchKernelGGL(triangulate_kernel<PROJECT_PINHOLE>, grid, block, 0, s, a);
+  const bool fisheye = a.kind == PROJECT_FISHEYE62;
+  if (a.sqrt_info) {
+    if (fisheye) hipLaunchKernelGGL((triangulate_kernel<PROJECT_FISHEYE62, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((triangulate_kernel<PROJECT_PINHOLE, true>), grid, block, 0, s, a);
+  } else {
+    if (fisheye) hipLaunchKernelGGL((triangulate_kernel<PROJECT_FISHEYE62, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((triangulate_kernel<PROJECT_PINHOLE, false>), grid, block, 0, s, a);
+  }
   return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 // units, weight folding and packing in ut_weights.cpp.
 #include "../../include/umetrack_hip.h"
 #include "../../include/umetrack_hip_fit.h"
+#include "../../include/umetrack_hip_info.h"
 #include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_triangulate.h"
 
@@ -1167,24 +1168,60 @@ int ut_fk(ut_handle h, const float* hand_model, int n_models, const float* joint
   return UT_OK;
 }
 
+namespace {
+int fail_as(ut_handle h, const char* who, const char* what) {
+  char msg[256];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return fail(h, UT_E_INVALID, msg);
+}
+
+// The argument checks ut_fit_pose and ut_fit_pose_info share; `who` names the entry in the message.
+int fit_pose_args(ut_handle h, const char* who, const float* hand_model, int n_models, const float* targets, int target_stride,
+                  const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride, float t_scale,
+                  int max_iters, int n, const float* joint_angles, int ja_stride, const float* wrist_xf, int xf_stride) {
+  if (!hand_model || !targets || !joint_angles || !wrist_xf || n < 0 || (n_models != 1 && n_models != n))
+    return fail_as(h, who, "bad argument");
+  if ((init_angles == nullptr) != (init_wrist_xf == nullptr))
+    return fail_as(h, who, "init_angles and init_wrist_xf must both be given or both be NULL");
+  if (target_stride < 63 || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
+    return fail_as(h, who, "a stride is below 63 (targets) / 22 (angles) / 12 (wrist)");
+  if (max_iters < 1 || max_iters > 256) return fail_as(h, who, "max_iters must be in 1..256");
+  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f)) return fail_as(h, who, "t_scale must be positive and finite");
+  return UT_OK;
+}
+}  // namespace
+
 int ut_fit_pose(ut_handle h, const float* hand_model, int n_models, const float* targets, int target_stride,
                 const float* weights, const float* limits, const float* init_angles, int init_ja_stride,
                 const float* init_wrist_xf, int init_xf_stride, const int64_t* mirror, float t_scale, int max_iters, int n,
                 float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride, float* info, void* stream) {
   // stateless like ut_fk: h may be NULL
   if (n == 0) return UT_OK;
-  if (!hand_model || !targets || !joint_angles || !wrist_xf || n < 0 || (n_models != 1 && n_models != n))
-    return fail(h, UT_E_INVALID, "ut_fit_pose: bad argument");
-  if ((init_angles == nullptr) != (init_wrist_xf == nullptr))
-    return fail(h, UT_E_INVALID, "ut_fit_pose: init_angles and init_wrist_xf must both be given or both be NULL");
-  if (target_stride < 63 || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
-    return fail(h, UT_E_INVALID, "ut_fit_pose: a stride is below 63 (targets) / 22 (angles) / 12 (wrist)");
-  if (max_iters < 1 || max_iters > 256) return fail(h, UT_E_INVALID, "ut_fit_pose: max_iters must be in 1..256");
-  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f)) return fail(h, UT_E_INVALID, "ut_fit_pose: t_scale must be positive and finite");
+  const int rc = fit_pose_args(h, "ut_fit_pose", hand_model, n_models, targets, target_stride, init_angles, init_ja_stride,
+                               init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
+  if (rc) return rc;
   ON_DEVICE_IF(h);
   const ut::FitArgs a{hand_model, n_models, targets, target_stride, weights, limits, init_angles, init_ja_stride, init_wrist_xf,
                       init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride, info};
   HIPCHK(h, ut::launch_fit_pose(a, (hipStream_t)stream));
+  return UT_OK;
+}
+
+int ut_fit_pose_info(ut_handle h, const float* hand_model, int n_models, const float* targets, int target_stride,
+                     const float* sqrt_info, const float* limits, const float* init_angles, int init_ja_stride,
+                     const float* init_wrist_xf, int init_xf_stride, const int64_t* mirror, float t_scale, int max_iters, int n,
+                     float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride, float* info, void* stream) {
+  // stateless like ut_fit_pose: h may be NULL
+  if (n == 0) return UT_OK;
+  if (!sqrt_info) return fail(h, UT_E_INVALID, "ut_fit_pose_info: bad argument");
+  const int rc = fit_pose_args(h, "ut_fit_pose_info", hand_model, n_models, targets, target_stride, init_angles, init_ja_stride,
+                               init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
+  if (rc) return rc;
+  ON_DEVICE_IF(h);
+  const ut::FitInfoArgs a{hand_model, n_models, targets, target_stride, sqrt_info, limits, init_angles, init_ja_stride,
+                          init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf,
+                          xf_stride, info};
+  HIPCHK(h, ut::launch_fit_pose_info(a, (hipStream_t)stream));
   return UT_OK;
 }
 
@@ -1402,23 +1439,24 @@ int ut_project_points(ut_handle h, const float* points, int point_stride, int n_
 static_assert(UT_TRI_MAX_VIEWS == ut::TRI_MAX_VIEWS && UT_TRI_CONVERGED == ut::TRI_CONVERGED && UT_TRI_AT_MAX_ITERS == ut::TRI_AT_MAX_ITERS &&
               UT_TRI_REFUSED == ut::TRI_REFUSED && UT_TRI_DEGENERATE == ut::TRI_DEGENERATE, "triangulation constants");
 
-int ut_triangulate_points(ut_handle h, const double* window, const float* weights, const int32_t* cam_rows, int max_views,
-                          const double* table, int n_rows, int table_kind, int n_points, int n, int max_iters,
-                          double* points, float* points_f32, int point_stride, float* info, float* residual, void* stream) {
-  if (!window || !cam_rows || !table) return fail(h, UT_E_INVALID, "ut_triangulate_points: null argument");
-  if (!points && !points_f32) return fail(h, UT_E_INVALID, "ut_triangulate_points: one of points and points_f32 must be given");
+namespace {
+// ut_triangulate_points and ut_triangulate_points_info: one path, sqrt_info null for the former; `who` names the entry.
+int triangulate_points(ut_handle h, const char* who, const double* window, const float* weights, const int32_t* cam_rows,
+                       int max_views, const double* table, int n_rows, int table_kind, int n_points, int n, int max_iters,
+                       double* points, float* points_f32, int point_stride, float* info, float* residual, float* sqrt_info,
+                       void* stream) {
+  if (!window || !cam_rows || !table) return fail_as(h, who, "null argument");
+  if (!points && !points_f32) return fail_as(h, who, "one of points and points_f32 must be given");
   if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
-    return fail(h, UT_E_INVALID, "ut_triangulate_points: table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
-  if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS)
-    return fail(h, UT_E_INVALID, "ut_triangulate_points: max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
-  if (max_iters < 1 || max_iters > 64) return fail(h, UT_E_INVALID, "ut_triangulate_points: max_iters must be in 1..64");
-  if (n < 0 || n_points < 1 || n_rows < 1 || (points_f32 && point_stride < 3 * n_points))
-    return fail(h, UT_E_INVALID, "ut_triangulate_points: bad argument");
+    return fail_as(h, who, "table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
+  if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS) return fail_as(h, who, "max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
+  if (max_iters < 1 || max_iters > 64) return fail_as(h, who, "max_iters must be in 1..64");
+  if (n < 0 || n_points < 1 || n_rows < 1 || (points_f32 && point_stride < 3 * n_points)) return fail_as(h, who, "bad argument");
   if (n == 0) return UT_OK;
   if (h) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, window) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device != h->device)
-      return fail(h, UT_E_INVALID, "ut_triangulate_points: the windows live on another device than the handle");
+      return fail_as(h, who, "the windows live on another device than the handle");
   }
   StatusTarget st;
   int rc = status_target(h, &st);
@@ -1430,9 +1468,26 @@ int ut_triangulate_points(ut_handle h, const double* window, const float* weight
   g.window = window; g.weights = weights; g.cam_rows = cam_rows; g.max_views = max_views; g.table = table; g.n_rows = n_rows;
   g.kind = table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE;
   g.n_points = n_points; g.n = n; g.max_iters = max_iters; g.points = points; g.points_f32 = points_f32;
-  g.point_stride = point_stride; g.info = info; g.residual = residual; g.status = st.dev;
+  g.point_stride = point_stride; g.info = info; g.residual = residual; g.status = st.dev; g.sqrt_info = sqrt_info;
   HIPCHK(h, ut::launch_triangulate(g, s));
-  return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, "ut_triangulate_points") : UT_OK;
+  return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, who) : UT_OK;
+}
+}  // namespace
+
+int ut_triangulate_points(ut_handle h, const double* window, const float* weights, const int32_t* cam_rows, int max_views,
+                          const double* table, int n_rows, int table_kind, int n_points, int n, int max_iters,
+                          double* points, float* points_f32, int point_stride, float* info, float* residual, void* stream) {
+  return triangulate_points(h, "ut_triangulate_points", window, weights, cam_rows, max_views, table, n_rows, table_kind, n_points,
+                            n, max_iters, points, points_f32, point_stride, info, residual, nullptr, stream);
+}
+
+int ut_triangulate_points_info(ut_handle h, const double* window, const float* weights, const int32_t* cam_rows, int max_views,
+                               const double* table, int n_rows, int table_kind, int n_points, int n, int max_iters,
+                               double* points, float* points_f32, int point_stride, float* info, float* residual,
+                               float* sqrt_info, void* stream) {
+  if (!sqrt_info) return fail(h, UT_E_INVALID, "ut_triangulate_points_info: null argument");
+  return triangulate_points(h, "ut_triangulate_points_info", window, weights, cam_rows, max_views, table, n_rows, table_kind,
+                            n_points, n, max_iters, points, points_f32, point_stride, info, residual, sqrt_info, stream);
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

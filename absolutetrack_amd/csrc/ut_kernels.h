@@ -316,6 +316,24 @@ struct FitArgs {
 };
 hipError_t launch_fit_pose(const FitArgs& a, hipStream_t s);
 
+// Poses from landmarks and their information (fit_info.hip): fit.hip's solver on residuals whitened by a 3 x 3 factor per
+// landmark.  Pointers as ut_fit_pose_info documents them.
+struct FitInfoArgs {
+  const float* hand_model; int n_models;
+  const float* targets; int target_stride;
+  const float* sqrt_info;               // [n,21,6]: l00 l10 l11 l20 l21 l22 of the lower factor of a landmark's information
+  const float* limits;                  // [n_models,20,2] or null
+  const float* init_ja; int init_ja_stride;
+  const float* init_xf; int init_xf_stride;   // both init pointers null: cold start
+  const int64_t* mirror;
+  float t_scale;
+  int max_iters, n;
+  float* ja; int ja_stride;
+  float* xf; int xf_stride;
+  float* info;                          // [n,4] or null
+};
+hipError_t launch_fit_pose_info(const FitInfoArgs& a, hipStream_t s);
+
 // Poses and the hand's scale from landmarks (fit_scale.hip): fit.hip's solver with ln(scale) as a 27th parameter, one wave per
 // pose, and the pool of per-pose scales, one wave per group.  Pointers as ut_fit_pose_scale / ut_pool_scale document them; the
 // constants are public as UT_SCALE_* / UT_FITS_*.
@@ -392,6 +410,7 @@ struct TriArgs {
   float* info;                  // [n,n_points,4] or null
   float* residual;              // [n,max_views,n_points] or null
   int* status;                  // sticky status word: UT_BAD_SRC_INDEX for a cam_rows entry outside [-1, n_rows)
+  float* sqrt_info;             // [n,n_points,6] or null: l00 l10 l11 l20 l21 l22 of the lower Cholesky factor of H at the point
 };
 hipError_t launch_triangulate(const TriArgs& a, hipStream_t s);
 

@@ -196,6 +196,45 @@ def fit_landmarks(hand_model: HandModel, landmarks: torch.Tensor, weights: Optio
             info.reshape(lead + (4,)).to(src_device))
 
 
+def fit_landmarks_info(hand_model: HandModel, landmarks: torch.Tensor, sqrt_info: torch.Tensor, init=None, limits: bool = False,
+                       mirror: Optional[torch.Tensor] = None, max_iters: int = 32):
+    """fit_landmarks for landmarks that come with their information, on the HIP kernel csrc/fit_info.hip (no CPU
+    implementation): sqrt_info [...,21,6] holds (l00, l10, l11, l20, l21, l22) of the lower Cholesky factor L of each
+    landmark's 3 x 3 information matrix - what tracker.triangulate_landmarks(..., with_information=True) returns, or
+    chol(covariance^-1) of a depth sensor's or a motion capture system's landmarks - and the fit minimises sum_l |L_l^T
+    (landmark_l - target_l)|^2 instead of treating a landmark's error as isotropic.  A landmark whose factor is all 0 is not used
+    and may be NaN.  init = (joint_angles, wrist_transforms) warm-starts the fit; without one, fit_landmarks runs first on
+    the used landmarks (weight 1, the others 0) and its result is the start - two launches, no host work between them: the
+    anisotropic cost is flat along the viewing rays and a cold start on it can end in a local minimum.  Returns (joint_angles
+    [...,22], wrist_transforms [...,4,4], info [...,4]: whitened rms residual - px for triangulated landmarks -, largest
+    Euclidean residual, iterations, status as for fit_landmarks).  Everything else as for fit_landmarks."""
+    lead = tuple(landmarks.shape[:-2])
+    n = int(np.prod(lead)) if lead else 1
+    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
+    if model_lead not in ((), lead):
+        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
+    if limits and hand_model.joint_limits is None:
+        raise ValueError("limits=True needs hand_model.joint_limits")
+    if tuple(sqrt_info.shape) != lead + (21, 6):
+        raise ValueError(f"sqrt_info must be {lead + (21, 6)}, got {tuple(sqrt_info.shape)}")
+    src_device = landmarks.device
+    dev = src_device if src_device.type == "cuda" else fk_device()
+
+    def dev32(t, tail):
+        return None if t is None else t.reshape((n,) + tail).to(dev, torch.float32)
+    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
+    blob, targets, factor = device_blob(hand_model, dev), dev32(landmarks, (21, 3)), dev32(sqrt_info, (21, 6))
+    flip = None if mirror is None else mirror.reshape(n).to(dev, torch.int64)
+    if init is None:
+        used = (factor != 0).any(-1).to(torch.float32)
+        start = _native.fit_pose(blob, targets, used, box, mirror=flip, max_iters=max_iters)[:2]
+    else:
+        start = (dev32(init[0], (22,)), dev32(init[1], (4, 4)))
+    ja, xf, info = _native.fit_pose_info(blob, targets, factor, box, start[0], start[1], flip, max_iters=max_iters)
+    return (ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device),
+            info.reshape(lead + (4,)).to(src_device))
+
+
 FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FITS_CONVERGED, _native.UT_FITS_AT_MAX_ITERS,
                                                                   _native.UT_FITS_REFUSED, _native.UT_FITS_AT_BOUND)
 

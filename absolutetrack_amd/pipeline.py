@@ -213,15 +213,19 @@ def project_keypoints(points: torch.Tensor, cam_params: torch.Tensor, src_row: t
 
 def triangulate_keypoints(window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
                           weights: Optional[torch.Tensor] = None, engine: Optional[_native.HipEngine] = None, max_iters: int = 16,
-                          out_f32: Optional[torch.Tensor] = None, point_stride: Optional[int] = None):
+                          out_f32: Optional[torch.Tensor] = None, point_stride: Optional[int] = None,
+                          with_information: bool = False):
     """Batched tracker.triangulate_landmarks, the inverse of project_keypoints: the window keypoints of n hand-samples in the
     cameras that see them -> their world points, ONE ut_triangulate_points launch.  window f64 [n,V,P,2] px on the device
     (what project_keypoints returns); cam_params f64 [R,32] (FrameBatch.cam_params) or [R,24] crop cameras; src_row i32
     [n,V] rows of cam_params per view, -1 where unused; weights f32 [n,V,P] or None, e.g. (flags == 3).float() of
     project_keypoints, or detection confidences.  out_f32 / point_stride: write the points as fp32 into records in place, e.g.
-    `records[:, POSE_REC:]` with point_stride=RECORD.  Returns (points f64 [n,P,3], info f32 [n,P,4], residual f32 [n,V,P])."""
-    return _native.triangulate_points(window, src_row, cam_params, weights=weights, max_iters=max_iters, engine=engine,
-                                      out_f32=out_f32, point_stride=point_stride)
+    `records[:, POSE_REC:]` with point_stride=RECORD.  Returns (points f64 [n,P,3], info f32 [n,P,4], residual f32 [n,V,P]);
+    with_information=True: ONE ut_triangulate_points_info launch instead, the same three and sqrt_info f32 [n,P,6], the factor
+    of every point's information that _native.fit_pose_info / hand.fit_landmarks_info read."""
+    entry = _native.triangulate_points_info if with_information else _native.triangulate_points
+    return entry(window, src_row, cam_params, weights=weights, max_iters=max_iters, engine=engine, out_f32=out_f32,
+                 point_stride=point_stride)
 
 
 def view_rows(src_index: torch.Tensor, sample_range: torch.Tensor, max_views: int = MAX_VIEW_NUM) -> torch.Tensor:

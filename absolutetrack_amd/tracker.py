@@ -18,7 +18,7 @@ import torch
 from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
-from .hand import FIT_CONVERGED, fit_landmarks
+from .hand import FIT_CONVERGED, fit_landmarks, fit_landmarks_info
 from .hand import ScaleCalibration, calibrate_scale
 from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
@@ -203,14 +203,16 @@ def _native_camera_table(cameras: List[CameraModel], who: str) -> np.ndarray:
     return np.stack([geometry.pack_camera_model(c) for c in cameras])
 
 
-def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weights: Optional[np.ndarray] = None
-                          ) -> Tuple[np.ndarray, np.ndarray]:
+def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weights: Optional[np.ndarray] = None,
+                          with_information: bool = False):
     """The inverse of project_landmarks: window coordinates [n_cams,P,2] of P points in every camera -> (world points [P,3]
     float64, info [P,4] float32: rms reprojection residual px, sigma - mm per px of detection noise -, views used, status
     bits _native.TRI_*), one ut_triangulate_points launch (csrc/triangulate.hip).  weights [n_cams,P] >= 0: how much each
     detection counts, 0 where the camera does not see the point (the window there is not read); None = all 1.  The cameras
     must all be Fisheye62 or all be pinhole models without distortion: any other model raises ValueError naming it - there
-    is no host implementation."""
+    is no host implementation.  with_information=True: one ut_triangulate_points_info launch instead, and a third result,
+    sqrt_info [P,6] float32 - the lower Cholesky factor (l00, l10, l11, l20, l21, l22) of each point's 3 x 3 information
+    matrix, px per mm, all 0 where the point carries none: what hand.fit_landmarks_info reads."""
     table = _native_camera_table(cameras, "triangulate_landmarks")
     win = np.ascontiguousarray(window, np.float64)
     if win.ndim != 3 or win.shape[0] != len(cameras) or win.shape[2] != 2:
@@ -221,22 +223,42 @@ def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weight
             raise ValueError(f"weights must be {win.shape[:2]}, got {weights.shape}")
     dev = fk_device()
     rows = torch.arange(len(cameras), dtype=torch.int32, device=dev)[None]
-    pts, info, _ = _native.triangulate_points(torch.from_numpy(win)[None].to(dev), rows, torch.from_numpy(table).to(dev),
-                                              weights=None if weights is None else torch.from_numpy(weights)[None].to(dev))
-    return pts[0].cpu().numpy(), info[0].cpu().numpy()
+    entry = _native.triangulate_points_info if with_information else _native.triangulate_points
+    out = entry(torch.from_numpy(win)[None].to(dev), rows, torch.from_numpy(table).to(dev),
+                weights=None if weights is None else torch.from_numpy(weights)[None].to(dev))
+    if with_information:
+        return out[0][0].cpu().numpy(), out[1][0].cpu().numpy(), out[3][0].cpu().numpy()
+    return out[0][0].cpu().numpy(), out[1][0].cpu().numpy()
 
 
 def hand_pose_from_window_keypoints(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray,
                                     hand_idx: int, weights: Optional[np.ndarray] = None,
-                                    init: Optional[SingleHandPose] = None) -> Tuple[SingleHandPose, np.ndarray]:
+                                    init: Optional[SingleHandPose] = None, use_information: bool = False
+                                    ) -> Tuple[SingleHandPose, np.ndarray]:
     """From 2-D detections to a pose: window_keypoints [n_cams,21,2] of one hand in the cameras -> (SingleHandPose, the
     triangulation's info [21,4]).  triangulate_landmarks first, then the pose fit of hand_pose_from_landmarks with each
     landmark weighted by (smallest finite sigma / its sigma)^2, in (0, 1]: a landmark the views pin down badly counts
     less; refused and degenerate landmarks count 0.  weights [n_cams,21], init and hand_confidence as for
-    triangulate_landmarks / hand_pose_from_landmarks."""
-    pts, info = triangulate_landmarks(cameras, window_keypoints, weights)
+    triangulate_landmarks / hand_pose_from_landmarks.  use_information=True: the triangulation hands its 3 x 3 information
+    per landmark to the fit instead (hand.fit_landmarks_info) - triangulation with factor, the isotropic fit on the
+    landmarks that carry information (from `init` when given), then the information fit started from it - so that depth,
+    which a narrow baseline measures badly, is fixed by the hand's known size."""
+    if use_information:
+        pts, info, factor = triangulate_landmarks(cameras, window_keypoints, weights, with_information=True)
+    else:
+        pts, info = triangulate_landmarks(cameras, window_keypoints, weights)
     if pts.shape[0] != 21:
         raise ValueError(f"window_keypoints must be [{len(cameras)},21,2], got {np.shape(window_keypoints)}")
+    if use_information:
+        flip = torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0)
+        target, used = torch.from_numpy(pts.astype(np.float32)), torch.from_numpy((factor != 0).any(-1).astype(np.float32))
+        start = None if init is None else (torch.from_numpy(np.asarray(init.joint_angles, np.float32)),
+                                           torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
+        if start is not None:
+            start = fit_landmarks(hand_model, target, weights=used, init=start, mirror=flip)[:2]
+        ja, xf, fit_info = fit_landmarks_info(hand_model, target, torch.from_numpy(factor), init=start, mirror=flip)
+        return SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(),
+                              hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0), info
     sigma = info[:, 1].astype(np.float64)
     ok = np.isfinite(sigma) & (sigma > 0)
     lw = np.zeros(21, np.float32)
