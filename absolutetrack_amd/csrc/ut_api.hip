@@ -1175,7 +1175,7 @@ int fail_as(ut_handle h, const char* who, const char* what) {
   return fail(h, UT_E_INVALID, msg);
 }
 
-// The argument checks ut_fit_pose and ut_fit_pose_info share; `who` names the entry in the message.
+// The argument checks the three pose fits share; `who` names the entry in the message.
 int fit_pose_args(ut_handle h, const char* who, const float* hand_model, int n_models, const float* targets, int target_stride,
                   const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride, float t_scale,
                   int max_iters, int n, const float* joint_angles, int ja_stride, const float* wrist_xf, int xf_stride) {
@@ -1201,8 +1201,9 @@ int ut_fit_pose(ut_handle h, const float* hand_model, int n_models, const float*
                                init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
   if (rc) return rc;
   ON_DEVICE_IF(h);
-  const ut::FitArgs a{hand_model, n_models, targets, target_stride, weights, limits, init_angles, init_ja_stride, init_wrist_xf,
-                      init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride, info};
+  const ut::FitArgs a{{hand_model, n_models, targets, target_stride, limits, init_angles, init_ja_stride, init_wrist_xf,
+                       init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                      weights, info};
   HIPCHK(h, ut::launch_fit_pose(a, (hipStream_t)stream));
   return UT_OK;
 }
@@ -1218,9 +1219,9 @@ int ut_fit_pose_info(ut_handle h, const float* hand_model, int n_models, const f
                                init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
   if (rc) return rc;
   ON_DEVICE_IF(h);
-  const ut::FitInfoArgs a{hand_model, n_models, targets, target_stride, sqrt_info, limits, init_angles, init_ja_stride,
-                          init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf,
-                          xf_stride, info};
+  const ut::FitInfoArgs a{{hand_model, n_models, targets, target_stride, limits, init_angles, init_ja_stride, init_wrist_xf,
+                           init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                          sqrt_info, info};
   HIPCHK(h, ut::launch_fit_pose_info(a, (hipStream_t)stream));
   return UT_OK;
 }
@@ -1237,21 +1238,16 @@ int ut_fit_pose_scale(ut_handle h, const float* hand_model, int n_models, const 
                       float* wrist_xf, int xf_stride, float* scale, float* info, void* stream) {
   // stateless like ut_fit_pose: h may be NULL
   if (n == 0) return UT_OK;
-  if (!hand_model || !targets || !joint_angles || !wrist_xf || !scale || n < 0 || (n_models != 1 && n_models != n))
-    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: bad argument");
+  if (!scale) return fail(h, UT_E_INVALID, "ut_fit_pose_scale: bad argument");
   if (scale_mode != UT_SCALE_FREE && scale_mode != UT_SCALE_FIXED)
     return fail(h, UT_E_INVALID, "ut_fit_pose_scale: scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED");
-  if ((init_angles == nullptr) != (init_wrist_xf == nullptr))
-    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: init_angles and init_wrist_xf must both be given or both be NULL");
-  if (target_stride < 63 || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
-    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: a stride is below 63 (targets) / 22 (angles) / 12 (wrist)");
-  if (max_iters < 1 || max_iters > 256) return fail(h, UT_E_INVALID, "ut_fit_pose_scale: max_iters must be in 1..256");
-  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f))
-    return fail(h, UT_E_INVALID, "ut_fit_pose_scale: t_scale must be positive and finite");
+  const int rc = fit_pose_args(h, "ut_fit_pose_scale", hand_model, n_models, targets, target_stride, init_angles, init_ja_stride,
+                               init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
+  if (rc) return rc;
   ON_DEVICE_IF(h);
-  const ut::FitScaleArgs a{hand_model, n_models, targets, target_stride, weights, limits, init_scale, scale_mode, init_angles,
-                           init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride,
-                           wrist_xf, xf_stride, scale, info};
+  const ut::FitScaleArgs a{{hand_model, n_models, targets, target_stride, limits, init_angles, init_ja_stride, init_wrist_xf,
+                            init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                           weights, init_scale, scale_mode, scale, info};
   HIPCHK(h, ut::launch_fit_pose_scale(a, (hipStream_t)stream));
   return UT_OK;
 }

@@ -299,11 +299,11 @@ hipError_t launch_fk(const float* hand_model, int n_models, const float* ja, int
                      const float* xf, int xf_stride, const int64_t* mirror, float t_scale, int n,
                      float* out, hipStream_t s);
 
-// Poses from landmarks (fit.hip), the inverse of launch_fk: one wave per pose.  Pointers as ut_fit_pose documents them.
-struct FitArgs {
+// Poses from landmarks, the inverse of launch_fk: one Levenberg-Marquardt solver (ut_fit_dev.h), one wave per pose, under three
+// costs.  FitPoseArgs is what the three entries share; pointers as ut_fit_pose documents them.
+struct FitPoseArgs {
   const float* hand_model; int n_models;
   const float* targets; int target_stride;
-  const float* weights;                 // [n,21] or null
   const float* limits;                  // [n_models,20,2] or null
   const float* init_ja; int init_ja_stride;
   const float* init_xf; int init_xf_stride;   // both init pointers null: cold start
@@ -312,48 +312,36 @@ struct FitArgs {
   int max_iters, n;
   float* ja; int ja_stride;
   float* xf; int xf_stride;
+};
+enum : int { FIT_CONVERGED = 1, FIT_AT_MAX_ITERS = 2, FIT_REFUSED = 4 };      // UT_FIT_*, and the low bits of UT_FITS_*
+
+// fit.hip: scalar weights, the cost sum_l w_l |landmark_l - target_l|^2.
+struct FitArgs {
+  FitPoseArgs pose;
+  const float* weights;                 // [n,21] or null
   float* info;                          // [n,4] or null
 };
 hipError_t launch_fit_pose(const FitArgs& a, hipStream_t s);
 
-// Poses from landmarks and their information (fit_info.hip): fit.hip's solver on residuals whitened by a 3 x 3 factor per
-// landmark.  Pointers as ut_fit_pose_info documents them.
+// fit_info.hip: landmarks with their information, the residuals whitened by a 3 x 3 factor per landmark.  Pointers as
+// ut_fit_pose_info documents them.
 struct FitInfoArgs {
-  const float* hand_model; int n_models;
-  const float* targets; int target_stride;
+  FitPoseArgs pose;
   const float* sqrt_info;               // [n,21,6]: l00 l10 l11 l20 l21 l22 of the lower factor of a landmark's information
-  const float* limits;                  // [n_models,20,2] or null
-  const float* init_ja; int init_ja_stride;
-  const float* init_xf; int init_xf_stride;   // both init pointers null: cold start
-  const int64_t* mirror;
-  float t_scale;
-  int max_iters, n;
-  float* ja; int ja_stride;
-  float* xf; int xf_stride;
   float* info;                          // [n,4] or null
 };
 hipError_t launch_fit_pose_info(const FitInfoArgs& a, hipStream_t s);
 
-// Poses and the hand's scale from landmarks (fit_scale.hip): fit.hip's solver with ln(scale) as a 27th parameter, one wave per
-// pose, and the pool of per-pose scales, one wave per group.  Pointers as ut_fit_pose_scale / ut_pool_scale document them; the
-// constants are public as UT_SCALE_* / UT_FITS_*.
+// fit_scale.hip: fit.hip's cost with ln(scale) of the hand as a 27th parameter, and the pool of per-pose scales, one wave per
+// group.  Pointers as ut_fit_pose_scale / ut_pool_scale document them; the constants are public as UT_SCALE_* / UT_FITS_*.
 constexpr int FITS_MODE_FREE = 0, FITS_MODE_FIXED = 1;
 constexpr float FITS_SCALE_MIN = 0.25f, FITS_SCALE_MAX = 4.0f, FITS_SCALE_INFO_LAMBDA = 1e-6f;
-enum : int { FITS_CONVERGED = 1, FITS_AT_MAX_ITERS = 2, FITS_REFUSED = 4, FITS_AT_BOUND = 8 };
+enum : int { FITS_CONVERGED = FIT_CONVERGED, FITS_AT_MAX_ITERS = FIT_AT_MAX_ITERS, FITS_REFUSED = FIT_REFUSED, FITS_AT_BOUND = 8 };
 struct FitScaleArgs {
-  const float* hand_model; int n_models;
-  const float* targets; int target_stride;
+  FitPoseArgs pose;
   const float* weights;                 // [n,21] or null
-  const float* limits;                  // [n_models,20,2] or null
   const float* init_scale;              // [n] or null = 1
   int scale_mode;
-  const float* init_ja; int init_ja_stride;
-  const float* init_xf; int init_xf_stride;   // both init pointers null: cold start
-  const int64_t* mirror;
-  float t_scale;
-  int max_iters, n;
-  float* ja; int ja_stride;
-  float* xf; int xf_stride;
   float* scale;                         // [n]
   float* info;                          // [n,6] or null
 };
