@@ -174,12 +174,27 @@ def cold_start(hm, targets, weights, mirror, box=None, dtype=np.float64):
     return ang, m
 
 
+def solve(a, b):
+    """The linear solve of a step, (A + lambda D) delta = -g, and of scale_cases.information.  A function of its own so that a
+    test can put another float32 algorithm in its place (step_cases.cholesky_solve): two correct float32 solvers differ by what
+    rounding alone does."""
+    return np.linalg.solve(a, b)
+
+
+def trial_record(idx, lam, delta, cost, trial_cost, accept):
+    """What `trace` receives per iteration, for the poses `idx` still active in it: the damping the step was solved with,
+    the step before the box clamps it, the accepted cost it started from, the trial's cost and the decision."""
+    return dict(idx=idx.copy(), lam=lam[idx].copy(), delta=delta.copy(), cost=cost[idx].copy(), trial_cost=trial_cost.copy(),
+                accept=accept.copy())
+
+
 def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=1.0, max_iters=32, dtype=np.float64,
-        history=None):
+        history=None, trace=None):
     """Fit B poses: (joint_angles [B,22], wrist_xf [B,4,4] proper, translation in target units / t_scale, info [B,4]:
     weighted rms residual, worst residual, iterations, status).  targets [B,21,3]; weights [B,21] >= 0 or None; limits
     [20,2] / [B,20,2] or None; init = (joint_angles [B,22], wrist_xf [B,4,4]) or None for the cold start; mirror [B] of
-    0 / 1.  history: a list that receives (angles, effective wrist) after every iteration."""
+    0 / 1.  history: a list that receives (angles, effective wrist) after every iteration.  trace: a list that receives
+    the decision of every iteration (trial_record)."""
     dt = dtype
     b = targets.shape[0]
     w = np.ones((b, 21), dt) if weights is None else np.asarray(weights).astype(dt)
@@ -229,7 +244,7 @@ def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=
         diag = np.einsum("bii->bi", a_mat)
         diag = np.maximum(diag, dt(DIAG_FLOOR) * diag.max(1, keepdims=True))
         damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(26, dtype=dt))
-        delta = np.linalg.solve(damped, -g[..., None])[..., 0].astype(dt)
+        delta = solve(damped, -g[..., None])[..., 0].astype(dt)
         ok = np.isfinite(delta).all(1)
         delta = np.where(ok[:, None], delta, 0)
         ta, tm = apply_step(ang[idx], m[idx], centroid[idx], delta, None if box is None else box[idx])
@@ -238,6 +253,8 @@ def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=
         d2 = (r * r).sum(-1)
         tc, tw = (sub_w * d2).sum(1), np.sqrt(d2.max(1))
         accept = ok & np.isfinite(tc) & (tc < cost[idx])
+        if trace is not None:
+            trace.append(trial_record(idx, lam, delta, cost, tc, accept))
         step_small = (np.abs(ta - ang[idx]).max(1) <= STEP_TOL) & (np.abs(delta[:, 20:23]).max(1) <= STEP_TOL) & \
                      (np.abs(delta[:, 23:26]).max(1) <= dt(STEP_TOL) * extent[idx])
         flat = ~accept | (cost[idx] - tc <= dt(DECREASE_TOL) * cost[idx])

@@ -67,10 +67,11 @@ def whiten(f, r):
 
 
 # ----------------------------------------------------------------------------- the fit
-def fit_info(hm, targets, sqrt_info, limits=None, init=None, mirror=None, t_scale=1.0, max_iters=32, dtype=np.float64):
+def fit_info(hm, targets, sqrt_info, limits=None, init=None, mirror=None, t_scale=1.0, max_iters=32, dtype=np.float64,
+             trace=None):
     """ut_fit_pose_info: fc.fit with the cost sum_l |L_l^T (landmark_l - target_l)|^2.  sqrt_info [B,21,6]; every other argument
-    and the outputs as for fc.fit, with info [B,4]: sqrt(cost / (3 used landmarks)), the largest Euclidean residual of a used
-    landmark, iterations, status.  A landmark is used when any entry of its factor is non-zero; its scalar weight (centroid,
+    (trace included) and the outputs as for fc.fit, with info [B,4]: sqrt(cost / (3 used landmarks)), the largest Euclidean
+    residual of a used landmark, iterations, status.  A landmark is used when any entry of its factor is non-zero; its scalar weight (centroid,
     extent, the cold start's Kabsch fit) is the factor's squared Frobenius norm.  Refused: a factor entry that is not finite,
     a non-finite target of a used landmark, fewer than 3 used landmarks."""
     dt = dtype
@@ -127,12 +128,14 @@ def fit_info(hm, targets, sqrt_info, limits=None, init=None, mirror=None, t_scal
         diag = np.einsum("bii->bi", a_mat)
         diag = np.maximum(diag, dt(fc.DIAG_FLOOR) * diag.max(1, keepdims=True))
         damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(26, dtype=dt))
-        delta = np.linalg.solve(damped, -g[..., None])[..., 0].astype(dt)
+        delta = fc.solve(damped, -g[..., None])[..., 0].astype(dt)
         ok = np.isfinite(delta).all(1)
         delta = np.where(ok[:, None], delta, 0)
         ta, tm = fc.apply_step(ang[idx], m[idx], centroid[idx], delta, None if box is None else box[idx])
         t_cost, t_worst, _u = cost_of(sub, ta, tm, idx)
         accept = ok & np.isfinite(t_cost) & (t_cost < cost[idx])
+        if trace is not None:
+            trace.append(fc.trial_record(idx, lam, delta, cost, t_cost, accept))
         step_small = (np.abs(ta - ang[idx]).max(1) <= fc.STEP_TOL) & (np.abs(delta[:, 20:23]).max(1) <= fc.STEP_TOL) & \
                      (np.abs(delta[:, 23:26]).max(1) <= dt(fc.STEP_TOL) * extent[idx])
         flat = ~accept | (cost[idx] - t_cost <= dt(fc.DECREASE_TOL) * cost[idx])

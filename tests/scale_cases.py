@@ -77,7 +77,7 @@ def information(a_mat, dtype=np.float64):
     for i in range(len(m)):
         try:
             np.linalg.cholesky(m[i, :26, :26])
-            x = np.linalg.solve(m[i, :26, :26], m[i, :26, 26])
+            x = fc.solve(m[i, :26, :26], m[i, :26, 26])
             v = m[i, 26, 26] - m[i, 26, :26] @ x
             out[i] = v if np.isfinite(v) and v > 0 else 0
         except np.linalg.LinAlgError:
@@ -94,11 +94,11 @@ def _normal(hm, s, ang, m, centroid, w, used, y, mode, dt):
 
 
 def fit_scale(hm, targets, weights=None, limits=None, init=None, init_scale=None, mode=FREE, mirror=None, t_scale=1.0,
-              max_iters=32, dtype=np.float64):
+              max_iters=32, dtype=np.float64, trace=None):
     """fit_cases.fit with the scale: (joint_angles [B,22], wrist_xf [B,4,4], scale [B], info [B,6]: weighted rms residual,
     worst residual, iterations, status, scale information, 0).  init_scale [B] or None = 1; a non-finite one or one outside
     [SCALE_MIN, SCALE_MAX] refuses the pose (scale 1).  mode FIXED: the sigma column is zero, the scale stays init_scale and
-    the information is 0.  Status bit AT_BOUND: a FREE fit ended at SCALE_MIN or SCALE_MAX."""
+    the information is 0.  Status bit AT_BOUND: a FREE fit ended at SCALE_MIN or SCALE_MAX.  trace: as for fit_cases.fit."""
     dt = dtype
     b = targets.shape[0]
     hm = {k: np.asarray(hm[k]) for k in _FIELDS}
@@ -152,7 +152,7 @@ def fit_scale(hm, targets, weights=None, limits=None, init=None, init_scale=None
         diag = np.einsum("bii->bi", a_mat)
         diag = np.maximum(diag, dt(fc.DIAG_FLOOR) * diag.max(1, keepdims=True))
         damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(27, dtype=dt))
-        delta = np.linalg.solve(damped, -g[..., None])[..., 0].astype(dt)
+        delta = fc.solve(damped, -g[..., None])[..., 0].astype(dt)
         ok = np.isfinite(delta).all(1)
         delta = np.where(ok[:, None], delta, 0)
         if mode == FIXED:
@@ -160,6 +160,8 @@ def fit_scale(hm, targets, weights=None, limits=None, init=None, init_scale=None
         ta, tm, ts = apply_step(ang[idx], m[idx], s[idx], centroid[idx], delta, None if box is None else box[idx])
         tc, tw = cost_of(ta, tm, ts, idx)
         accept = ok & np.isfinite(tc) & (tc < cost[idx])
+        if trace is not None:
+            trace.append(fc.trial_record(idx, lam, delta, cost, tc, accept))
         step_small = (np.abs(ta - ang[idx]).max(1) <= fc.STEP_TOL) & (np.abs(delta[:, 20:23]).max(1) <= fc.STEP_TOL) & \
                      (np.abs(delta[:, 23:26]).max(1) <= dt(fc.STEP_TOL) * extent[idx]) & (np.abs(delta[:, 26]) <= fc.STEP_TOL)
         flat = ~accept | (cost[idx] - tc <= dt(fc.DECREASE_TOL) * cost[idx])
