@@ -96,6 +96,12 @@ _INFO_PROTOTYPES = {
                                 _i32, _vp, _vp]),
 }
 INFO_EXPORTS = tuple(_INFO_PROTOTYPES)
+# The entry of include/umetrack_hip_views.h, in a table of its own like its header (tests/test_views_host.py pins it).
+_VIEWS_PROTOTYPES = {
+    "ut_fit_pose_views": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _f32, _i32,
+                                 _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+}
+VIEWS_EXPORTS = tuple(_VIEWS_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -120,7 +126,7 @@ def load_library() -> ctypes.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
-                                      **_INFO_PROTOTYPES}.items():
+                                      **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -650,6 +656,81 @@ def _triangulate_points(window, cam_rows, table, weights, max_iters, out, engine
             rc = lib.ut_triangulate_points_info(*args, _ptr(sqrt_info), _stream(d))
     _check_rc(lib, h, rc, "ut_triangulate_points_info" if factor else "ut_triangulate_points", "points")
     return points, info, residual, sqrt_info
+
+
+def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                   init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                   limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                   max_iters: int = 32, *, n: Optional[int] = None, init_ja_stride: int = 22, init_xf_stride: int = 16,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22, xf_stride: int = 16,
+                   info: Optional[torch.Tensor] = None, residual=False, engine: Optional["HipEngine"] = None):
+    """ut_fit_pose_views: the pose whose landmarks, projected into the views, meet the detections - fit_pose on the
+    reprojection cost sum_v sum_l w_vl |project_v(landmark_l) - window_vl|^2 instead of 3-D targets.  window f64 [n,V,21,2] px,
+    cam_rows i32 [n,V] (-1 = unused view), table f64 [R,32] Fisheye62 source cameras or [R,24] pinhole crop cameras (told apart
+    by the row length), weights f32 [n,V,21] >= 0 or None = all 1 (a window of weight 0 is not read: it may be NaN); V <=
+    TRI_MAX_VIEWS.  init_angles [n,22] / init_wrist_xf [n,4,4] are required: the previous frame's pose, or fit_pose on the
+    triangulated landmarks.  hand_model, limits, mirror, t_scale, the strided form (n, init_*_stride, out, *_stride) and the
+    pose outputs as for fit_pose.  Returns (joint_angles, wrist_xf, info [n,4]: rms reprojection residual px, largest
+    reprojection distance px, iterations, status bits UT_FIT_*) and, with residual=True or a preallocated f32 [n,V,21], the
+    reprojection distance of every used observation as a fourth item.  A cam_rows entry outside [-1, R) raises IndexError and
+    writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks."""
+    if init_angles is None or init_wrist_xf is None:
+        raise ValueError("init_angles and init_wrist_xf are required: ut_fit_pose_views has no cold start")
+    if window.dim() != 4 or tuple(window.shape[2:]) != (21, 2) or window.dtype != torch.float64:
+        raise ValueError(f"window must be f64 [n,V,21,2], got {window.dtype} {tuple(window.shape)}")
+    nw, v = window.shape[:2]
+    if not 1 <= v <= TRI_MAX_VIEWS:
+        raise ValueError(f"window [n,V,21,2] needs 1 <= V <= {TRI_MAX_VIEWS}, got V = {v}")
+    if table.dim() != 2 or table.shape[1] not in (24, 32) or table.shape[0] < 1 or table.dtype != torch.float64:
+        raise ValueError(f"table must be f64 [R,32] source cameras or [R,24] crop cameras, got {table.dtype} {tuple(table.shape)}")
+    if cam_rows.dtype != torch.int32 or tuple(cam_rows.shape) != (nw, v):
+        raise ValueError(f"cam_rows must be i32 [{nw},{v}], got {cam_rows.dtype} {tuple(cam_rows.shape)}")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (nw, v, 21)):
+        raise ValueError(f"weights must be f32 [{nw},{v},21], got {weights.dtype} {tuple(weights.shape)}")
+    kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
+    lib = load_library()
+    d = _hip_device(window, "fit_pose_views")
+    window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
+    if weights is not None:
+        weights = _need(weights, torch.float32, d, "weights")
+    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
+    if n is None:
+        n = nw
+        init_angles = _need(init_angles, torch.float32, d, "init_angles").reshape(-1, 22)
+        init_wrist_xf = _need(init_wrist_xf, torch.float32, d, "init_wrist_xf").reshape(-1, 16)
+        if init_angles.shape[0] != n or init_wrist_xf.shape[0] != n:
+            raise ValueError("init_angles / init_wrist_xf batch mismatch")
+        if out is not None:
+            out = (_out(out[0], (n, 22), torch.float32, d, "out[0]"), _out(out[1], (n, 4, 4), torch.float32, d, "out[1]"))
+    else:
+        views = [init_angles, init_wrist_xf] + list(out or ())
+        if n != nw or out is None or any(t.device != d or t.dtype != torch.float32 for t in views):
+            raise ValueError(f"strided views must be fp32 on {d}, n the windows' batch, and `out` must be given with them")
+    if out is None:
+        out = (torch.empty(n, 22, dtype=torch.float32, device=d), torch.empty(n, 4, 4, dtype=torch.float32, device=d))
+    if hand_model.shape[0] not in (1, n) and n:
+        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
+    if limits is not None:
+        limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
+        if limits.shape[0] != hand_model.shape[0]:
+            raise ValueError(f"limits has {limits.shape[0]} rows for {hand_model.shape[0]} model rows")
+    if mirror is not None:
+        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
+        if mirror.shape[0] != n:
+            raise ValueError("mirror batch mismatch")
+    info = _out(info, (n, 4), torch.float32, d, "info")
+    if residual is True or isinstance(residual, torch.Tensor):
+        residual = _out(None if residual is True else residual, (n, v, 21), torch.float32, d, "residual")
+    else:
+        residual = None
+    h = engine._h if engine is not None else None
+    with torch.cuda.device(d):
+        rc = lib.ut_fit_pose_views(h, _ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v,
+                                   _ptr(table), table.shape[0], kind, _ptr(limits), _ptr(init_angles), init_ja_stride,
+                                   _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale), int(max_iters), n,
+                                   _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride, _ptr(info), _ptr(residual), _stream(d))
+    _check_rc(lib, h, rc, "ut_fit_pose_views", "points")
+    return (out[0], out[1], info) if residual is None else (out[0], out[1], info, residual)
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

@@ -6,6 +6,7 @@
 #include "../../include/umetrack_hip_info.h"
 #include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_triangulate.h"
+#include "../../include/umetrack_hip_views.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -1175,15 +1176,19 @@ int fail_as(ut_handle h, const char* who, const char* what) {
   return fail(h, UT_E_INVALID, msg);
 }
 
-// The argument checks the three pose fits share; `who` names the entry in the message.
+// The argument checks the pose fits share; `who` names the entry in the message.  with_targets false: ut_fit_pose_views, which has
+// no 3-D targets and needs its start.
 int fit_pose_args(ut_handle h, const char* who, const float* hand_model, int n_models, const float* targets, int target_stride,
                   const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride, float t_scale,
-                  int max_iters, int n, const float* joint_angles, int ja_stride, const float* wrist_xf, int xf_stride) {
-  if (!hand_model || !targets || !joint_angles || !wrist_xf || n < 0 || (n_models != 1 && n_models != n))
+                  int max_iters, int n, const float* joint_angles, int ja_stride, const float* wrist_xf, int xf_stride,
+                  bool with_targets = true) {
+  if (!hand_model || (with_targets && !targets) || !joint_angles || !wrist_xf || n < 0 || (n_models != 1 && n_models != n))
     return fail_as(h, who, "bad argument");
+  if (!with_targets && (!init_angles || !init_wrist_xf))
+    return fail_as(h, who, "init_angles and init_wrist_xf are required: there is no cold start");
   if ((init_angles == nullptr) != (init_wrist_xf == nullptr))
     return fail_as(h, who, "init_angles and init_wrist_xf must both be given or both be NULL");
-  if (target_stride < 63 || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
+  if ((with_targets && target_stride < 63) || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
     return fail_as(h, who, "a stride is below 63 (targets) / 22 (angles) / 12 (wrist)");
   if (max_iters < 1 || max_iters > 256) return fail_as(h, who, "max_iters must be in 1..256");
   if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f)) return fail_as(h, who, "t_scale must be positive and finite");
@@ -1484,6 +1489,40 @@ int ut_triangulate_points_info(ut_handle h, const double* window, const float* w
   if (!sqrt_info) return fail(h, UT_E_INVALID, "ut_triangulate_points_info: null argument");
   return triangulate_points(h, "ut_triangulate_points_info", window, weights, cam_rows, max_views, table, n_rows, table_kind,
                             n_points, n, max_iters, points, points_f32, point_stride, info, residual, sqrt_info, stream);
+}
+
+int ut_fit_pose_views(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
+                      const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind, const float* limits,
+                      const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
+                      const int64_t* mirror, float t_scale, int max_iters, int n, float* joint_angles, int ja_stride,
+                      float* wrist_xf, int xf_stride, float* info, float* residual, void* stream) {
+  const char* who = "ut_fit_pose_views";
+  if (!window || !cam_rows || !table) return fail_as(h, who, "null argument");
+  if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
+    return fail_as(h, who, "table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
+  if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS) return fail_as(h, who, "max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
+  if (n_rows < 1) return fail_as(h, who, "bad argument");
+  const int rc = fit_pose_args(h, who, hand_model, n_models, nullptr, 0, init_angles, init_ja_stride, init_wrist_xf,
+                               init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride, false);
+  if (rc) return rc;
+  if (n == 0) return UT_OK;
+  if (h) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, window) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device != h->device)
+      return fail_as(h, who, "the windows live on another device than the handle");
+  }
+  StatusTarget st;
+  const int rs = status_target(h, &st);
+  if (rs) return rs;
+  DeviceScope scope(st.device);
+  if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
+  hipStream_t s = (hipStream_t)stream;
+  const ut::FitViewsArgs a{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride,
+                            mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                           window, weights, cam_rows, max_views, table, n_rows,
+                           table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE, info, residual, st.dev};
+  HIPCHK(h, ut::launch_fit_pose_views(a, s));
+  return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, who) : UT_OK;
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

@@ -1,4 +1,4 @@
-// The pose fits' solver, written once: fit.hip, fit_scale.hip and fit_info.hip each describe a cost and instantiate it.
+// The pose fits' solver, written once: fit.hip, fit_scale.hip, fit_info.hip and fit_views.hip each describe a cost and instantiate it.
 //
 // Levenberg-Marquardt on NP parameters (20 angle increments, a wrist rotation about the weighted centroid of the targets, a
 // wrist translation, then whatever the problem adds) and 63 residual rows, Marquardt's diagonal scaling with a floor, Cholesky
@@ -33,9 +33,15 @@
 //   trial       what else a trial changes; whether that change is small
 //   keep        the trial's extra state becomes the accepted one
 //   report      what is written besides the pose and the wrist
+// A problem without 3-D targets (fit_views.hip) declares `static constexpr bool PIVOT_FROM_START = true`: nothing is read
+// through FitPoseArgs::targets, S.target stays 0, and the pivot of the wrist increment and the extent behind the translation's
+// step tolerance are the weighted centroid and extent of the START's landmarks.  Compile time only: the other problems
+// compile to what they compiled to without it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include <type_traits>
 
 #include "ut_fk.h"
 #include "ut_kernels.h"
@@ -161,6 +167,20 @@ __device__ inline void rodrigues(float vx, float vy, float vz, float* r) {
 
 // ---- start
 
+template <class P, class = void>
+struct fit_pivot_from_start : std::false_type {};
+template <class P>
+struct fit_pivot_from_start<P, std::void_t<decltype(P::PIVOT_FROM_START)>> : std::bool_constant<P::PIVOT_FROM_START> {};
+
+// The weighted centroid and extent of 21 points `q` in LDS: the targets', or the start's landmarks' (PIVOT_FROM_START).
+__device__ inline void fit_pivot(const float (*q)[3], int lane, FitState& st) {
+  const float wl = st.wl, wsum = st.wsum;
+  const float tx = lane < 21 ? q[lane][0] : 0.f, ty = lane < 21 ? q[lane][1] : 0.f, tz = lane < 21 ? q[lane][2] : 0.f;
+  const float cx = wave_sum(wl * tx) / wsum, cy = wave_sum(wl * ty) / wsum, cz = wave_sum(wl * tz) / wsum;
+  st.extent = sqrtf(wave_sum(wl * ((tx - cx) * (tx - cx) + (ty - cy) * (ty - cy) + (tz - cz) * (tz - cz))) / wsum);
+  st.cx = cx; st.cy = cy; st.cz = cz;
+}
+
 // The model, the landmarks (P::load, then the targets of used ones: others are never read), the box, the start and the refusal
 // rules: a weight, factor or target of a used landmark that is not finite, fewer than three used landmarks.  Then the weighted
 // centroid and extent of the targets.
@@ -174,10 +194,12 @@ __device__ inline void fit_load(P& prob, typename P::Lds& S, const FitPoseArgs& 
   bool bad = !prob.load(S, i, mrow, lane, st.wl, st.used);
   if (lane < 21) {
     float tx = 0.f, ty = 0.f, tz = 0.f;
-    if (!bad && st.used) {
-      const float* t = a.targets + (size_t)i * a.target_stride + 3 * lane;
-      tx = t[0]; ty = t[1]; tz = t[2];
-      bad = !(fabsf(tx) <= 3.0e38f) || !(fabsf(ty) <= 3.0e38f) || !(fabsf(tz) <= 3.0e38f);
+    if constexpr (!fit_pivot_from_start<P>::value) {
+      if (!bad && st.used) {
+        const float* t = a.targets + (size_t)i * a.target_stride + 3 * lane;
+        tx = t[0]; ty = t[1]; tz = t[2];
+        bad = !(fabsf(tx) <= 3.0e38f) || !(fabsf(ty) <= 3.0e38f) || !(fabsf(tz) <= 3.0e38f);
+      }
     }
     if (bad) { st.wl = 0.f; st.used = false; }
     S.w[lane] = st.wl;
@@ -204,13 +226,8 @@ __device__ inline void fit_load(P& prob, typename P::Lds& S, const FitPoseArgs& 
   st.keep_start = st.warm;
   st.wsum = wave_sum(st.wl);
   wave_sync();
-  if (!st.refused) {
-    const float wl = st.wl, wsum = st.wsum;
-    const float tx = lane < 21 ? S.target[lane][0] : 0.f, ty = lane < 21 ? S.target[lane][1] : 0.f,
-                tz = lane < 21 ? S.target[lane][2] : 0.f;
-    const float cx = wave_sum(wl * tx) / wsum, cy = wave_sum(wl * ty) / wsum, cz = wave_sum(wl * tz) / wsum;
-    st.extent = sqrtf(wave_sum(wl * ((tx - cx) * (tx - cx) + (ty - cy) * (ty - cy) + (tz - cz) * (tz - cz))) / wsum);
-    st.cx = cx; st.cy = cy; st.cz = cz;
+  if constexpr (!fit_pivot_from_start<P>::value) {
+    if (!st.refused) fit_pivot(S.target, lane, st);
   }
 }
 
@@ -445,6 +462,7 @@ __device__ inline void fit_pose(P& prob, typename P::Lds& S, const FitPoseArgs& 
   if (!st.refused && !st.warm) fit_cold_start(S, lane, st);
   if (!st.refused) {
     const float iso = fit_eval(S, S.ang, S.wrist, lane, st.worst);
+    if constexpr (fit_pivot_from_start<P>::value) fit_pivot(S.p, lane, st);
     st.cost = prob.cost(S, lane, st.used, iso);
     if (!(st.cost <= 3.0e38f)) { st.refused = true; st.keep_start = false; }      // a start that is not finite
   }

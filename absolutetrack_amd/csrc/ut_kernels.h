@@ -299,8 +299,8 @@ hipError_t launch_fk(const float* hand_model, int n_models, const float* ja, int
                      const float* xf, int xf_stride, const int64_t* mirror, float t_scale, int n,
                      float* out, hipStream_t s);
 
-// Poses from landmarks, the inverse of launch_fk: one Levenberg-Marquardt solver (ut_fit_dev.h), one wave per pose, under three
-// costs.  FitPoseArgs is what the three entries share; pointers as ut_fit_pose documents them.
+// Poses from landmarks, the inverse of launch_fk: one Levenberg-Marquardt solver (ut_fit_dev.h), one wave per pose, under four
+// costs.  FitPoseArgs is what the four entries share; pointers as ut_fit_pose documents them.
 struct FitPoseArgs {
   const float* hand_model; int n_models;
   const float* targets; int target_stride;
@@ -331,6 +331,22 @@ struct FitInfoArgs {
   float* info;                          // [n,4] or null
 };
 hipError_t launch_fit_pose_info(const FitInfoArgs& a, hipStream_t s);
+
+// fit_views.hip: no 3-D targets (pose.targets is null), the cost is the reprojection error of the landmarks in camera views.
+// Pointers as ut_fit_pose_views documents them; kind is PROJECT_FISHEYE62 or PROJECT_PINHOLE, max_views 1..TRI_MAX_VIEWS (below).
+struct FitViewsArgs {
+  FitPoseArgs pose;
+  const double* window;                 // [n,max_views,21,2]
+  const float* weights;                 // [n,max_views,21] or null
+  const int32_t* cam_rows;              // [n,max_views] row of `table`, -1 = unused view
+  int max_views;
+  const double* table;                  // [n_rows,32] or [n_rows,24]
+  int n_rows, kind;
+  float* info;                          // [n,4] or null
+  float* residual;                      // [n,max_views,21] or null
+  int* status;                          // sticky status word: UT_BAD_SRC_INDEX for a cam_rows entry outside [-1, n_rows)
+};
+hipError_t launch_fit_pose_views(const FitViewsArgs& a, hipStream_t s);
 
 // fit_scale.hip: fit.hip's cost with ln(scale) of the hand as a 27th parameter, and the pool of per-pose scales, one wave per
 // group.  Pointers as ut_fit_pose_scale / ut_pool_scale document them; the constants are public as UT_SCALE_* / UT_FITS_*.

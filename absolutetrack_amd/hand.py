@@ -235,6 +235,47 @@ def fit_landmarks_info(hand_model: HandModel, landmarks: torch.Tensor, sqrt_info
             info.reshape(lead + (4,)).to(src_device))
 
 
+def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, init,
+                        weights: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, limits=None,
+                        max_iters: int = 32, with_residual: bool = False):
+    """fit_landmarks on 2-D keypoints in camera views instead of 3-D landmarks, on the HIP kernel csrc/fit_views.hip (no CPU
+    implementation): the pose that minimises sum_v sum_l w_vl |project_v(landmark_l) - window_vl|^2 through the exact camera
+    model.  window f64 [...,V,21,2] px; cam_rows i32 [...,V] rows of `table`, -1 = unused view; table f64 [R,32] Fisheye62
+    source cameras or [R,24] pinhole crop cameras; weights [...,V,21] >= 0 or None = all 1 - a detection of weight 0 is not
+    read and may be NaN.  Every detection counts, also of a landmark that one camera alone sees, and one view is enough.
+    init = (joint_angles [...,22], wrist_transforms [...,4,4]) is required - the previous frame's pose, or fit_landmarks on
+    the triangulated landmarks: without 3-D targets there is nothing to align a cold start to.  limits: true keeps the
+    angles inside hand_model.joint_limits.  Returns (joint_angles [...,22], wrist_transforms [...,4,4], info [...,4]: rms
+    reprojection residual px, largest reprojection distance px, iterations, status as for fit_landmarks) and, with
+    with_residual=True, the reprojection distance [...,V,21] of every used detection - zero an outlier's weight and call
+    again.  Leading dims, devices and mirror as for fit_landmarks."""
+    if init is None:
+        raise ValueError("init = (joint_angles, wrist_transforms) is required: fit_landmarks_views has no cold start")
+    if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
+        raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
+    lead, v = tuple(window.shape[:-3]), window.shape[-3]
+    n = int(np.prod(lead)) if lead else 1
+    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
+    if model_lead not in ((), lead):
+        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
+    if limits and hand_model.joint_limits is None:
+        raise ValueError("limits needs hand_model.joint_limits")
+    src_device = window.device
+    dev = src_device if src_device.type == "cuda" else fk_device()
+
+    def dev32(t, tail):
+        return None if t is None else t.reshape((n,) + tail).to(dev, torch.float32)
+    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
+    res = _native.fit_pose_views(device_blob(hand_model, dev), window.reshape(n, v, 21, 2).to(dev, torch.float64),
+                                 cam_rows.reshape(n, v).to(dev, torch.int32), table.to(dev, torch.float64),
+                                 dev32(init[0], (22,)), dev32(init[1], (4, 4)), dev32(weights, (v, 21)), box,
+                                 None if mirror is None else mirror.reshape(n).to(dev, torch.int64), max_iters=max_iters,
+                                 residual=with_residual)
+    out = (res[0].reshape(lead + (22,)).to(src_device), res[1].reshape(lead + (4, 4)).to(src_device),
+           res[2].reshape(lead + (4,)).to(src_device))
+    return out + (res[3].reshape(lead + (v, 21)).to(src_device),) if with_residual else out
+
+
 FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FITS_CONVERGED, _native.UT_FITS_AT_MAX_ITERS,
                                                                   _native.UT_FITS_REFUSED, _native.UT_FITS_AT_BOUND)
 

@@ -228,6 +228,23 @@ def triangulate_keypoints(window: torch.Tensor, cam_params: torch.Tensor, src_ro
                  point_stride=point_stride)
 
 
+def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
+                           init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                           mirror: Optional[torch.Tensor] = None, limits: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                           max_iters: int = 32, with_residual: bool = False, engine: Optional[_native.HipEngine] = None, **strided):
+    """Batched tracker.refine_hand_pose_in_views over frames and hands: the poses of n hand-samples whose landmarks meet their
+    window keypoints in the cameras that see them, ONE ut_fit_pose_views launch.  hand_model f32 [1|n,321] packed models
+    (hand.device_blob); window f64 [n,V,21,2] px on the device (what project_keypoints returns, or detections); cam_params f64
+    [R,32] (FrameBatch.cam_params) or [R,24] crop cameras; src_row i32 [n,V] rows of cam_params per view, -1 where unused;
+    init_angles [n,22] / init_wrist_xf [n,4,4]: the start, required - the previous frame's poses or _native.fit_pose on
+    triangulate_keypoints' points; weights f32 [n,V,21] or None, e.g. (flags == 3).float() of project_keypoints or detection
+    confidences, 0 where a landmark is not seen.  **strided: n, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride of
+    _native.fit_pose_views - poses inside HotPath records, read and written in place.  Returns (joint_angles, wrist_xf, info
+    f32 [n,4]) and, with with_residual=True, residual f32 [n,V,21]."""
+    return _native.fit_pose_views(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, weights=weights, limits=limits,
+                                  mirror=mirror, t_scale=t_scale, max_iters=max_iters, residual=with_residual, engine=engine, **strided)
+
+
 def view_rows(src_index: torch.Tensor, sample_range: torch.Tensor, max_views: int = MAX_VIEW_NUM) -> torch.Tensor:
     """[S,max_views] i32: the entries of a per-crop tensor (FrameBatch.src_index, or arange(n_crops) for the crop cameras
     themselves) that belong to each sample's views, -1 where the sample has fewer - the cam_rows of project_keypoints."""
