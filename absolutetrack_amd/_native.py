@@ -325,17 +325,17 @@ def fit_pose_info(hand_model: torch.Tensor, targets: torch.Tensor, sqrt_info: to
                      max_iters, n, target_stride, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride, info, engine)
 
 
-def _fit_pose(entry, hand_model, targets, weights, limits, init_angles, init_wrist_xf, mirror, t_scale, max_iters, n,
-              target_stride, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride, info, engine):
-    """fit_pose and fit_pose_info: `weights` is [n,21] for ut_fit_pose, the factors [n,21,6] for ut_fit_pose_info."""
-    lib = load_library()
-    d = _hip_device(targets, entry[3:])
+def _fit_args(d, hand_model, init_angles, init_wrist_xf, n, batch, strided, out, limits, mirror, engine, windows=False):
+    """What the four pose fits marshal alike, on device d: hand_model as [1|n,321]; the init pair, both or neither; the packed
+    form (n None: n = batch, the init as [n,22] / [n,16], `out` checked or fresh) against the strided form (n given: the views
+    `strided`, the init and `out` are fp32 on d and used in place, `out` is required and, with windows=True, n is the windows'
+    batch); limits as one [20,2] row per model row; mirror [n]; the engine's handle.  Returns (hand_model, init_angles,
+    init_wrist_xf, n, out, limits, mirror, handle)."""
     hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
     if (init_angles is None) != (init_wrist_xf is None):
         raise ValueError("init_angles and init_wrist_xf go together")
     if n is None:
-        targets = _need(targets, torch.float32, d, "targets").reshape(-1, 63)
-        n = targets.shape[0]
+        n = batch
         if init_angles is not None:
             init_angles = _need(init_angles, torch.float32, d, "init_angles").reshape(-1, 22)
             init_wrist_xf = _need(init_wrist_xf, torch.float32, d, "init_wrist_xf").reshape(-1, 16)
@@ -344,18 +344,14 @@ def _fit_pose(entry, hand_model, targets, weights, limits, init_angles, init_wri
         if out is not None:
             out = (_out(out[0], (n, 22), torch.float32, d, "out[0]"), _out(out[1], (n, 4, 4), torch.float32, d, "out[1]"))
     else:
-        views = [targets] + ([] if init_angles is None else [init_angles, init_wrist_xf]) + list(out or ())
-        if out is None or any(v.device != d or v.dtype != torch.float32 for v in views):
-            raise ValueError(f"strided views must be fp32 on {d}, and `out` must be given with them")
+        views = list(strided) + ([] if init_angles is None else [init_angles, init_wrist_xf]) + list(out or ())
+        if (windows and n != batch) or out is None or any(v.device != d or v.dtype != torch.float32 for v in views):
+            also = "n the windows' batch, " if windows else ""
+            raise ValueError(f"strided views must be fp32 on {d}, {also}and `out` must be given with them")
     if out is None:
         out = (torch.empty(n, 22, dtype=torch.float32, device=d), torch.empty(n, 4, 4, dtype=torch.float32, device=d))
     if hand_model.shape[0] not in (1, n) and n:
         raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
-    if weights is not None:
-        name, shape = ("weights", (n, 21)) if entry == "ut_fit_pose" else ("sqrt_info", (n, 21, 6))
-        weights = _need(weights, torch.float32, d, name)
-        if tuple(weights.shape) != shape:
-            raise ValueError(f"{name} must be [{','.join(map(str, shape))}], got {tuple(weights.shape)}")
     if limits is not None:
         limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
         if limits.shape[0] != hand_model.shape[0]:
@@ -364,14 +360,34 @@ def _fit_pose(entry, hand_model, targets, weights, limits, init_angles, init_wri
         mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
         if mirror.shape[0] != n:
             raise ValueError("mirror batch mismatch")
-    info = _out(info, (n, 4), torch.float32, d, "info")
-    h = engine._h if engine is not None else None
+    return hand_model, init_angles, init_wrist_xf, n, out, limits, mirror, engine._h if engine is not None else None
+
+
+def _fit_call(entry, d, h, *args):
+    """The C entry of a pose fit on d's current stream; a negative return code raises."""
+    lib = load_library()
     with torch.cuda.device(d):
-        rc = getattr(lib, entry)(h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights), _ptr(limits),
-                                 _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror),
-                                 ctypes.c_float(t_scale), int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride,
-                                 _ptr(info), _stream(d))
+        rc = getattr(lib, entry)(h, *args, _stream(d))
     _check_rc(lib, h, rc, entry, "points")
+
+
+def _fit_pose(entry, hand_model, targets, weights, limits, init_angles, init_wrist_xf, mirror, t_scale, max_iters, n,
+              target_stride, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride, info, engine):
+    """fit_pose and fit_pose_info: `weights` is [n,21] for ut_fit_pose, the factors [n,21,6] for ut_fit_pose_info."""
+    d = _hip_device(targets, entry[3:])
+    if n is None:
+        targets = _need(targets, torch.float32, d, "targets").reshape(-1, 63)
+    hand_model, init_angles, init_wrist_xf, n, out, limits, mirror, h = _fit_args(
+        d, hand_model, init_angles, init_wrist_xf, n, targets.shape[0], [targets], out, limits, mirror, engine)
+    if weights is not None:
+        name, shape = ("weights", (n, 21)) if entry == "ut_fit_pose" else ("sqrt_info", (n, 21, 6))
+        weights = _need(weights, torch.float32, d, name)
+        if tuple(weights.shape) != shape:
+            raise ValueError(f"{name} must be [{','.join(map(str, shape))}], got {tuple(weights.shape)}")
+    info = _out(info, (n, 4), torch.float32, d, "info")
+    _fit_call(entry, d, h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights), _ptr(limits),
+              _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale),
+              int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride, _ptr(info))
     return out[0], out[1], info
 
 
@@ -392,54 +408,25 @@ def fit_pose_scale(hand_model: torch.Tensor, targets: torch.Tensor, weights: Opt
     weighted rms residual, worst residual, iterations, status bits UT_FITS_*, scale information, 0).  init_scale [n] or None
     (= 1); scale_mode UT_SCALE_FREE fits the scale, UT_SCALE_FIXED keeps init_scale.  Every other argument as for fit_pose,
     strided views included; `scale` and `info` may be the caller's buffers."""
-    lib = load_library()
     d = _hip_device(targets, "fit_pose_scale")
-    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
-    if (init_angles is None) != (init_wrist_xf is None):
-        raise ValueError("init_angles and init_wrist_xf go together")
     if n is None:
         targets = _need(targets, torch.float32, d, "targets").reshape(-1, 63)
-        n = targets.shape[0]
-        if init_angles is not None:
-            init_angles = _need(init_angles, torch.float32, d, "init_angles").reshape(-1, 22)
-            init_wrist_xf = _need(init_wrist_xf, torch.float32, d, "init_wrist_xf").reshape(-1, 16)
-            if init_angles.shape[0] != n or init_wrist_xf.shape[0] != n:
-                raise ValueError("init_angles / init_wrist_xf batch mismatch")
-        if out is not None:
-            out = (_out(out[0], (n, 22), torch.float32, d, "out[0]"), _out(out[1], (n, 4, 4), torch.float32, d, "out[1]"))
-    else:
-        views = [targets] + ([] if init_angles is None else [init_angles, init_wrist_xf]) + list(out or ())
-        if out is None or any(v.device != d or v.dtype != torch.float32 for v in views):
-            raise ValueError(f"strided views must be fp32 on {d}, and `out` must be given with them")
-    if out is None:
-        out = (torch.empty(n, 22, dtype=torch.float32, device=d), torch.empty(n, 4, 4, dtype=torch.float32, device=d))
-    if hand_model.shape[0] not in (1, n) and n:
-        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
+    hand_model, init_angles, init_wrist_xf, n, out, limits, mirror, h = _fit_args(
+        d, hand_model, init_angles, init_wrist_xf, n, targets.shape[0], [targets], out, limits, mirror, engine)
     if weights is not None:
         weights = _need(weights, torch.float32, d, "weights")
         if tuple(weights.shape) != (n, 21):
             raise ValueError(f"weights must be [{n},21], got {tuple(weights.shape)}")
-    if limits is not None:
-        limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
-        if limits.shape[0] != hand_model.shape[0]:
-            raise ValueError(f"limits has {limits.shape[0]} rows for {hand_model.shape[0]} model rows")
     if init_scale is not None:
         init_scale = _need(init_scale, torch.float32, d, "init_scale").reshape(-1)
         if init_scale.shape[0] != n:
             raise ValueError("init_scale batch mismatch")
-    if mirror is not None:
-        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
-        if mirror.shape[0] != n:
-            raise ValueError("mirror batch mismatch")
     scale = _out(scale, (n,), torch.float32, d, "scale")
     info = _out(info, (n, 6), torch.float32, d, "info")
-    h = engine._h if engine is not None else None
-    with torch.cuda.device(d):
-        rc = lib.ut_fit_pose_scale(h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights),
-                                   _ptr(limits), _ptr(init_scale), int(scale_mode), _ptr(init_angles), init_ja_stride,
-                                   _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale), int(max_iters),
-                                   n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride, _ptr(scale), _ptr(info), _stream(d))
-    _check_rc(lib, h, rc, "ut_fit_pose_scale", "points")
+    _fit_call("ut_fit_pose_scale", d, h, _ptr(hand_model), hand_model.shape[0], _ptr(targets), target_stride, _ptr(weights),
+              _ptr(limits), _ptr(init_scale), int(scale_mode), _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf),
+              init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale), int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]),
+              xf_stride, _ptr(scale), _ptr(info))
     return out[0], out[1], scale, info
 
 
@@ -688,48 +675,21 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
     if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (nw, v, 21)):
         raise ValueError(f"weights must be f32 [{nw},{v},21], got {weights.dtype} {tuple(weights.shape)}")
     kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
-    lib = load_library()
     d = _hip_device(window, "fit_pose_views")
     window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
     if weights is not None:
         weights = _need(weights, torch.float32, d, "weights")
-    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
-    if n is None:
-        n = nw
-        init_angles = _need(init_angles, torch.float32, d, "init_angles").reshape(-1, 22)
-        init_wrist_xf = _need(init_wrist_xf, torch.float32, d, "init_wrist_xf").reshape(-1, 16)
-        if init_angles.shape[0] != n or init_wrist_xf.shape[0] != n:
-            raise ValueError("init_angles / init_wrist_xf batch mismatch")
-        if out is not None:
-            out = (_out(out[0], (n, 22), torch.float32, d, "out[0]"), _out(out[1], (n, 4, 4), torch.float32, d, "out[1]"))
-    else:
-        views = [init_angles, init_wrist_xf] + list(out or ())
-        if n != nw or out is None or any(t.device != d or t.dtype != torch.float32 for t in views):
-            raise ValueError(f"strided views must be fp32 on {d}, n the windows' batch, and `out` must be given with them")
-    if out is None:
-        out = (torch.empty(n, 22, dtype=torch.float32, device=d), torch.empty(n, 4, 4, dtype=torch.float32, device=d))
-    if hand_model.shape[0] not in (1, n) and n:
-        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} poses")
-    if limits is not None:
-        limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
-        if limits.shape[0] != hand_model.shape[0]:
-            raise ValueError(f"limits has {limits.shape[0]} rows for {hand_model.shape[0]} model rows")
-    if mirror is not None:
-        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
-        if mirror.shape[0] != n:
-            raise ValueError("mirror batch mismatch")
+    hand_model, init_angles, init_wrist_xf, n, out, limits, mirror, h = _fit_args(
+        d, hand_model, init_angles, init_wrist_xf, n, nw, [], out, limits, mirror, engine, windows=True)
     info = _out(info, (n, 4), torch.float32, d, "info")
     if residual is True or isinstance(residual, torch.Tensor):
         residual = _out(None if residual is True else residual, (n, v, 21), torch.float32, d, "residual")
     else:
         residual = None
-    h = engine._h if engine is not None else None
-    with torch.cuda.device(d):
-        rc = lib.ut_fit_pose_views(h, _ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v,
-                                   _ptr(table), table.shape[0], kind, _ptr(limits), _ptr(init_angles), init_ja_stride,
-                                   _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale), int(max_iters), n,
-                                   _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride, _ptr(info), _ptr(residual), _stream(d))
-    _check_rc(lib, h, rc, "ut_fit_pose_views", "points")
+    _fit_call("ut_fit_pose_views", d, h, _ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v,
+              _ptr(table), table.shape[0], kind, _ptr(limits), _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf),
+              init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale), int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]),
+              xf_stride, _ptr(info), _ptr(residual))
     return (out[0], out[1], info) if residual is None else (out[0], out[1], info, residual)
 
 

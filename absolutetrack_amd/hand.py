@@ -161,6 +161,41 @@ def skin_landmarks(hand_model: HandModel, joint_angles: torch.Tensor, wrist_tran
 FIT_CONVERGED, FIT_AT_MAX_ITERS, FIT_REFUSED = _native.UT_FIT_CONVERGED, _native.UT_FIT_AT_MAX_ITERS, _native.UT_FIT_REFUSED
 
 
+class _FitStaging:
+    """How the fit_landmarks* wrappers stage a call: the model checked against the leading dims `lead` of the landmarks (or
+    windows), `limits` against the model (`limits_word`: how the wrapper's message names the argument), the device the kernel
+    runs on, the model blob and the box there; f32 / flags flatten an argument to n poses on that device, back gives a result
+    its leading dims again on the source device.  broadcast: arguments are first expanded to the leading dims, so a number or
+    one row stands for all poses - fit_landmarks_scale and calibrate_scale alone."""
+
+    def __init__(self, hand_model: HandModel, lead, src_device, limits, limits_word="limits=True", broadcast=False):
+        self.lead, self.n, self.src_device, self.broadcast = lead, int(np.prod(lead)) if lead else 1, src_device, broadcast
+        model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
+        if model_lead not in ((), lead):
+            raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
+        if limits and hand_model.joint_limits is None:
+            raise ValueError(f"{limits_word} needs hand_model.joint_limits")
+        self.dev = src_device if src_device.type == "cuda" else fk_device()
+        self.box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(self.dev, torch.float32) if limits else None
+        self.blob = device_blob(hand_model, self.dev)
+
+    def f32(self, t, tail, dtype=torch.float32):
+        if t is None:
+            return None
+        if self.broadcast:
+            t = torch.as_tensor(t).expand(self.lead + tail)
+        return t.reshape((self.n,) + tail).to(self.dev, dtype)
+
+    def flags(self, mirror):
+        return self.f32(mirror, (), torch.int64)
+
+    def init(self, init):
+        return (None, None) if init is None else (self.f32(init[0], (22,)), self.f32(init[1], (4, 4)))
+
+    def back(self, t, tail):
+        return t.reshape(self.lead + tail).to(self.src_device)
+
+
 def fit_landmarks(hand_model: HandModel, landmarks: torch.Tensor, weights: Optional[torch.Tensor] = None, init=None,
                   limits: bool = False, mirror: Optional[torch.Tensor] = None, max_iters: int = 32):
     """The inverse of skin_landmarks: [...,21,3] landmarks -> (joint_angles [...,22], wrist_transforms [...,4,4], info
@@ -175,25 +210,10 @@ def fit_landmarks(hand_model: HandModel, landmarks: torch.Tensor, weights: Optio
     returned transform is the proper one a pose holds (column 0 is negated by the consumer).  info: weighted rms residual,
     worst residual, iterations, status - FIT_CONVERGED | FIT_AT_MAX_ITERS | FIT_REFUSED (fewer than 3 weighted landmarks,
     a bad weight or a non-finite weighted landmark: the pose is the init, or the rest pose)."""
-    lead = tuple(landmarks.shape[:-2])
-    n = int(np.prod(lead)) if lead else 1
-    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
-    if model_lead not in ((), lead):
-        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
-    if limits and hand_model.joint_limits is None:
-        raise ValueError("limits=True needs hand_model.joint_limits")
-    src_device = landmarks.device
-    dev = src_device if src_device.type == "cuda" else fk_device()
-
-    def dev32(t, tail):
-        return None if t is None else t.reshape((n,) + tail).to(dev, torch.float32)
-    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
-    ja, xf, info = _native.fit_pose(device_blob(hand_model, dev), dev32(landmarks, (21, 3)), dev32(weights, (21,)), box,
-                                    None if init is None else dev32(init[0], (22,)),
-                                    None if init is None else dev32(init[1], (4, 4)),
-                                    None if mirror is None else mirror.reshape(n).to(dev, torch.int64), max_iters=max_iters)
-    return (ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device),
-            info.reshape(lead + (4,)).to(src_device))
+    s = _FitStaging(hand_model, tuple(landmarks.shape[:-2]), landmarks.device, limits)
+    ja, xf, info = _native.fit_pose(s.blob, s.f32(landmarks, (21, 3)), s.f32(weights, (21,)), s.box, *s.init(init), s.flags(mirror),
+                                    max_iters=max_iters)
+    return s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(info, (4,))
 
 
 def fit_landmarks_info(hand_model: HandModel, landmarks: torch.Tensor, sqrt_info: torch.Tensor, init=None, limits: bool = False,
@@ -209,30 +229,17 @@ def fit_landmarks_info(hand_model: HandModel, landmarks: torch.Tensor, sqrt_info
     [...,22], wrist_transforms [...,4,4], info [...,4]: whitened rms residual - px for triangulated landmarks -, largest
     Euclidean residual, iterations, status as for fit_landmarks).  Everything else as for fit_landmarks."""
     lead = tuple(landmarks.shape[:-2])
-    n = int(np.prod(lead)) if lead else 1
-    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
-    if model_lead not in ((), lead):
-        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
-    if limits and hand_model.joint_limits is None:
-        raise ValueError("limits=True needs hand_model.joint_limits")
     if tuple(sqrt_info.shape) != lead + (21, 6):
         raise ValueError(f"sqrt_info must be {lead + (21, 6)}, got {tuple(sqrt_info.shape)}")
-    src_device = landmarks.device
-    dev = src_device if src_device.type == "cuda" else fk_device()
-
-    def dev32(t, tail):
-        return None if t is None else t.reshape((n,) + tail).to(dev, torch.float32)
-    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
-    blob, targets, factor = device_blob(hand_model, dev), dev32(landmarks, (21, 3)), dev32(sqrt_info, (21, 6))
-    flip = None if mirror is None else mirror.reshape(n).to(dev, torch.int64)
+    s = _FitStaging(hand_model, lead, landmarks.device, limits)
+    targets, factor, flip = s.f32(landmarks, (21, 3)), s.f32(sqrt_info, (21, 6)), s.flags(mirror)
     if init is None:
         used = (factor != 0).any(-1).to(torch.float32)
-        start = _native.fit_pose(blob, targets, used, box, mirror=flip, max_iters=max_iters)[:2]
+        start = _native.fit_pose(s.blob, targets, used, s.box, mirror=flip, max_iters=max_iters)[:2]
     else:
-        start = (dev32(init[0], (22,)), dev32(init[1], (4, 4)))
-    ja, xf, info = _native.fit_pose_info(blob, targets, factor, box, start[0], start[1], flip, max_iters=max_iters)
-    return (ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device),
-            info.reshape(lead + (4,)).to(src_device))
+        start = s.init(init)
+    ja, xf, info = _native.fit_pose_info(s.blob, targets, factor, s.box, start[0], start[1], flip, max_iters=max_iters)
+    return s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(info, (4,))
 
 
 def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, init,
@@ -253,27 +260,13 @@ def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: t
         raise ValueError("init = (joint_angles, wrist_transforms) is required: fit_landmarks_views has no cold start")
     if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
         raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
-    lead, v = tuple(window.shape[:-3]), window.shape[-3]
-    n = int(np.prod(lead)) if lead else 1
-    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
-    if model_lead not in ((), lead):
-        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
-    if limits and hand_model.joint_limits is None:
-        raise ValueError("limits needs hand_model.joint_limits")
-    src_device = window.device
-    dev = src_device if src_device.type == "cuda" else fk_device()
-
-    def dev32(t, tail):
-        return None if t is None else t.reshape((n,) + tail).to(dev, torch.float32)
-    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
-    res = _native.fit_pose_views(device_blob(hand_model, dev), window.reshape(n, v, 21, 2).to(dev, torch.float64),
-                                 cam_rows.reshape(n, v).to(dev, torch.int32), table.to(dev, torch.float64),
-                                 dev32(init[0], (22,)), dev32(init[1], (4, 4)), dev32(weights, (v, 21)), box,
-                                 None if mirror is None else mirror.reshape(n).to(dev, torch.int64), max_iters=max_iters,
-                                 residual=with_residual)
-    out = (res[0].reshape(lead + (22,)).to(src_device), res[1].reshape(lead + (4, 4)).to(src_device),
-           res[2].reshape(lead + (4,)).to(src_device))
-    return out + (res[3].reshape(lead + (v, 21)).to(src_device),) if with_residual else out
+    v = window.shape[-3]
+    s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, limits, "limits")
+    res = _native.fit_pose_views(s.blob, s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32),
+                                 table.to(s.dev, torch.float64), *s.init(init), s.f32(weights, (v, 21)), s.box, s.flags(mirror),
+                                 max_iters=max_iters, residual=with_residual)
+    out = (s.back(res[0], (22,)), s.back(res[1], (4, 4)), s.back(res[2], (4,)))
+    return out + (s.back(res[3], (v, 21)),) if with_residual else out
 
 
 FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FITS_CONVERGED, _native.UT_FITS_AT_MAX_ITERS,
@@ -282,24 +275,10 @@ FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FIT
 
 def _scale_fit_inputs(hand_model: HandModel, landmarks, weights, init, init_scale, limits, mirror):
     """What fit_landmarks_scale and calibrate_scale hand to _native.fit_pose_scale, flattened to n poses on the device."""
-    lead = tuple(landmarks.shape[:-2])
-    n = int(np.prod(lead)) if lead else 1
-    model_lead = tuple(hand_model.joint_rest_positions.shape[:-2])
-    if model_lead not in ((), lead):
-        raise AssertionError(f"Leading dimensions do not match, got {lead} and {model_lead}")
-    if limits and hand_model.joint_limits is None:
-        raise ValueError("limits=True needs hand_model.joint_limits")
-    src_device = landmarks.device
-    dev = src_device if src_device.type == "cuda" else fk_device()
-
-    def dev32(t, tail):
-        return None if t is None else torch.as_tensor(t).expand(lead + tail).reshape((n,) + tail).to(dev, torch.float32)
-    box = hand_model.joint_limits[..., :20, :].reshape(-1, 20, 2).to(dev, torch.float32) if limits else None
-    args = dict(hand_model=device_blob(hand_model, dev), targets=dev32(landmarks, (21, 3)), weights=dev32(weights, (21,)), limits=box,
-                init_scale=dev32(init_scale, ()), init_angles=None if init is None else dev32(init[0], (22,)),
-                init_wrist_xf=None if init is None else dev32(init[1], (4, 4)),
-                mirror=None if mirror is None else torch.as_tensor(mirror).expand(lead).reshape(n).to(dev, torch.int64))
-    return lead, src_device, args
+    s = _FitStaging(hand_model, tuple(landmarks.shape[:-2]), landmarks.device, limits, broadcast=True)
+    ja, xf = s.init(init)
+    return s, dict(hand_model=s.blob, targets=s.f32(landmarks, (21, 3)), weights=s.f32(weights, (21,)), limits=s.box,
+                   init_scale=s.f32(init_scale, ()), init_angles=ja, init_wrist_xf=xf, mirror=s.flags(mirror))
 
 
 def fit_landmarks_scale(hand_model: HandModel, landmarks: torch.Tensor, weights: Optional[torch.Tensor] = None, init=None,
@@ -312,11 +291,10 @@ def fit_landmarks_scale(hand_model: HandModel, landmarks: torch.Tensor, weights:
     without building it.  info: weighted rms residual, worst residual, iterations, status - FITS_CONVERGED |
     FITS_AT_MAX_ITERS | FITS_REFUSED | FITS_AT_BOUND -, scale information (1 / variance of ln scale per unit^2 of landmark
     noise; 0 with fixed=True), 0.  Everything else as for fit_landmarks."""
-    lead, src_device, args = _scale_fit_inputs(hand_model, landmarks, weights, init, init_scale, limits, mirror)
+    s, args = _scale_fit_inputs(hand_model, landmarks, weights, init, init_scale, limits, mirror)
     ja, xf, scale, info = _native.fit_pose_scale(scale_mode=_native.UT_SCALE_FIXED if fixed else _native.UT_SCALE_FREE,
                                                  max_iters=max_iters, **args)
-    return (ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device), scale.reshape(lead).to(src_device),
-            info.reshape(lead + (6,)).to(src_device))
+    return s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(scale, ()), s.back(info, (6,))
 
 
 class ScaleCalibration(NamedTuple):
@@ -343,8 +321,8 @@ def calibrate_scale(hand_model: HandModel, landmarks: torch.Tensor, weights: Opt
     when a group has no usable pose."""
     if landmarks.dim() < 3:
         raise ValueError(f"landmarks must be [...,N,21,3], got {tuple(landmarks.shape)}")
-    lead, src_device, args = _scale_fit_inputs(hand_model, landmarks, weights, None, None, False, mirror)
-    group_lead, n_per = lead[:-1], lead[-1]
+    s, args = _scale_fit_inputs(hand_model, landmarks, weights, None, None, False, mirror)
+    group_lead, n_per = s.lead[:-1], s.lead[-1]
     ja, xf, scale, info = _native.fit_pose_scale(max_iters=max_iters, **args)
     group, pose_scale = _native.pool_scale(scale, info, n_per)
     if refit:
@@ -352,15 +330,14 @@ def calibrate_scale(hand_model: HandModel, landmarks: torch.Tensor, weights: Opt
         ja, xf, pose_scale, info = _native.fit_pose_scale(scale_mode=_native.UT_SCALE_FIXED, max_iters=max_iters, **args)
     else:
         pose_scale = scale
-    stats = group.reshape(group_lead + (4,)).to(src_device)
+    stats = group.reshape(group_lead + (4,)).to(s.src_device)
     if bool((stats[..., 3] == 0).any()):
         raise ValueError("calibrate_scale: a group has no usable pose (none converged away from the scale bounds)")
     pooled = stats[..., 0]
     model = None
     if group_lead == () and hand_model.joint_rest_positions.dim() == 2:
         model = scaled_hand_model(hand_model, float(pooled))
-    return ScaleCalibration(pooled, stats, model, ja.reshape(lead + (22,)).to(src_device), xf.reshape(lead + (4, 4)).to(src_device),
-                            info.reshape(lead + (6,)).to(src_device), pose_scale.reshape(lead).to(src_device))
+    return ScaleCalibration(pooled, stats, model, s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(info, (6,)), s.back(pose_scale, ()))
 
 
 _MESH_FIELDS = ("mesh_vertices", "mesh_triangles", "dense_bone_weights")

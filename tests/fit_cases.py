@@ -188,44 +188,103 @@ def trial_record(idx, lam, delta, cost, trial_cost, accept):
                 accept=accept.copy())
 
 
-def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=1.0, max_iters=32, dtype=np.float64,
-        history=None, trace=None):
-    """Fit B poses: (joint_angles [B,22], wrist_xf [B,4,4] proper, translation in target units / t_scale, info [B,4]:
-    weighted rms residual, worst residual, iterations, status).  targets [B,21,3]; weights [B,21] >= 0 or None; limits
-    [20,2] / [B,20,2] or None; init = (joint_angles [B,22], wrist_xf [B,4,4]) or None for the cold start; mirror [B] of
-    0 / 1.  history: a list that receives (angles, effective wrist) after every iteration.  trace: a list that receives
-    the decision of every iteration (trial_record)."""
+def weighted_targets(targets, weights, dtype, also_refused=False):
+    """The targets as `fit` and scale_cases.fit_scale read them: (w [B,21], 0 where unused and 1 for refused poses; used = w > 0;
+    y [B,21,3], 0 where unused; refused [B]: fewer than 3 weighted landmarks, a negative or non-finite weight, a non-finite
+    target of a weighted landmark, or `also_refused`)."""
     dt = dtype
-    b = targets.shape[0]
-    w = np.ones((b, 21), dt) if weights is None else np.asarray(weights).astype(dt)
+    w = np.ones((targets.shape[0], 21), dt) if weights is None else np.asarray(weights).astype(dt)
     used = w > 0
-    refused = (used.sum(1) < 3) | ~np.isfinite(w).all(1) | (w < 0).any(1) | (~np.isfinite(np.asarray(targets)) & used[..., None]).any((1, 2))
+    refused = (used.sum(1) < 3) | ~np.isfinite(w).all(1) | (w < 0).any(1) | \
+        (~np.isfinite(np.asarray(targets)) & used[..., None]).any((1, 2)) | also_refused
     w = np.where(refused[:, None], dt(1), np.where(used, w, dt(0)))
     used = w > 0
     y = np.where(used[..., None], np.asarray(targets), 0).astype(dt)
     y[refused] = 0
+    return w, used, y, refused
+
+
+class Problem:
+    """A cost as the loop `lm` sees it, shaped like the problem P of csrc/ut_fit_dev.h.  As it stands it is `fit`'s: the
+    weighted distance to 3-D targets (hm; dt the working dtype; w, used, y, refused of weighted_targets).  The other
+    restatements derive from it and replace what differs; `idx` are the poses still active, states are theirs alone.
+      NP                              the parameter count: 20 angles, the wrist increment, then the problem's own
+      model()                         the skeleton the cold start poses
+      cold_start(mir, box)            (angles [B,20], effective wrist [B,4,4]) where a fit without an init starts
+      pivot(ang, m)                   (centroid [B,3] the wrist increment turns about, extent [B] that scales the translation's
+                                      step tolerance, the denominator [B] of info's rms) - of the start ang, m or of the targets
+      system(idx, ang, m, centroid)   the linearised system (J [k,63,NP], r [k,63]) in dt
+      cost(idx, ang, m, extra=None)   (cost [k], worst residual [k]) of a state; extra: a trial's own state in place of the kept
+      trial(idx, delta)               a trial's state beyond angles and wrist (None: there is none); it may edit delta first
+      small(delta)                    what else the step-small rule asks
+      keep(idx, accept, extra)        an accepted trial's own state becomes the kept one
+      report(refused, ang, m, centroid, status)   after the loop: columns of info beyond the four, status bits of its own"""
+    NP = 26
+
+    def __init__(self, hm, dtype, w, used, y, refused):
+        self.hm, self.dt, self.w, self.used, self.y, self.refused = hm, dtype, w, used, y, refused
+
+    def model(self):
+        return self.hm
+
+    def cold_start(self, mir, box):
+        return cold_start(self.model(), self.y, self.w, mir, box, self.dt)
+
+    def pivot(self, ang, m):
+        wsum = self.w.sum(1)
+        centroid = (self.w[..., None] * self.y).sum(1) / wsum[:, None]
+        extent = np.sqrt((self.w * ((self.y - centroid[:, None]) ** 2).sum(-1)).sum(1) / wsum)
+        return centroid, extent, wsum
+
+    def system(self, idx, ang, m, centroid):
+        sub, dt, root = _take(self.hm, idx), self.dt, np.sqrt(self.w[idx])
+        jac = jacobian(sub, ang, m, centroid, dt) * np.repeat(root, 3, 1)[..., None]
+        res = (np.where(self.used[idx][..., None], forward(sub, ang, m, dt) - self.y[idx], dt(0)) * root[..., None]).reshape(-1, 63)
+        return jac, res
+
+    def cost(self, idx, ang, m, extra=None):
+        r = np.where(self.used[idx][..., None], forward(_take(self.hm, idx), ang, m, self.dt) - self.y[idx], self.dt(0))
+        d2 = (r * r).sum(-1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return (self.w[idx] * d2).sum(1), np.sqrt(d2.max(1))
+
+    def trial(self, idx, delta):
+        return None
+
+    def small(self, delta):
+        return True
+
+    def keep(self, idx, accept, extra):
+        pass
+
+    def report(self, refused, ang, m, centroid, status):
+        return []
+
+
+def lm(prob, limits, init, mirror, t_scale, max_iters, history=None, trace=None):
+    """The restatement of fit_pose (csrc/ut_fit_dev.h) on a Problem, once for all four entries.  Prologue: mirror flags, the box,
+    the start - init = (joint_angles [B,22], wrist_xf [B,4,4]) clamped into the box, or the problem's cold start - the pivot, the
+    start's cost; a start whose cost is not finite is refused.  Loop: Marquardt's floored diagonal scaling, the damped solve
+    through `solve`, a trial kept only when the cost goes down, the stop rules and the lambda schedule.  Epilogue: angles
+    wrapped into (-pi, pi] without a box, the proper wrist in target units / t_scale, a refused pose gets its init back (the
+    rest pose at the identity without one or after a bad start).  Returns (joint_angles [B,22], wrist_xf [B,4,4], info
+    [B, 4 + the problem's columns]: rms, worst, iterations, status - zeros before the status of a refused pose)."""
+    dt = prob.dt
+    refused = prob.refused.copy()
+    b = len(refused)
     mir = np.zeros(b, np.int64) if mirror is None else np.asarray(mirror).astype(np.int64)
     box = None if limits is None else np.broadcast_to(np.asarray(limits).astype(dt)[..., :20, :], (b, 20, 2))
-    wsum = w.sum(1)
-    centroid = (w[..., None] * y).sum(1) / wsum[:, None]
-    extent = np.sqrt((w * ((y - centroid[:, None]) ** 2).sum(-1)).sum(1) / wsum)
     tail = np.zeros((b, 2), dt)
     if init is None:
-        ang, m = cold_start(hm, y, w, mir, box, dt)
+        ang, m = prob.cold_start(mir, box)
     else:
         ang = np.asarray(init[0]).astype(dt)[:, :20].copy()
         tail = np.asarray(init[0]).astype(dt)[:, 20:22].copy()
         m = effective_wrist(np.asarray(init[1]), mir, t_scale, dt)
         if box is not None:
             ang = np.minimum(np.maximum(ang, box[..., 0]), box[..., 1])
-
-    def cost_of(a, mm):
-        r = np.where(used[..., None], forward(hm, a, mm, dt) - y, dt(0))
-        d2 = (r * r).sum(-1)
-        with np.errstate(invalid="ignore", over="ignore"):
-            return (w * d2).sum(1), np.sqrt(d2.max(1))
-
-    cost, worst = cost_of(ang, m)
+    centroid, extent, denominator = prob.pivot(ang, m)
+    cost, worst = prob.cost(np.arange(b), ang, m)
     bad_start = ~refused & ~np.isfinite(cost)
     refused |= bad_start
     lam = np.full(b, LAMBDA_START, dt)
@@ -236,33 +295,30 @@ def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=
         if not active.any():
             break
         idx = np.nonzero(active)[0]
-        sub = _take(hm, idx)
-        jac = jacobian(sub, ang[idx], m[idx], centroid[idx], dt) * np.repeat(np.sqrt(w[idx]), 3, 1)[..., None]
-        res = (np.where(used[idx][..., None], forward(sub, ang[idx], m[idx], dt) - y[idx], dt(0)) * np.sqrt(w[idx])[..., None]).reshape(-1, 63)
+        jac, res = prob.system(idx, ang[idx], m[idx], centroid[idx])
         a_mat = jac.transpose(0, 2, 1) @ jac
         g = (jac.transpose(0, 2, 1) @ res[..., None])[..., 0]
         diag = np.einsum("bii->bi", a_mat)
         diag = np.maximum(diag, dt(DIAG_FLOOR) * diag.max(1, keepdims=True))
-        damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(26, dtype=dt))
+        damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(prob.NP, dtype=dt))
         delta = solve(damped, -g[..., None])[..., 0].astype(dt)
         ok = np.isfinite(delta).all(1)
         delta = np.where(ok[:, None], delta, 0)
-        ta, tm = apply_step(ang[idx], m[idx], centroid[idx], delta, None if box is None else box[idx])
-        sub_used, sub_y, sub_w = used[idx], y[idx], w[idx]
-        r = np.where(sub_used[..., None], forward(sub, ta, tm, dt) - sub_y, dt(0))
-        d2 = (r * r).sum(-1)
-        tc, tw = (sub_w * d2).sum(1), np.sqrt(d2.max(1))
+        extra = prob.trial(idx, delta)
+        ta, tm = apply_step(ang[idx], m[idx], centroid[idx], delta[:, :26], None if box is None else box[idx])
+        tc, tw = prob.cost(idx, ta, tm, extra)
         accept = ok & np.isfinite(tc) & (tc < cost[idx])
         if trace is not None:
             trace.append(trial_record(idx, lam, delta, cost, tc, accept))
         step_small = (np.abs(ta - ang[idx]).max(1) <= STEP_TOL) & (np.abs(delta[:, 20:23]).max(1) <= STEP_TOL) & \
-                     (np.abs(delta[:, 23:26]).max(1) <= dt(STEP_TOL) * extent[idx])
-        flat = ~accept | (cost[idx] - tc <= dt(DECREASE_TOL) * cost[idx])
+                     (np.abs(delta[:, 23:26]).max(1) <= dt(STEP_TOL) * extent[idx]) & prob.small(delta)
         with np.errstate(invalid="ignore"):
+            flat = ~accept | (cost[idx] - tc <= dt(DECREASE_TOL) * cost[idx])
             stationary = ok & ~accept & (np.abs(tc - cost[idx]) <= dt(FLAT_TOL) * cost[idx])
         done = (ok & step_small & flat & (lam[idx] <= LAMBDA_CONVERGED_MAX)) | stationary
         acc = idx[accept]
         ang[acc], m[acc], cost[acc], worst[acc] = ta[accept], tm[accept], tc[accept], tw[accept]
+        prob.keep(idx, accept, extra)
         lam[idx] = np.where(accept, np.maximum(lam[idx] * dt(LAMBDA_DOWN), dt(LAMBDA_MIN)), lam[idx] * dt(LAMBDA_UP))
         iters[idx] += 1
         status[idx[done]] |= CONVERGED
@@ -270,6 +326,7 @@ def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=
         if history is not None:
             history.append((ang.copy(), m.copy()))
     status[active] |= AT_MAX_ITERS
+    columns = prob.report(refused, ang, m, centroid, status)
     if box is None:
         big = np.abs(ang) > dt(np.pi)
         ang = np.where(big, wrap(ang), ang)
@@ -284,6 +341,19 @@ def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=
         else:
             out_ja[refused] = np.where(bad_start[refused, None], 0, np.asarray(init[0]).astype(dt)[refused])
             out_xf[refused] = np.where(bad_start[refused, None, None], np.eye(4), np.asarray(init[1]).astype(dt)[refused])
-    info = np.stack([np.sqrt(cost / wsum), worst, iters.astype(dt), status.astype(dt)], 1)
+    with np.errstate(invalid="ignore"):
+        info = np.stack([np.sqrt(cost / denominator), worst, iters.astype(dt), status.astype(dt)] + columns, 1)
     info[refused, :3] = 0
     return out_ja, out_xf, info
+
+
+def fit(hm, targets, weights=None, limits=None, init=None, mirror=None, t_scale=1.0, max_iters=32, dtype=np.float64,
+        history=None, trace=None):
+    """Fit B poses: (joint_angles [B,22], wrist_xf [B,4,4] proper, translation in target units / t_scale, info [B,4]:
+    weighted rms residual, worst residual, iterations, status).  targets [B,21,3]; weights [B,21] >= 0 or None; limits
+    [20,2] / [B,20,2] or None; init = (joint_angles [B,22], wrist_xf [B,4,4]) or None for the cold start; mirror [B] of
+    0 / 1.  history: a list that receives (angles, effective wrist) after every iteration.  trace: a list that receives
+    the decision of every iteration (trial_record)."""
+    return lm(Problem(hm, dtype, *weighted_targets(targets, weights, dtype)), limits, init, mirror, t_scale, max_iters, history, trace)
+
+

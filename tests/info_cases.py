@@ -67,6 +67,34 @@ def whiten(f, r):
 
 
 # ----------------------------------------------------------------------------- the fit
+class _Whitened(fc.Problem):
+    """fc.Problem with the residuals and the Jacobian rows of every landmark whitened by its factor f [B,21,6]; w is the
+    factor's squared Frobenius norm, n_used [B] the number of used landmarks."""
+
+    def __init__(self, hm, dtype, f, w, used, y, refused, n_used):
+        super().__init__(hm, dtype, w, used, y, refused)
+        self.f, self.n_used = f, n_used
+
+    def pivot(self, ang, m):
+        centroid, extent, _wsum = super().pivot(ang, m)
+        return centroid, extent, (3 * self.n_used).astype(self.dt)
+
+    def _residuals(self, idx, ang, m):
+        r = np.where(self.used[idx][..., None], fc.forward(fc._take(self.hm, idx), ang, m, self.dt) - self.y[idx], self.dt(0))
+        return r, whiten(self.f[idx], r)
+
+    def system(self, idx, ang, m, centroid):
+        k = len(idx)
+        jac = fc.jacobian(fc._take(self.hm, idx), ang, m, centroid, self.dt).reshape(k, 21, 3, 26)
+        jac = whiten(self.f[idx], np.where(self.used[idx][..., None, None], jac, self.dt(0))).reshape(k, 63, 26)
+        return jac, self._residuals(idx, ang, m)[1].reshape(k, 63)
+
+    def cost(self, idx, ang, m, extra=None):
+        r, u = self._residuals(idx, ang, m)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return (u * u).sum((1, 2)), np.sqrt((r * r).sum(-1).max(1))
+
+
 def fit_info(hm, targets, sqrt_info, limits=None, init=None, mirror=None, t_scale=1.0, max_iters=32, dtype=np.float64,
              trace=None):
     """ut_fit_pose_info: fc.fit with the cost sum_l |L_l^T (landmark_l - target_l)|^2.  sqrt_info [B,21,6]; every other argument
@@ -75,7 +103,6 @@ def fit_info(hm, targets, sqrt_info, limits=None, init=None, mirror=None, t_scal
     extent, the cold start's Kabsch fit) is the factor's squared Frobenius norm.  Refused: a factor entry that is not finite,
     a non-finite target of a used landmark, fewer than 3 used landmarks."""
     dt = dtype
-    b = targets.shape[0]
     f = np.asarray(sqrt_info).astype(dt)
     with np.errstate(invalid="ignore", over="ignore"):
         bad_f = ~np.isfinite(f).all((1, 2)) | ~np.isfinite((f * f).sum(-1)).all(1)
@@ -86,87 +113,7 @@ def fit_info(hm, targets, sqrt_info, limits=None, init=None, mirror=None, t_scal
     w = np.where(refused[:, None], dt(1), (f * f).sum(-1))
     n_used = np.where(refused, 21, used.sum(1))
     y = np.where(used[..., None], np.asarray(targets), 0).astype(dt)
-    mir = np.zeros(b, np.int64) if mirror is None else np.asarray(mirror).astype(np.int64)
-    box = None if limits is None else np.broadcast_to(np.asarray(limits).astype(dt)[..., :20, :], (b, 20, 2))
-    wsum = w.sum(1)
-    centroid = (w[..., None] * y).sum(1) / wsum[:, None]
-    extent = np.sqrt((w * ((y - centroid[:, None]) ** 2).sum(-1)).sum(1) / wsum)
-    tail = np.zeros((b, 2), dt)
-    if init is None:
-        ang, m = fc.cold_start(hm, y, w, mir, box, dt)
-    else:
-        ang = np.asarray(init[0]).astype(dt)[:, :20].copy()
-        tail = np.asarray(init[0]).astype(dt)[:, 20:22].copy()
-        m = fc.effective_wrist(np.asarray(init[1]), mir, t_scale, dt)
-        if box is not None:
-            ang = np.minimum(np.maximum(ang, box[..., 0]), box[..., 1])
-
-    def cost_of(sub, a, mm, idx):
-        r = np.where(used[idx][..., None], fc.forward(sub, a, mm, dt) - y[idx], dt(0))
-        u = whiten(f[idx], r)
-        with np.errstate(invalid="ignore", over="ignore"):
-            return (u * u).sum((1, 2)), np.sqrt((r * r).sum(-1).max(1)), u
-
-    every = np.arange(b)
-    cost, worst, _u = cost_of(hm, ang, m, every)
-    bad_start = ~refused & ~np.isfinite(cost)
-    refused |= bad_start
-    lam = np.full(b, fc.LAMBDA_START, dt)
-    iters = np.zeros(b, np.int64)
-    status = np.where(refused, REFUSED, 0)
-    active = ~refused
-    for _ in range(max_iters):
-        if not active.any():
-            break
-        idx = np.nonzero(active)[0]
-        sub = fc._take(hm, idx)
-        jac = fc.jacobian(sub, ang[idx], m[idx], centroid[idx], dt).reshape(len(idx), 21, 3, 26)
-        jac = whiten(f[idx], np.where(used[idx][..., None, None], jac, dt(0))).reshape(len(idx), 63, 26)
-        res = cost_of(sub, ang[idx], m[idx], idx)[2].reshape(len(idx), 63)
-        a_mat = jac.transpose(0, 2, 1) @ jac
-        g = (jac.transpose(0, 2, 1) @ res[..., None])[..., 0]
-        diag = np.einsum("bii->bi", a_mat)
-        diag = np.maximum(diag, dt(fc.DIAG_FLOOR) * diag.max(1, keepdims=True))
-        damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(26, dtype=dt))
-        delta = fc.solve(damped, -g[..., None])[..., 0].astype(dt)
-        ok = np.isfinite(delta).all(1)
-        delta = np.where(ok[:, None], delta, 0)
-        ta, tm = fc.apply_step(ang[idx], m[idx], centroid[idx], delta, None if box is None else box[idx])
-        t_cost, t_worst, _u = cost_of(sub, ta, tm, idx)
-        accept = ok & np.isfinite(t_cost) & (t_cost < cost[idx])
-        if trace is not None:
-            trace.append(fc.trial_record(idx, lam, delta, cost, t_cost, accept))
-        step_small = (np.abs(ta - ang[idx]).max(1) <= fc.STEP_TOL) & (np.abs(delta[:, 20:23]).max(1) <= fc.STEP_TOL) & \
-                     (np.abs(delta[:, 23:26]).max(1) <= dt(fc.STEP_TOL) * extent[idx])
-        flat = ~accept | (cost[idx] - t_cost <= dt(fc.DECREASE_TOL) * cost[idx])
-        with np.errstate(invalid="ignore"):
-            stationary = ok & ~accept & (np.abs(t_cost - cost[idx]) <= dt(fc.FLAT_TOL) * cost[idx])
-        done = (ok & step_small & flat & (lam[idx] <= fc.LAMBDA_CONVERGED_MAX)) | stationary
-        acc = idx[accept]
-        ang[acc], m[acc], cost[acc], worst[acc] = ta[accept], tm[accept], t_cost[accept], t_worst[accept]
-        lam[idx] = np.where(accept, np.maximum(lam[idx] * dt(fc.LAMBDA_DOWN), dt(fc.LAMBDA_MIN)), lam[idx] * dt(fc.LAMBDA_UP))
-        iters[idx] += 1
-        status[idx[done]] |= CONVERGED
-        active[idx[done]] = False
-    status[active] |= AT_MAX_ITERS
-    if box is None:
-        big = np.abs(ang) > dt(np.pi)
-        ang = np.where(big, fc.wrap(ang), ang)
-    out_ja = np.concatenate([ang, tail], 1)
-    out_xf = m.copy()
-    out_xf[mir == 1, :, 0] *= -1
-    out_xf[:, :3, 3] /= dt(t_scale)
-    if refused.any():
-        if init is None:
-            out_ja[refused] = 0
-            out_xf[refused] = np.eye(4, dtype=dt)
-        else:
-            out_ja[refused] = np.where(bad_start[refused, None], 0, np.asarray(init[0]).astype(dt)[refused])
-            out_xf[refused] = np.where(bad_start[refused, None, None], np.eye(4), np.asarray(init[1]).astype(dt)[refused])
-    with np.errstate(invalid="ignore"):
-        info = np.stack([np.sqrt(cost / (3 * n_used).astype(dt)), worst, iters.astype(dt), status.astype(dt)], 1)
-    info[refused, :3] = 0
-    return out_ja, out_xf, info
+    return fc.lm(_Whitened(hm, dt, f, w, used, y, refused, n_used), limits, init, mirror, t_scale, max_iters, trace=trace)
 
 
 # ----------------------------------------------------------------------------- the golden chain

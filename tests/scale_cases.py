@@ -56,13 +56,18 @@ def jacobian(hm, s, angles, eff_wrist, centroid, dtype=np.float64):
     return jac
 
 
+def trial_scale(s, d_sigma, dtype):
+    """s_t = clamp(s exp(d sigma), SCALE_MIN, SCALE_MAX) in `dtype`."""
+    dt = dtype.type
+    with np.errstate(over="ignore", invalid="ignore"):
+        st = np.minimum(np.maximum(s * np.exp(d_sigma), dt(SCALE_MIN)), dt(SCALE_MAX))
+    return st.astype(dtype)
+
+
 def apply_step(angles, eff_wrist, s, centroid, delta, box=None):
     """fit_cases.apply_step on the first 26 entries; s_t = clamp(s exp(delta[26]))."""
-    dt = angles.dtype.type
     a, m = fc.apply_step(angles, eff_wrist, centroid, delta[:, :26], box)
-    with np.errstate(over="ignore", invalid="ignore"):
-        st = np.minimum(np.maximum(s * np.exp(delta[:, 26]), dt(SCALE_MIN)), dt(SCALE_MAX))
-    return a, m, st.astype(angles.dtype)
+    return a, m, trial_scale(s, delta[:, 26], angles.dtype)
 
 
 def information(a_mat, dtype=np.float64):
@@ -85,12 +90,62 @@ def information(a_mat, dtype=np.float64):
     return out
 
 
-def _normal(hm, s, ang, m, centroid, w, used, y, mode, dt):
+def _rows(hm, s, ang, m, centroid, w, used, y, mode, dt):
+    """The weighted system (J [k,63,27], r [k,63]); mode FIXED: the sigma column is zero."""
     jac = jacobian(hm, s, ang, m, centroid, dt) * np.repeat(np.sqrt(w), 3, 1)[..., None]
     if mode == FIXED:
         jac[:, :, 26] = 0
     res = (np.where(used[..., None], forward(hm, s, ang, m, dt) - y, dt(0)) * np.sqrt(w)[..., None]).reshape(-1, 63)
+    return jac, res
+
+
+def _normal(hm, s, ang, m, centroid, w, used, y, mode, dt):
+    jac, res = _rows(hm, s, ang, m, centroid, w, used, y, mode, dt)
     return jac.transpose(0, 2, 1) @ jac, (jac.transpose(0, 2, 1) @ res[..., None])[..., 0]
+
+
+class _WithScale(fc.Problem):
+    """fc.Problem with sigma = ln s as parameter 26: s [B] is the kept scale."""
+    NP = 27
+
+    def __init__(self, hm, dtype, w, used, y, refused, s, mode):
+        super().__init__(hm, dtype, w, used, y, refused)
+        self.s, self.mode = s, mode
+
+    def model(self):
+        return scaled_model(self.hm, self.s, self.dt)
+
+    def system(self, idx, ang, m, centroid):
+        return _rows(fc._take(self.hm, idx), self.s[idx], ang, m, centroid, self.w[idx], self.used[idx], self.y[idx], self.mode, self.dt)
+
+    def cost(self, idx, ang, m, extra=None):
+        s = self.s[idx] if extra is None else extra
+        r = np.where(self.used[idx][..., None], forward(fc._take(self.hm, idx), s, ang, m, self.dt) - self.y[idx], self.dt(0))
+        d2 = (r * r).sum(-1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return (self.w[idx] * d2).sum(1), np.sqrt(d2.max(1))
+
+    def trial(self, idx, delta):
+        if self.mode == FIXED:
+            delta[:, 26] = 0
+        return trial_scale(self.s[idx], delta[:, 26], delta.dtype)
+
+    def small(self, delta):
+        return np.abs(delta[:, 26]) <= fc.STEP_TOL
+
+    def keep(self, idx, accept, extra):
+        self.s[idx[accept]] = extra[accept]
+
+    def report(self, refused, ang, m, centroid, status):
+        """The scale information of the accepted state and AT_BOUND, for a FREE fit; a refused pose's scale is 1."""
+        scale_info = np.zeros(len(refused), self.dt)
+        if self.mode == FREE and not refused.all():
+            idx = np.nonzero(~refused)[0]
+            jac, _res = self.system(idx, ang[idx], m[idx], centroid[idx])
+            scale_info[idx] = information(jac.transpose(0, 2, 1) @ jac, self.dt)
+            status[idx[(self.s[idx] <= self.dt(SCALE_MIN)) | (self.s[idx] >= self.dt(SCALE_MAX))]] |= AT_BOUND
+        self.s[refused] = 1
+        return [scale_info, np.zeros(len(refused), self.dt)]
 
 
 def fit_scale(hm, targets, weights=None, limits=None, init=None, init_scale=None, mode=FREE, mirror=None, t_scale=1.0,
@@ -100,106 +155,14 @@ def fit_scale(hm, targets, weights=None, limits=None, init=None, init_scale=None
     [SCALE_MIN, SCALE_MAX] refuses the pose (scale 1).  mode FIXED: the sigma column is zero, the scale stays init_scale and
     the information is 0.  Status bit AT_BOUND: a FREE fit ended at SCALE_MIN or SCALE_MAX.  trace: as for fit_cases.fit."""
     dt = dtype
-    b = targets.shape[0]
-    hm = {k: np.asarray(hm[k]) for k in _FIELDS}
-    w = np.ones((b, 21), dt) if weights is None else np.asarray(weights).astype(dt)
-    used = w > 0
-    s = np.ones(b, dt) if init_scale is None else np.asarray(init_scale).astype(dt).copy()
+    s = np.ones(targets.shape[0], dt) if init_scale is None else np.asarray(init_scale).astype(dt).copy()
     with np.errstate(invalid="ignore"):
         bad_scale = ~(np.isfinite(s) & (s >= dt(SCALE_MIN)) & (s <= dt(SCALE_MAX)))
-    refused = (used.sum(1) < 3) | ~np.isfinite(w).all(1) | (w < 0).any(1) | \
-        (~np.isfinite(np.asarray(targets)) & used[..., None]).any((1, 2)) | bad_scale
+    w, used, y, refused = fc.weighted_targets(targets, weights, dt, bad_scale)
     s[refused] = 1
-    w = np.where(refused[:, None], dt(1), np.where(used, w, dt(0)))
-    used = w > 0
-    y = np.where(used[..., None], np.asarray(targets), 0).astype(dt)
-    y[refused] = 0
-    mir = np.zeros(b, np.int64) if mirror is None else np.asarray(mirror).astype(np.int64)
-    box = None if limits is None else np.broadcast_to(np.asarray(limits).astype(dt)[..., :20, :], (b, 20, 2))
-    wsum = w.sum(1)
-    centroid = (w[..., None] * y).sum(1) / wsum[:, None]
-    extent = np.sqrt((w * ((y - centroid[:, None]) ** 2).sum(-1)).sum(1) / wsum)
-    tail = np.zeros((b, 2), dt)
-    if init is None:
-        ang, m = fc.cold_start(scaled_model(hm, s, dt), y, w, mir, box, dt)
-    else:
-        ang = np.asarray(init[0]).astype(dt)[:, :20].copy()
-        tail = np.asarray(init[0]).astype(dt)[:, 20:22].copy()
-        m = fc.effective_wrist(np.asarray(init[1]), mir, t_scale, dt)
-        if box is not None:
-            ang = np.minimum(np.maximum(ang, box[..., 0]), box[..., 1])
-
-    def cost_of(a, mm, ss, sel):
-        r = np.where(used[sel][..., None], forward(fc._take(hm, sel), ss, a, mm, dt) - y[sel], dt(0))
-        d2 = (r * r).sum(-1)
-        with np.errstate(invalid="ignore", over="ignore"):
-            return (w[sel] * d2).sum(1), np.sqrt(d2.max(1))
-
-    every = np.arange(b)
-    cost, worst = cost_of(ang, m, s, every)
-    bad_start = ~refused & ~np.isfinite(cost)
-    refused |= bad_start
-    lam = np.full(b, fc.LAMBDA_START, dt)
-    iters = np.zeros(b, np.int64)
-    status = np.where(refused, REFUSED, 0)
-    active = ~refused
-    for _ in range(max_iters):
-        if not active.any():
-            break
-        idx = np.nonzero(active)[0]
-        sub = fc._take(hm, idx)
-        a_mat, g = _normal(sub, s[idx], ang[idx], m[idx], centroid[idx], w[idx], used[idx], y[idx], mode, dt)
-        diag = np.einsum("bii->bi", a_mat)
-        diag = np.maximum(diag, dt(fc.DIAG_FLOOR) * diag.max(1, keepdims=True))
-        damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(27, dtype=dt))
-        delta = fc.solve(damped, -g[..., None])[..., 0].astype(dt)
-        ok = np.isfinite(delta).all(1)
-        delta = np.where(ok[:, None], delta, 0)
-        if mode == FIXED:
-            delta[:, 26] = 0
-        ta, tm, ts = apply_step(ang[idx], m[idx], s[idx], centroid[idx], delta, None if box is None else box[idx])
-        tc, tw = cost_of(ta, tm, ts, idx)
-        accept = ok & np.isfinite(tc) & (tc < cost[idx])
-        if trace is not None:
-            trace.append(fc.trial_record(idx, lam, delta, cost, tc, accept))
-        step_small = (np.abs(ta - ang[idx]).max(1) <= fc.STEP_TOL) & (np.abs(delta[:, 20:23]).max(1) <= fc.STEP_TOL) & \
-                     (np.abs(delta[:, 23:26]).max(1) <= dt(fc.STEP_TOL) * extent[idx]) & (np.abs(delta[:, 26]) <= fc.STEP_TOL)
-        flat = ~accept | (cost[idx] - tc <= dt(fc.DECREASE_TOL) * cost[idx])
-        with np.errstate(invalid="ignore"):
-            stationary = ok & ~accept & (np.abs(tc - cost[idx]) <= dt(fc.FLAT_TOL) * cost[idx])
-        done = (ok & step_small & flat & (lam[idx] <= fc.LAMBDA_CONVERGED_MAX)) | stationary
-        acc = idx[accept]
-        ang[acc], m[acc], s[acc], cost[acc], worst[acc] = ta[accept], tm[accept], ts[accept], tc[accept], tw[accept]
-        lam[idx] = np.where(accept, np.maximum(lam[idx] * dt(fc.LAMBDA_DOWN), dt(fc.LAMBDA_MIN)), lam[idx] * dt(fc.LAMBDA_UP))
-        iters[idx] += 1
-        status[idx[done]] |= CONVERGED
-        active[idx[done]] = False
-    status[active] |= AT_MAX_ITERS
-    fitted = ~refused
-    scale_info = np.zeros(b, dt)
-    if mode == FREE and fitted.any():
-        idx = np.nonzero(fitted)[0]
-        a_mat, _g = _normal(fc._take(hm, idx), s[idx], ang[idx], m[idx], centroid[idx], w[idx], used[idx], y[idx], mode, dt)
-        scale_info[idx] = information(a_mat, dt)
-        status[idx[(s[idx] <= dt(SCALE_MIN)) | (s[idx] >= dt(SCALE_MAX))]] |= AT_BOUND
-    if box is None:
-        big = np.abs(ang) > dt(np.pi)
-        ang = np.where(big, fc.wrap(ang), ang)
-    out_ja = np.concatenate([ang, tail], 1)
-    out_xf = m.copy()
-    out_xf[mir == 1, :, 0] *= -1
-    out_xf[:, :3, 3] /= dt(t_scale)
-    if refused.any():
-        s[refused] = 1
-        if init is None:
-            out_ja[refused] = 0
-            out_xf[refused] = np.eye(4, dtype=dt)
-        else:
-            out_ja[refused] = np.where(bad_start[refused, None], 0, np.asarray(init[0]).astype(dt)[refused])
-            out_xf[refused] = np.where(bad_start[refused, None, None], np.eye(4), np.asarray(init[1]).astype(dt)[refused])
-    info = np.stack([np.sqrt(cost / wsum), worst, iters.astype(dt), status.astype(dt), scale_info, np.zeros(b, dt)], 1)
-    info[refused, :3] = 0
-    return out_ja, out_xf, s, info
+    prob = _WithScale({k: np.asarray(hm[k]) for k in _FIELDS}, dt, w, used, y, refused, s, mode)
+    out_ja, out_xf, info = fc.lm(prob, limits, init, mirror, t_scale, max_iters, trace=trace)
+    return out_ja, out_xf, prob.s, info
 
 
 def usable(scale, info):

@@ -276,15 +276,19 @@ def landmarks(c, res):
     return sc.forward(c["hm"], np.asarray(res["scale"], np.float64), np.asarray(res["ja"], np.float64)[:, :20], m, np.float64)
 
 
+def angle_and_rotation_distance(a, b):
+    """The `ang` of distance(), here and in views_cases: the 20 angles modulo 2 pi and the entries of the wrist's rotation, rad."""
+    return float(max(fc.angle_distance(a["ja"][:, :20], b["ja"][:, :20]).max(),
+                     np.abs(np.asarray(a["xf"], np.float64)[:, :3, :3] - np.asarray(b["xf"], np.float64)[:, :3, :3]).max()))
+
+
 def distance(c, a, b):
     """How far two results of a case lie apart.  ang: the 20 angles modulo 2 pi and the entries of the wrist's rotation, rad.
     kp: landmarks through the float64 forward function of both (which carries the wrist's translation), and rms / worst of
     info, mm.  scale: |s_a - s_b|.  scale_info: info[4] relative to b's (0 where the entry has none)."""
-    ang = max(fc.angle_distance(a["ja"][:, :20], b["ja"][:, :20]).max(),
-              np.abs(np.asarray(a["xf"], np.float64)[:, :3, :3] - np.asarray(b["xf"], np.float64)[:, :3, :3]).max())
     ia, ib = np.asarray(a["info"], np.float64), np.asarray(b["info"], np.float64)
     kp = max(np.linalg.norm(landmarks(c, a) - landmarks(c, b), axis=-1).max(), np.abs(ia[:, :2] - ib[:, :2]).max())
-    out = dict(ang=float(ang), kp=float(kp), scale=float(np.abs(np.asarray(a["scale"], np.float64) - b["scale"]).max()),
+    out = dict(ang=angle_and_rotation_distance(a, b), kp=float(kp), scale=float(np.abs(np.asarray(a["scale"], np.float64) - b["scale"]).max()),
                scale_info=0.0)
     if c["entry"] == "scale_free":
         out["scale_info"] = float((np.abs(ia[:, 4] - ib[:, 4]) / ib[:, 4]).max())
@@ -328,7 +332,8 @@ def decisions(res, trace):
 
 
 def within(d, tol):
-    return all(d[k] <= tol[k] for k in ("ang", "kp", "scale", "scale_info"))
+    """Every figure of a distance() - this module's or views_cases' - within its bound of the matching bounds_from()."""
+    return all(d[k] <= tol[k] for k in d)
 
 
 # ----------------------------------------------------------------------------- wrong Jacobians, for the sensitivity test

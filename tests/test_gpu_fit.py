@@ -305,3 +305,121 @@ def test_python_surface(rec00, golden_dir):
             worst = max(worst, float(np.abs(tracker.landmarks_from_hand_pose(hm00, pose, h) - kp[h, t]).max()))
     print(f"hand_poses_from_keypoints, recording 00: {int(valid.sum())} poses, landmarks back within {worst:.3e} mm")
     assert worst <= KP_TOL_MM
+
+
+# ----------------------------------------------------------------------------- what the four fit entries refuse, word for word
+N_MSG = 2                    # two poses: the smallest batch that tells "batch mismatch" from "one row"
+STRIDED = "strided views must be fp32 on cuda:0, and `out` must be given with them"
+STRIDED_VIEWS = "strided views must be fp32 on cuda:0, n the windows' batch, and `out` must be given with them"
+NO_COLD_START = "init_angles and init_wrist_xf are required: ut_fit_pose_views has no cold start"
+# fault: (what it changes in the arguments, exception, message - one for all entries, or {entry: message})
+BINDING_FAULTS = {
+    "init_pair": (dict(init_wrist_xf=None), ValueError, dict(fit="init_angles and init_wrist_xf go together",
+                  info="init_angles and init_wrist_xf go together", scale="init_angles and init_wrist_xf go together", views=NO_COLD_START)),
+    "init_batch": (dict(init_angles=(N_MSG + 1, 22)), ValueError, "init_angles / init_wrist_xf batch mismatch"),
+    "mirror_batch": (dict(mirror=(N_MSG + 1,)), ValueError, "mirror batch mismatch"),
+    "limits_rows": (dict(limits=(2, 20, 2)), ValueError, "limits has 2 rows for 1 model rows"),
+    "model_rows": (dict(hand_model=(3, 321)), ValueError, "hand_model has 3 rows for 2 poses"),
+    "strided_without_out": (dict(n=N_MSG), ValueError, dict(fit=STRIDED, info=STRIDED, scale=STRIDED, views=STRIDED_VIEWS)),
+    "strided_fp16": (dict(n=N_MSG, out="fp16"), ValueError, dict(fit=STRIDED, info=STRIDED, scale=STRIDED, views=STRIDED_VIEWS)),
+    "own_shape": (dict(own=True), ValueError, dict(fit="weights must be [2,21], got (2, 20)", info="sqrt_info must be [2,21,6], got (2, 21, 5)",
+                  scale="init_scale batch mismatch", views="weights must be f32 [2,2,21], got torch.float32 (2, 2, 20)")),
+    "scale_weights": (dict(weights=(N_MSG, 20)), ValueError, dict(scale="weights must be [2,21], got (2, 20)")),
+    "no_sqrt_info": (dict(sqrt_info=None), ValueError, dict(info="sqrt_info is required")),
+    "no_init": (dict(init_angles=None, init_wrist_xf=None), ValueError, dict(views=NO_COLD_START)),
+    "no_views": (dict(window=(N_MSG, 0, 21, 2), cam_rows=(N_MSG, 0)), ValueError, dict(views="window [n,V,21,2] needs 1 <= V <= 8, got V = 0")),
+    "f32_window": (dict(window=torch.float32), ValueError, dict(views="window must be f64 [n,V,21,2], got torch.float32 (2, 2, 21, 2)")),
+    "table_31": (dict(table=(4, 31)), ValueError,
+                 dict(views="table must be f64 [R,32] source cameras or [R,24] crop cameras, got torch.float64 (4, 31)")),
+    "i64_cam_rows": (dict(cam_rows=torch.int64), ValueError, dict(views="cam_rows must be i32 [2,2], got torch.int64 (2, 2)")),
+}
+BINDING_CASES = [(e, f) for f, (_c, _x, m) in BINDING_FAULTS.items() for e in ("fit", "info", "scale", "views")
+                 if not isinstance(m, dict) or e in m]
+
+
+def _binding_args(entry):
+    """Valid arguments of one _native entry for N_MSG poses, warm start included: every check passes, nothing is launched yet."""
+    z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=DEV)
+    kw = dict(hand_model=z(1, 321), init_angles=z(N_MSG, 22), init_wrist_xf=z(N_MSG, 4, 4), mirror=z(N_MSG, dtype=torch.int64),
+              limits=z(1, 20, 2))
+    if entry == "views":
+        kw.update(window=z(N_MSG, 2, 21, 2, dtype=torch.float64), cam_rows=z(N_MSG, 2, dtype=torch.int32),
+                  table=z(4, 32, dtype=torch.float64), weights=z(N_MSG, 2, 21))
+    else:
+        kw.update(targets=z(N_MSG, 21, 3))
+    if entry == "info":
+        kw.update(sqrt_info=z(N_MSG, 21, 6))
+    elif entry in ("fit", "scale"):
+        kw.update(weights=z(N_MSG, 21))
+    if entry == "scale":
+        kw.update(init_scale=z(N_MSG))
+    return kw
+
+
+@pytest.mark.parametrize("entry,fault", BINDING_CASES, ids=[f"{e}-{f}" for e, f in BINDING_CASES])
+def test_binding_refusals_word_for_word(entry, fault):
+    """One fault at a time in otherwise valid arguments of _native.fit_pose / fit_pose_info / fit_pose_scale / fit_pose_views:
+    the exception's type and its whole message.  Every one of these checks raises before anything is launched."""
+    change, exc, msg = BINDING_FAULTS[fault]
+    msg = msg[entry] if isinstance(msg, dict) else msg
+    kw = _binding_args(entry)
+    for k, v in change.items():
+        if k == "own":
+            own = dict(fit=("weights", (N_MSG, 20)), info=("sqrt_info", (N_MSG, 21, 5)), scale=("init_scale", (N_MSG + 1,)),
+                       views=("weights", (N_MSG, 2, 20)))[entry]
+            kw[own[0]] = torch.zeros(own[1], device=DEV)
+        elif k == "out":
+            kw["out"] = (torch.zeros(N_MSG, 22, dtype=torch.float16, device=DEV), torch.zeros(N_MSG, 4, 4, device=DEV))
+        elif isinstance(v, tuple):
+            kw[k] = torch.zeros(v, dtype=kw[k].dtype, device=DEV)
+        elif isinstance(v, torch.dtype):
+            kw[k] = kw[k].to(v)
+        else:
+            kw[k] = v
+    fn = dict(fit=_native.fit_pose, info=_native.fit_pose_info, scale=_native.fit_pose_scale, views=_native.fit_pose_views)[entry]
+    with pytest.raises(exc) as e:
+        fn(**kw)
+    assert type(e.value) is exc and str(e.value) == msg
+
+
+WRAPPER_FAULTS = {
+    "leading_dims": (AssertionError, "Leading dimensions do not match, got (2,) and (3,)"),
+    "no_limits": (ValueError, dict(fit="limits=True needs hand_model.joint_limits", info="limits=True needs hand_model.joint_limits",
+                                   scale="limits=True needs hand_model.joint_limits", views="limits needs hand_model.joint_limits")),
+    "sqrt_info_shape": (ValueError, dict(info="sqrt_info must be (2, 21, 6), got (2, 21, 5)")),
+    "no_init": (ValueError, dict(views="init = (joint_angles, wrist_transforms) is required: fit_landmarks_views has no cold start")),
+    "scalar_weights": (RuntimeError, dict(fit="shape '[2, 21]' is invalid for input of size 1")),
+}
+WRAPPER_CASES = [(e, f) for f, (_x, m) in WRAPPER_FAULTS.items() for e in ("fit", "info", "scale", "views")
+                 if not isinstance(m, dict) or e in m]
+
+
+@pytest.mark.parametrize("entry,fault", WRAPPER_CASES, ids=[f"{e}-{f}" for e, f in WRAPPER_CASES])
+def test_wrapper_refusals_word_for_word(entry, fault):
+    """hand.fit_landmarks / _info / _scale / _views on CPU tensors of N_MSG poses with one fault: the exception's type and its
+    whole message.  A scalar `weights` is refused by fit_landmarks (fit_landmarks_scale alone broadcasts)."""
+    exc, msg = WRAPPER_FAULTS[fault]
+    msg = msg[entry] if isinstance(msg, dict) else msg
+    hmt = pipeline.hand_model_from_labels(pipeline.load_labels())
+    assert hmt.joint_limits is not None and hmt.joint_rest_positions.dim() == 2
+    init = (torch.zeros(N_MSG, 22), torch.eye(4).repeat(N_MSG, 1, 1))
+    if entry == "views":
+        args = [torch.zeros(N_MSG, 2, 21, 2, dtype=torch.float64), torch.zeros(N_MSG, 2, dtype=torch.int32),
+                torch.zeros(4, 32, dtype=torch.float64), init]
+    else:
+        args = [torch.zeros(N_MSG, 21, 3)] + ([torch.zeros(N_MSG, 21, 6)] if entry == "info" else [])
+    kw = {}
+    if fault == "leading_dims":
+        hmt = hand.scaled_hand_model(hmt, torch.ones(3))
+    elif fault == "no_limits":
+        hmt, kw = hmt._replace(joint_limits=None), dict(limits=True)
+    elif fault == "sqrt_info_shape":
+        args[1] = torch.zeros(N_MSG, 21, 5)
+    elif fault == "no_init":
+        args[3] = None
+    else:
+        kw = dict(weights=torch.tensor(1.0))
+    fn = dict(fit=hand.fit_landmarks, info=hand.fit_landmarks_info, scale=hand.fit_landmarks_scale, views=hand.fit_landmarks_views)[entry]
+    with pytest.raises(exc) as e:
+        fn(hmt, *args, **kw)
+    assert type(e.value) is exc and str(e.value) == msg

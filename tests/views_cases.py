@@ -164,6 +164,33 @@ def pivot(vw, p, dtype):
 
 
 # ----------------------------------------------------------------------------- the fit
+class _Reprojection(fc.Problem):
+    """fc.Problem on the observations vw (Views): no targets, so no cold start, and the pivot, the extent and the sum of the
+    weights are those of the START's landmarks (pivot).  residual [B,V,21] float32 after the fit."""
+
+    def __init__(self, hm, dtype, vw):
+        self.hm, self.dt, self.vw, self.refused = hm, dtype, vw, vw.refused
+
+    def _cost(self, idx, ang, m):
+        with np.errstate(all="ignore"):
+            return self.vw.cost(fc.forward(fc._take(self.hm, idx), ang, m, self.dt), idx, self.dt)
+
+    def pivot(self, ang, m):
+        with np.errstate(all="ignore"):
+            return pivot(self.vw, fc.forward(self.hm, ang, m, self.dt), self.dt)
+
+    def system(self, idx, ang, m, centroid):
+        return reduced_system(self.vw, fc._take(self.hm, idx), ang, m, centroid, idx, self.dt)
+
+    def cost(self, idx, ang, m, extra=None):
+        return self._cost(idx, ang, m)[:2]
+
+    def report(self, refused, ang, m, centroid, status):
+        residual = self._cost(np.arange(len(refused)), ang, m)[2]
+        self.residual = np.where(refused[:, None, None], 0.0, residual).astype(np.float32)
+        return []
+
+
 def fit_views(hm, window, cam_rows, table, weights=None, init=None, mirror=None, limits=None, t_scale=1.0, max_iters=32,
               dtype=np.float64, solver="lu", trace=None):
     """ut_fit_pose_views: (joint_angles [B,22], wrist_xf [B,4,4], info [B,4]: sqrt(cost / sum of the used weights), the largest
@@ -171,85 +198,11 @@ def fit_views(hm, window, cam_rows, table, weights=None, init=None, mirror=None,
     observation at the returned pose).  init = (joint_angles [B,22], wrist_xf [B,4,4]) is required.  Refused: a negative or
     non-finite weight of a seen view, a non-finite window at a positive weight, fewer than 3 landmarks with a used observation
     (the start comes back), a start whose cost is not finite (the rest pose at the identity comes back, as fc.fit does)."""
-    with st.solver(solver):
-        return _fit_views(hm, window, cam_rows, table, weights, init, mirror, limits, t_scale, max_iters, dtype, trace)
-
-
-def _fit_views(hm, window, cam_rows, table, weights, init, mirror, limits, t_scale, max_iters, dtype, trace):
     if init is None:
         raise ValueError("init is required: there is no cold start")
-    dt = dtype
-    vw = Views(window, cam_rows, table, weights, dt)
-    b = len(vw.refused)
-    refused = vw.refused.copy()
-    mir = np.zeros(b, np.int64) if mirror is None else np.asarray(mirror).astype(np.int64)
-    box = None if limits is None else np.broadcast_to(np.asarray(limits).astype(dt)[..., :20, :], (b, 20, 2))
-    ang = np.asarray(init[0]).astype(dt)[:, :20].copy()
-    tail = np.asarray(init[0]).astype(dt)[:, 20:22].copy()
-    m = fc.effective_wrist(np.asarray(init[1]), mir, t_scale, dt)
-    if box is not None:
-        ang = np.minimum(np.maximum(ang, box[..., 0]), box[..., 1])
-    every = np.arange(b)
-    with np.errstate(all="ignore"):
-        p0 = fc.forward(hm, ang, m, dt)
-    centroid, extent, wsum = pivot(vw, p0, dt)
-    cost, worst, _d = vw.cost(p0, every, dt)
-    bad_start = ~refused & ~np.isfinite(cost)
-    refused |= bad_start
-    lam = np.full(b, fc.LAMBDA_START, dt)
-    iters = np.zeros(b, np.int64)
-    status = np.where(refused, REFUSED, 0)
-    active = ~refused
-    for _ in range(max_iters):
-        if not active.any():
-            break
-        idx = np.nonzero(active)[0]
-        sub = fc._take(hm, idx)
-        jac, res = reduced_system(vw, sub, ang[idx], m[idx], centroid[idx], idx, dt)
-        a_mat = jac.transpose(0, 2, 1) @ jac
-        g = (jac.transpose(0, 2, 1) @ res[..., None])[..., 0]
-        diag = np.einsum("bii->bi", a_mat)
-        diag = np.maximum(diag, dt(fc.DIAG_FLOOR) * diag.max(1, keepdims=True))
-        damped = a_mat + np.einsum("bi,ij->bij", lam[idx, None] * diag, np.eye(26, dtype=dt))
-        delta = fc.solve(damped, -g[..., None])[..., 0].astype(dt)
-        ok = np.isfinite(delta).all(1)
-        delta = np.where(ok[:, None], delta, 0)
-        ta, tm = fc.apply_step(ang[idx], m[idx], centroid[idx], delta, None if box is None else box[idx])
-        with np.errstate(all="ignore"):
-            t_cost, t_worst, _d = vw.cost(fc.forward(sub, ta, tm, dt), idx, dt)
-        accept = ok & np.isfinite(t_cost) & (t_cost < cost[idx])
-        if trace is not None:
-            trace.append(fc.trial_record(idx, lam, delta, cost, t_cost, accept))
-        step_small = (np.abs(ta - ang[idx]).max(1) <= fc.STEP_TOL) & (np.abs(delta[:, 20:23]).max(1) <= fc.STEP_TOL) & \
-                     (np.abs(delta[:, 23:26]).max(1) <= dt(fc.STEP_TOL) * extent[idx])
-        with np.errstate(invalid="ignore"):
-            flat = ~accept | (cost[idx] - t_cost <= dt(fc.DECREASE_TOL) * cost[idx])
-            stationary = ok & ~accept & (np.abs(t_cost - cost[idx]) <= dt(fc.FLAT_TOL) * cost[idx])
-        done = (ok & step_small & flat & (lam[idx] <= fc.LAMBDA_CONVERGED_MAX)) | stationary
-        acc = idx[accept]
-        ang[acc], m[acc], cost[acc], worst[acc] = ta[accept], tm[accept], t_cost[accept], t_worst[accept]
-        lam[idx] = np.where(accept, np.maximum(lam[idx] * dt(fc.LAMBDA_DOWN), dt(fc.LAMBDA_MIN)), lam[idx] * dt(fc.LAMBDA_UP))
-        iters[idx] += 1
-        status[idx[done]] |= CONVERGED
-        active[idx[done]] = False
-    status[active] |= AT_MAX_ITERS
-    with np.errstate(all="ignore"):
-        residual = vw.cost(fc.forward(hm, ang, m, dt), every, dt)[2]
-    residual = np.where(refused[:, None, None], 0.0, residual).astype(np.float32)
-    if box is None:
-        big = np.abs(ang) > dt(np.pi)
-        ang = np.where(big, fc.wrap(ang), ang)
-    out_ja = np.concatenate([ang, tail], 1)
-    out_xf = m.copy()
-    out_xf[mir == 1, :, 0] *= -1
-    out_xf[:, :3, 3] /= dt(t_scale)
-    if refused.any():
-        out_ja[refused] = np.where(bad_start[refused, None], 0, np.asarray(init[0]).astype(dt)[refused])
-        out_xf[refused] = np.where(bad_start[refused, None, None], np.eye(4), np.asarray(init[1]).astype(dt)[refused])
-    with np.errstate(invalid="ignore"):
-        info = np.stack([np.sqrt(cost / wsum), worst, iters.astype(dt), status.astype(dt)], 1)
-    info[refused, :3] = 0
-    return out_ja, out_xf, info, residual
+    prob = _Reprojection(hm, dtype, Views(window, cam_rows, table, weights, dtype))
+    with st.solver(solver):
+        return fc.lm(prob, limits, init, mirror, t_scale, max_iters, trace=trace) + (prob.residual,)
 
 
 # ----------------------------------------------------------------------------- cases
@@ -366,17 +319,14 @@ def landmarks(c, res):
 def distance(c, a, b):
     """How far two results of a case lie apart.  ang: the 20 angles modulo 2 pi and the entries of the wrist's rotation, rad.
     kp: landmarks through the float64 forward function of both, mm.  px: rms / worst of info."""
-    ang = max(fc.angle_distance(a["ja"][:, :20], b["ja"][:, :20]).max(),
-              np.abs(np.asarray(a["xf"], np.float64)[:, :3, :3] - np.asarray(b["xf"], np.float64)[:, :3, :3]).max())
     ia, ib = np.asarray(a["info"], np.float64), np.asarray(b["info"], np.float64)
-    return dict(ang=float(ang), kp=float(np.linalg.norm(landmarks(c, a) - landmarks(c, b), axis=-1).max()),
+    return dict(ang=st.angle_and_rotation_distance(a, b), kp=float(np.linalg.norm(landmarks(c, a) - landmarks(c, b), axis=-1).max()),
                 px=float(np.abs(ia[:, :2] - ib[:, :2]).max()))
 
 
 def float32_distance(c, want, max_iters=1):
     """The worst distance of the float32 restatements - one per solver of st.SOLVERS - from the float64 result `want`."""
-    ds = [distance(c, restate(c, np.float32, max_iters, s), want) for s in st.SOLVERS]
-    return {k: max(d[k] for d in ds) for k in ds[0]}
+    return st.worst([distance(c, restate(c, np.float32, max_iters, s), want) for s in st.SOLVERS])
 
 
 def bounds_from(d32):
@@ -387,8 +337,7 @@ def bounds_from(d32):
                 px=max(300.0 * 2.0 ** -23, st.FLOAT32_FACTOR * d32["px"]))
 
 
-def within(d, tol):
-    return all(d[k] <= tol[k] for k in ("ang", "kp", "px"))
+within = st.within
 
 
 # ----------------------------------------------------------------------------- full fits
