@@ -347,20 +347,15 @@ __global__ __launch_bounds__(64 * B_WAVES) void conv_block32_kernel(BlockLaunch 
 bool conv_block32_applicable(const BlockLaunch& b) {
   return b.in && b.out && b.w1_split && b.w2_split && b.bias1 && b.bias2 && b.in_max && b.tile_counter && b.num_cu > 0 &&
          b.unscale_w1 > 0.f && b.unscale_w2 > 0.f && b.n_img > 0 && b.H % BT_Y == 0 && b.W % BT_X == 0 &&
-         (size_t)b.n_img * b.H * b.W * 32 * sizeof(float) < 0x7FFFFF00ull;
+         offsets_fit_32(b.n_img, b.H, b.W, 32);
 }
 
 hipError_t launch_conv_block32(const BlockLaunch& b, hipStream_t s) {
   if (!conv_block32_applicable(b)) return hipErrorInvalidValue;
   const int tiles_x = b.W / BT_X, tiles_per_img = tiles_x * (b.H / BT_Y);
   const int n_tiles = b.n_img * tiles_per_img;
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t attr_e = set_dynamic_lds_once(attr_set, b.device, B_LDS, &conv_block32_kernel);
-  if (attr_e != hipSuccess) return attr_e;
-  int grid = b.num_cu;           // one 512-thread workgroup per CU (LDS: 156 KB)
-  if (grid > n_tiles) grid = n_tiles;
-  hipLaunchKernelGGL(conv_block32_kernel, dim3(grid), dim3(64 * B_WAVES), B_LDS, s, b, tiles_x, tiles_per_img, n_tiles);
-  return hipGetLastError();
+  // one 512-thread workgroup per CU (LDS: 156 KB)
+  return launch_with_lds<&conv_block32_kernel>(b.device, B_LDS, persistent_grid(b.num_cu, n_tiles), 64 * B_WAVES, s, b, tiles_x, tiles_per_img, n_tiles);
 }
 
 }  // namespace ut

@@ -376,19 +376,13 @@ __global__ __launch_bounds__(512, 1) void conv_c32s2_kernel(Stride2Launch p, int
 
 bool conv_c32s2_applicable(const Stride2Launch& c) {
   return c.in && c.out1 && c.out2 && c.w1_split && c.wd_split && c.unscale1 > 0.f && c.unscale_d > 0.f && c.in_max && c.W == 48 &&
-         c.H % 8 == 0 && c.H >= 8 && c.n_img > 0 && c.num_cu > 0 && (size_t)c.n_img * c.H * c.W * 32 * sizeof(float) < 0x7FFFFF00ull;
+         c.H % 8 == 0 && c.H >= 8 && c.n_img > 0 && c.num_cu > 0 && offsets_fit_32(c.n_img, c.H, c.W, 32);
 }
 
 hipError_t launch_conv_c32s2(const Stride2Launch& c, hipStream_t s) {
   if (!conv_c32s2_applicable(c)) return hipErrorInvalidValue;
   const int n_tiles = c.n_img * (c.H / 8);
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, S_LDS, &conv_c32s2_kernel);
-  if (attr_e != hipSuccess) return attr_e;
-  int grid = c.num_cu;
-  if (grid > n_tiles) grid = n_tiles;
-  hipLaunchKernelGGL(conv_c32s2_kernel, dim3(grid), dim3(512), S_LDS, s, c, n_tiles);
-  return hipGetLastError();
+  return launch_with_lds<&conv_c32s2_kernel>(c.device, S_LDS, persistent_grid(c.num_cu, n_tiles), 512, s, c, n_tiles);
 }
 
 }  // namespace ut

@@ -477,23 +477,18 @@ __global__ __launch_bounds__(512, 1) void conv_c64k_kernel(ConvLaunch p, int n_t
 }
 
 bool conv_c64k_applicable(const ConvLaunch& c) {
-  return !(c.no_resident & 1) && c.w_split && c.split_unscale > 0.f && c.ksize == 3 && c.stride == 1 && c.pad == 1 && c.cin == 64 && c.cout_store == 64 &&
+  return c.w_split && c.split_unscale > 0.f && c.ksize == 3 && c.stride == 1 && c.pad == 1 && c.cin == 64 && c.cout_store == 64 &&
          c.cslice == 32 && c.k_pad == 576 && c.cout_pad >= 64 && !c.out_nchw && c.splits == 0 && c.W <= 31 && c.H == c.Ho &&
          c.W == c.Wo && c.H * c.W <= K_MAXHW && c.H * c.W >= K_BM && c.num_cu > 0 &&
-         (size_t)c.n_img * c.H * c.W * 64 * sizeof(float) < 0x7FFFFF00ull;
+         offsets_fit_32(c.n_img, c.H, c.W, 64);
 }
 
 hipError_t launch_conv_c64k(const ConvLaunch& c, hipStream_t s) {
   if (!conv_c64k_applicable(c)) return hipErrorInvalidValue;
   const long M = (long)c.n_img * c.H * c.W;
   const int n_tiles = (int)((M + K_BM - 1) / K_BM);
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, K_LDS, &conv_c64k_kernel);
-  if (attr_e != hipSuccess) return attr_e;
-  int grid = c.num_cu;           // one 512-thread workgroup per CU, two waves per SIMD; tiles are dealt round robin (they all cost the same)
-  if (grid > n_tiles) grid = n_tiles;
-  hipLaunchKernelGGL(conv_c64k_kernel, dim3(grid), dim3(512), K_LDS, s, c, n_tiles);
-  return hipGetLastError();
+  // one 512-thread workgroup per CU, two waves per SIMD; tiles are dealt round robin (they all cost the same)
+  return launch_with_lds<&conv_c64k_kernel>(c.device, K_LDS, persistent_grid(c.num_cu, n_tiles), 512, s, c, n_tiles);
 }
 
 }  // namespace ut

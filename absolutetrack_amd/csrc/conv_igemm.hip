@@ -485,20 +485,12 @@ static hipError_t launch_cfg(const ConvLaunch& c, hipStream_t s) {
   const int tiles_n = (c.cout_store + BN - 1) / BN;
   const int n_tiles = tiles_m * tiles_n * (SPLITK ? c.splits : 1);      // queue entries
   const size_t lds = 2 * (size_t)(BM + BN) * LDS_ROW * sizeof(float) + 16;   // + tile-queue slot
-  // the attribute belongs to (kernel, device): one bit per device, set on the first launch there
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, (int)lds, &conv_igemm_kernel<BM, BN, WR, WC, NCHW, C32, SPLITK>);
-  if (attr_e != hipSuccess) return attr_e;
-  // persistent grid: as many workgroups as stay resident (LDS bound), never more than tiles
-  const int per_cu = (int)((160 * 1024) / lds);
-  int grid = c.num_cu * (per_cu < 1 ? 1 : per_cu);
-  if (grid > n_tiles) grid = n_tiles;
+  const int per_cu = (int)((160 * 1024) / lds);      // workgroups that stay resident (LDS bound)
+  const int grid = persistent_grid(c.num_cu, n_tiles, per_cu < 1 ? 1 : per_cu);
   // start stagger of co-resident workgroups: with r of them a chunk takes r x (its MFMA time) of wall time, so the
   // even spacing between ranks is one chunk's MFMA time = (MI*NI) x 16 MFMAs x 64 cycles = (MI*NI) x 2 units
   const int stagger = grid > c.num_cu ? (BM / WR / 32) * (BN / WC / 32) * 2 : 0;
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WR, WC, NCHW, C32, SPLITK>), dim3(grid), dim3(256), lds, s, c, tiles_n, n_tiles,
-                     stagger);
-  return hipGetLastError();
+  return launch_with_lds<&conv_igemm_kernel<BM, BN, WR, WC, NCHW, C32, SPLITK>>(c.device, (int)lds, grid, 256, s, c, tiles_n, n_tiles, stagger);
 }
 
 // out = act(bias + residual + slab_0 + slab_1 + ... ) in that order, 4 channels per thread (cout_store % 4 == 0)
@@ -535,11 +527,8 @@ hipError_t launch_conv_igemm(const ConvLaunch& c, hipStream_t s) {
   if (c.cin % 4 != 0 || c.cslice < BK || c.k_pad % BK != 0 || c.cout_pad % 128 != 0 || c.ksize * c.ksize > 9 ||
       c.num_cu <= 0)
     return hipErrorInvalidValue;
-  // 32-bit byte offsets into the activation / residual tensors
-  if ((size_t)c.n_img * c.H * c.W * c.cin * sizeof(float) >= 0x7FFFFF00ull) return hipErrorInvalidValue;
-  if ((size_t)c.n_img * c.Ho * c.Wo * c.cout_store * sizeof(float) >= 0x7FFFFF00ull) return hipErrorInvalidValue;
-  // One dispatch, by shape:
-  //  layer1 (3x3 stride 1, 32 -> 32 channels)                      halo-patch kernel (conv_patch.hip)
+  if (!offsets_fit_32(c.n_img, c.H, c.W, c.cin) || !offsets_fit_32(c.n_img, c.Ho, c.Wo, c.cout_store)) return hipErrorInvalidValue;
+  // The tile, by shape (which convolutions come here at all: ut_kernels.h::choose_conv):
   //  projection (the only NCHW output)                             64x128 tile
   //  backbone, cout <= 64  (channel slice == chunk width)          128x64 tile, three workgroups per CU
   //  few tiles (the head: 73,728 pixels = 576 tiles of 128 rows on 512 resident slots, i.e. two rounds the
@@ -548,14 +537,12 @@ hipError_t launch_conv_igemm(const ConvLaunch& c, hipStream_t s) {
   //  launches with fewer 64x64 tiles than CUs (a few crops)        64x64 tile
   if (c.splits > 1) {       // latency mode (ut_api.hip::run_conv): partial sums of K ranges into slabs of c.out
     if (c.out_nchw || c.res || c.relu || (c.k_pad / BK) % c.splits != 0 ||
-        (size_t)c.splits * c.n_img * c.Ho * c.Wo * c.cout_store * sizeof(float) >= 0x7FFFFF00ull)
+        !offsets_fit_32((size_t)c.splits * c.n_img, c.Ho, c.Wo, c.cout_store))
       return hipErrorInvalidValue;
     return c.cslice == BK ? launch_cfg<64, 64, 2, 2, false, true, true>(c, s) : launch_cfg<64, 64, 2, 2, false, false, true>(c, s);
   }
   const long M = (long)c.n_img * c.Ho * c.Wo;
   const bool few_tiles = ((M + 63) / 64) * ((c.cout_store + 63) / 64) <= (long)c.num_cu;
-  // (latency mode also takes layer1 of a few crops off the halo-patch kernel: 144 small tiles beat 24 large ones)
-  if (conv_patch_applicable(c) && !(c.splits == 1 && few_tiles)) return launch_conv_patch(c, s);
   if (c.out_nchw) return launch_cfg<64, 128, 1, 4, true>(c, s);
   const bool c32 = c.cslice == BK;          // scalar tap bookkeeping
   // a handful of crops (the per-frame tracker: 4 crops = 576 pixels at 12x12): fewer quarter-size tiles than CUs ->

@@ -369,7 +369,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_c32_patch_kernel(ConvLaunch p
 bool conv_patch_applicable(const ConvLaunch& c) {
   return c.ksize == 3 && c.stride == 1 && c.pad == 1 && c.cin == C && c.cout_store == C && c.cslice == C &&
          c.k_pad == 9 * C && c.H % TY == 0 && c.W % TX == 0 && !c.out_nchw && c.H == c.Ho && c.W == c.Wo &&
-         (size_t)c.n_img * c.H * c.W * C * sizeof(float) < 0x7FFFFF00ull;
+         offsets_fit_32(c.n_img, c.H, c.W, C);
 }
 
 hipError_t launch_conv_patch(const ConvLaunch& c, hipStream_t s) {
@@ -377,18 +377,10 @@ hipError_t launch_conv_patch(const ConvLaunch& c, hipStream_t s) {
   const int tiles_x = c.W / TX, tiles_per_img = tiles_x * (c.H / TY);
   const int n_tiles = c.n_img * tiles_per_img;
   const size_t lds = (size_t)(W_FLOATS + 2 * P_FLOATS) * sizeof(float) + 16;
-  // the attribute belongs to (kernel, device): one bit per device, set on the first launch there
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t attr_e =
-      set_dynamic_lds_once(attr_set, c.device, (int)lds, &conv3x3_c32_patch_kernel<false>, &conv3x3_c32_patch_kernel<true>);
-  if (attr_e != hipSuccess) return attr_e;
-  int grid = c.num_cu;           // one 512-thread workgroup per CU (LDS: 121 KB)
-  if (grid > n_tiles) grid = n_tiles;
-  if (c.w_split && c.split_unscale > 0.f)      // split-fp16 arithmetic (ut_set_conv_arithmetic)
-    hipLaunchKernelGGL(conv3x3_c32_patch_kernel<true>, dim3(grid), dim3(64 * NW), lds, s, c, tiles_x, tiles_per_img, n_tiles);
-  else
-    hipLaunchKernelGGL(conv3x3_c32_patch_kernel<false>, dim3(grid), dim3(64 * NW), lds, s, c, tiles_x, tiles_per_img, n_tiles);
-  return hipGetLastError();
+  const int grid = persistent_grid(c.num_cu, n_tiles);      // one 512-thread workgroup per CU (LDS: 121 KB)
+  if (!(c.w_split && c.split_unscale > 0.f))      // else: split-fp16 arithmetic (ut_set_conv_arithmetic)
+    return launch_with_lds<&conv3x3_c32_patch_kernel<false>, &conv3x3_c32_patch_kernel<true>>(c.device, (int)lds, grid, 64 * NW, s, c, tiles_x, tiles_per_img, n_tiles);
+  return launch_with_lds<&conv3x3_c32_patch_kernel<true>, &conv3x3_c32_patch_kernel<false>>(c.device, (int)lds, grid, 64 * NW, s, c, tiles_x, tiles_per_img, n_tiles);
 }
 
 }  // namespace ut

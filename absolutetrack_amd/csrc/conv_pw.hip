@@ -287,8 +287,7 @@ template <int KC, int NB0, int NB1, int NB2, bool NCHW, int NPASS, int WAVES>
 hipError_t pw_launch_cfg(const PwLaunch& c, hipStream_t s) {
   const int M = c.n_img * c.Ho * c.Wo;
   const int n_tiles = (M + 31) / 32;
-  int grid = (n_tiles + 3) / 4;
-  if (grid > WAVES * c.num_cu) grid = WAVES * c.num_cu;      // the workgroups that stay resident: WAVES waves per SIMD
+  const int grid = persistent_grid(c.num_cu, (n_tiles + 3) / 4, WAVES);      // the workgroups that stay resident: WAVES waves per SIMD
   hipLaunchKernelGGL((conv_pw_kernel<KC, NB0, NB1, NB2, NCHW, NPASS, WAVES>), dim3(grid), dim3(256), 0, s, c, n_tiles);
   return hipGetLastError();
 }
@@ -313,8 +312,7 @@ PwShape pw_shape(const PwLaunch& c) {
   if (c.cout_store != c.layer[c.n_layers - 1].cout_store) return r;
   if (c.out_nchw && c.n_layers != 1) return r;
   // 32-bit byte offsets below PW_OOB
-  if ((size_t)c.n_img * c.H * c.W * c.cin * sizeof(float) >= 0x7FFFFF00ull) return r;
-  if ((size_t)c.n_img * c.Ho * c.Wo * c.cout_store * sizeof(float) >= 0x7FFFFF00ull) return r;
+  if (!offsets_fit_32(c.n_img, c.H, c.W, c.cin) || !offsets_fit_32(c.n_img, c.Ho, c.Wo, c.cout_store)) return r;
   r.ok = true;
   return r;
 }

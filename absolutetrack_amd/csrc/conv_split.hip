@@ -648,13 +648,7 @@ hipError_t launch_split_cfg(const ConvLaunch& c, hipStream_t s) {
   const int tiles_n = (c.cout_store + BN - 1) / BN;
   const int n_tiles = tiles_m * tiles_n;
   const size_t lds = (HALO ? 2 * (size_t)320 * 128 : 3 * (size_t)BM * 128) + (HALO ? 4 : 3) * (size_t)BN * 128 + 256 + 16;
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, (int)lds, &conv_split_kernel<BM, BN, WR, WC, HALO>);
-  if (attr_e != hipSuccess) return attr_e;
-  int grid = c.num_cu;
-  if (grid > n_tiles) grid = n_tiles;
-  hipLaunchKernelGGL((conv_split_kernel<BM, BN, WR, WC, HALO>), dim3(grid), dim3(512), lds, s, c, tiles_n, n_tiles);
-  return hipGetLastError();
+  return launch_with_lds<&conv_split_kernel<BM, BN, WR, WC, HALO>>(c.device, (int)lds, persistent_grid(c.num_cu, n_tiles), 512, s, c, tiles_n, n_tiles);
 }
 
 }  // namespace
@@ -666,13 +660,8 @@ bool conv_split_applicable(const ConvLaunch& c) {
 
 hipError_t launch_conv_split(const ConvLaunch& c, hipStream_t s) {
   if (!conv_split_applicable(c)) return hipErrorInvalidValue;
-  if ((size_t)c.n_img * c.H * c.W * c.cin * sizeof(float) >= 0x7FFFFF00ull) return hipErrorInvalidValue;
-  if ((size_t)c.n_img * c.Ho * c.Wo * c.cout_store * sizeof(float) >= 0x7FFFFF00ull) return hipErrorInvalidValue;
-  // the stride-1 convolutions of layer2 .. layer4 and the stride-2 entries of layer3 / layer4 on whole-map tiles: four waves, weights
-  // global -> registers, the patch at padded image coordinates, no chunk synchronisation (conv_w4.hip)
-  if (conv_w4_applicable(c)) return launch_conv_w4(c, s);
-  // layer2's 64 -> 64 convolutions with the weights resident in registers (conv_c64k.hip): the form conv_w4 replaced, kept for A/B
-  if (conv_c64k_applicable(c)) return launch_conv_c64k(c, s);
+  if (!offsets_fit_32(c.n_img, c.H, c.W, c.cin) || !offsets_fit_32(c.n_img, c.Ho, c.Wo, c.cout_store)) return hipErrorInvalidValue;
+  // the chunked kernels only: what conv_w4.hip or conv_c64k.hip take instead never comes here (ut_kernels.h::choose_conv)
   // stride-1 3x3 from 64 input channels up (image rows of at most 31 pixels): the input halo resident in LDS
   const bool halo = c.ksize == 3 && c.stride == 1 && c.pad == 1 && c.cin >= 64 && c.W <= 31 && c.H == c.Ho && c.W == c.Wo;
   if (c.cout_store <= 64) return halo ? launch_split_cfg<256, 64, 8, 1, true>(c, s) : launch_split_cfg<256, 64, 8, 1, false>(c, s);

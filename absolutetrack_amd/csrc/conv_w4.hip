@@ -567,13 +567,7 @@ hipError_t launch_w4_cfg(const ConvLaunch& c, hipStream_t s) {
   const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = c.cout_store / BN;
   const int n_tiles = tiles_m * tiles_n;
   constexpr int lds = (SCH == 32 ? 2 : 3) * (SCH / 4) * w4_cap(BM, WI, HI) * 16 + 16 + 4 * 4096;
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t attr_e = set_dynamic_lds_once(attr_set, c.device, lds, &conv_w4_kernel<WI, HI, SCH, WPX, S2>);
-  if (attr_e != hipSuccess) return attr_e;
-  int grid = c.num_cu;
-  if (grid > n_tiles) grid = n_tiles;
-  hipLaunchKernelGGL((conv_w4_kernel<WI, HI, SCH, WPX, S2>), dim3(grid), dim3(256), lds, s, c, tiles_n, n_tiles);
-  return hipGetLastError();
+  return launch_with_lds<&conv_w4_kernel<WI, HI, SCH, WPX, S2>>(c.device, lds, persistent_grid(c.num_cu, n_tiles), 256, s, c, tiles_n, n_tiles);
 }
 
 }  // namespace
@@ -581,26 +575,26 @@ hipError_t launch_w4_cfg(const ConvLaunch& c, hipStream_t s) {
 // (the map sizes are template parameters - taps and padded rows are immediates of the fragment reads: the backbone's 12x12 and 6x6 maps
 // with 128-channel tiles, its 24x24 maps with 64 -> 64 channels as tiles of one whole map; stride 2: the entries of layer3 and layer4,
 // 12x12 and 6x6 OUTPUT maps)
-bool conv_w4_applicable(const ConvLaunch& c) {
-  const bool common = !(c.no_resident & 2) && c.w_split && c.split_unscale > 0.f && c.ksize == 3 && c.pad == 1 && c.cslice == 32 &&
+W4Form conv_w4_form(const ConvLaunch& c) {
+  const bool common = c.w_split && c.split_unscale > 0.f && c.ksize == 3 && c.pad == 1 && c.cslice == 32 &&
                       c.cin % 32 == 0 && c.cout_pad >= c.cout_store && !c.out_nchw && c.splits == 0 &&
                       c.k_pad == 9 * c.cin && c.tile_counter && c.num_cu > 0 &&
-                      (size_t)c.n_img * c.H * c.W * c.cin * sizeof(float) < 0x7FFFFF00ull &&
-                      (size_t)c.n_img * c.Ho * c.Wo * c.cout_store * sizeof(float) < 0x7FFFFF00ull;
-  if (!common) return false;
+                      offsets_fit_32(c.n_img, c.H, c.W, c.cin) && offsets_fit_32(c.n_img, c.Ho, c.Wo, c.cout_store);
+  if (!common) return W4_NONE;
   if (c.stride == 2)      // phase planes
-    return !(c.no_resident & 8) && c.cin >= 64 /* (what the tests cover: 64 and 128; two-slice tiles are untested) */ && c.cout_store % 128 == 0 && c.H == 2 * c.Ho && c.W == 2 * c.Wo && !c.res &&
-           ((c.Wo == 12 && c.Ho == 12) || (c.Wo == 6 && c.Ho == 6));
-  if (c.stride != 1 || c.cin < 64 || c.H != c.Ho || c.W != c.Wo) return false;
-  if (c.k_cin != 0 && (c.k_cin % 32 != 0 || c.k_cin < 64 || c.k_cin > c.cin)) return false;
-  if (c.cout_store % 128 == 0) return (c.W == 12 && c.H == 12) || (c.W == 6 && c.H == 6);
-  return !(c.no_resident & 4) && c.cout_store == 64 && c.W == 24 && c.H == 24;
+    return c.cin >= 64 /* (what the tests cover: 64 and 128; two-slice tiles are untested) */ && c.cout_store % 128 == 0 && c.H == 2 * c.Ho && c.W == 2 * c.Wo && !c.res &&
+           ((c.Wo == 12 && c.Ho == 12) || (c.Wo == 6 && c.Ho == 6)) ? W4_STRIDE2 : W4_NONE;
+  if (c.stride != 1 || c.cin < 64 || c.H != c.Ho || c.W != c.Wo) return W4_NONE;
+  if (c.k_cin != 0 && (c.k_cin % 32 != 0 || c.k_cin < 64 || c.k_cin > c.cin)) return W4_NONE;
+  if (c.cout_store % 128 == 0) return (c.W == 12 && c.H == 12) || (c.W == 6 && c.H == 6) ? W4_TILES128 : W4_NONE;
+  return c.cout_store == 64 && c.W == 24 && c.H == 24 ? W4_MAP24 : W4_NONE;
 }
 
 hipError_t launch_conv_w4(const ConvLaunch& c, hipStream_t s) {
-  if (!conv_w4_applicable(c)) return hipErrorInvalidValue;
-  if (c.stride == 2) return c.Wo == 12 ? launch_w4_cfg<12, 12, 32, 1, true>(c, s) : launch_w4_cfg<6, 6, 32, 1, true>(c, s);
-  if (c.W == 24) return launch_w4_cfg<24, 24, 16, 2>(c, s);
+  const W4Form form = conv_w4_form(c);
+  if (form == W4_NONE) return hipErrorInvalidValue;
+  if (form == W4_STRIDE2) return c.Wo == 12 ? launch_w4_cfg<12, 12, 32, 1, true>(c, s) : launch_w4_cfg<6, 6, 32, 1, true>(c, s);
+  if (form == W4_MAP24) return launch_w4_cfg<24, 24, 16, 2>(c, s);
   return c.W == 12 ? launch_w4_cfg<12, 12, 32, 1>(c, s) : launch_w4_cfg<6, 6, 32, 1>(c, s);
 }
 

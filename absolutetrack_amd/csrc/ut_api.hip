@@ -364,18 +364,15 @@ int begin_call(ut_handle h, hipStream_t s) {
   return UT_OK;
 }
 
-// the next launch's index into the per-launch words; *recycled (optional): taking it zeroed the words, so every max word an
-// earlier launch of the call left is stale
-int next_launch_word(ut_handle h, hipStream_t s, int* idx, bool* recycled = nullptr) {
-  const bool full = h->counter_next >= kMaxCounters;
-  if (full) {   // recycle: stream order puts the memset behind the earlier launches
-    int rc0 = begin_call(h, s);
-    if (rc0) return rc0;
-  }
-  if (recycled) *recycled = full;
-  *idx = h->counter_next++;
-  return UT_OK;
+// The lease on the per-launch words: the next n launches take theirs (take_word) from one zeroing, so that a word handed from one
+// of them to the next stays live.  With fewer than n left the words are zeroed (in stream order, behind the earlier launches) and
+// handed out again; *zeroed (optional) reports it: every max word an earlier launch of the call left is stale then.
+int lease_words(ut_handle h, hipStream_t s, int n, bool* zeroed = nullptr) {
+  const bool full = h->counter_next + n > kMaxCounters;
+  if (zeroed) *zeroed = full;
+  return full ? begin_call(h, s) : UT_OK;
 }
+int take_word(ut_handle h) { return h->counter_next++; }      // index of the next launch's words, inside a lease
 
 // The scale word a split-fp16 consumer of tensor `tid` reads, and the word it guards against: calibrated mode - the handle's
 // calibrated word, guarded by the word the producer left in this call (may be null); adaptive mode - the same, and the consumer
@@ -389,6 +386,11 @@ ScaleRef scale_for(ut_handle h, int tid, const unsigned* producer_word) {
   else { r.word = h->calib + tid; r.obs = producer_word; }
   if (!h->calibrating && h->scale_mode == UT_SPLIT_SCALE_CALIBRATED_ADAPTIVE && r.obs) { r.adaptive = 1; r.adapt_count = h->adapt_count; }
   return r;
+}
+// the scale fields that ConvLaunch, BlockLaunch and Stride2Launch share
+template <class Launch>
+void set_scale(Launch& l, const ScaleRef& sr, int* status) {
+  l.in_max = sr.word; l.in_obs = sr.obs; l.split_adaptive = sr.adaptive; l.adapt_count = sr.adapt_count; l.status = status;
 }
 // One convolution launch (`launch()` enqueues kernel `what`).  A calibration pass first folds the producer's word of the
 // input tensor `in_tid` into its calibrated word; while the handle profiles, two events time the launch, kept with its flops
@@ -428,12 +430,12 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
   c.k_cin = h->block_fusion && cw.k_cin < cw.cin_pad ? cw.k_cin : 0;     // (the switch off: every convolution walks its whole K)
   c.ksize = cw.ksize; c.stride = cw.stride; c.pad = cw.pad;
   c.relu = relu; c.out_nchw = nchw;
-  c.device = h->device; c.num_cu = h->num_cu; { static const int kMask[7] = {15, 0, 14, 9, 12, 13, 8}; c.no_resident = kMask[h->resident_weights]; }      // (ut_kernels.h::ConvLaunch::no_resident)
-  int word = 0;
-  bool recycled = false;
-  int rc = next_launch_word(h, s, &word, &recycled);
+  c.device = h->device; c.num_cu = h->num_cu; c.no_resident = ut::kResidentKinds[h->resident_weights];
+  bool zeroed = false;
+  int rc = lease_words(h, s, 1, &zeroed);
   if (rc) return rc;
-  if (recycled) in_max = nullptr;      // recycled in mid-call: the producer's word has just been zeroed
+  if (zeroed) in_max = nullptr;      // zeroed in mid-call: the producer's word is gone
+  const int word = take_word(h);
   c.tile_counter = h->counters + word;
   // Latency mode: a convolution of a few crops has far fewer 64x64 tiles than the chip has CUs and every workgroup
   // walks all of K alone (a layer-4 conv of 4 crops: 12 tiles x 72 chunks).  Cut K into S equal chunk ranges (S the
@@ -462,20 +464,15 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
   const ScaleRef sr = scale_for(h, in_tid, in_max);
   c.w_split = sr.word ? cw.w_split : nullptr;
   c.split_unscale = cw.split_unscale;
-  c.status = h->status;
-  c.in_max = sr.word;
-  c.in_obs = sr.obs;
-  c.split_adaptive = sr.adaptive;
-  c.adapt_count = sr.adapt_count;
-  const int kind = c.w_split && (ut::conv_split_applicable(c) || ut::conv_patch_applicable(c)) ? 1 : 0;
+  set_scale(c, sr, h->status);
+  const ut::ConvKernel kernel = ut::choose_conv(c);
+  const int kind = c.w_split && kernel != ut::CONV_IGEMM ? 1 : 0;      // every other kernel computes in split-fp16 when it has the planes
   if (kind) {
     c.out_max = h->counters + kMaxCounters + word;
     if (out_max) *out_max = c.out_max;
   }
-  const bool split = c.w_split && ut::conv_split_applicable(c);
   return bracket_launch(h, s, kind ? in_tid : -1, in_max, cw.flops_per_pixel * (double)n_img * c.Ho * c.Wo, kind,
-                        split ? "launch_conv_split" : "launch_conv_igemm",
-                        [&] { return split ? ut::launch_conv_split(c, s) : ut::launch_conv_igemm(c, s); });
+                        ut::kConvKernelName[kernel], [&] { return ut::launch_conv_on(kernel, c, s); });
 }
 
 // 1x1 convolutions without residual, alone or as a chain whose intermediates nothing else reads, in one streaming launch
@@ -511,12 +508,10 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
               int W, hipStream_t s, const unsigned* x_max = nullptr, unsigned** y_max = nullptr, int x_tid = -1, int mid_tid = -1) {
   int rc;
   if (y_max) *y_max = nullptr;
-  // the words of one block (at most three launches) come from one zeroing: a word handed from conv1 to conv2 is never recycled
-  // between the two (x's own word is gone after a recycle: its consumers then run unguarded / on the fp32 instruction)
-  if (h->counter_next + 8 > kMaxCounters) {
-    if ((rc = begin_call(h, s))) return rc;
-    x_max = nullptr;
-  }
+  // the words of one block (at most three launches): the word conv1 hands to conv2 stays live between the two
+  bool zeroed = false;
+  if ((rc = lease_words(h, s, 8, &zeroed))) return rc;
+  if (zeroed) x_max = nullptr;
   const ScaleRef xs = scale_for(h, x_tid, x_max);
   // layer1 in split-fp16 mode: the whole block in one launch, the intermediate stays in LDS (conv_block32.hip)
   if (h->block_fusion && xs.word && !b.has_ds && b.conv1.w_split && b.conv2.w_split && b.conv1.stride == 1 &&
@@ -526,21 +521,16 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
     bl.unscale_w1 = b.conv1.split_unscale; bl.unscale_w2 = b.conv2.split_unscale;
     bl.bias1 = b.conv1.bias; bl.bias2 = b.conv2.bias;
     bl.wsum1 = b.conv1.wsum_rows; bl.bmax1 = b.conv1.bias_max;
-    bl.in_max = xs.word; bl.in_obs = xs.obs; bl.split_adaptive = xs.adaptive; bl.adapt_count = xs.adapt_count; bl.status = h->status;
+    set_scale(bl, xs, h->status);
     bl.n_img = n_img; bl.H = H; bl.W = W; bl.device = h->device; bl.num_cu = h->num_cu;
-    if (ut::conv_block32_applicable((bl.tile_counter = h->counters, bl))) {
-      int word = 0;
-      bool recycled = false;
-      if ((rc = next_launch_word(h, s, &word, &recycled))) return rc;
-      if (!recycled) {          // (never a recycle here: the block's words were reserved above)
-        bl.tile_counter = h->counters + word;
-        bl.out_max = h->counters + kMaxCounters + word;
-        const double flops = (b.conv1.flops_per_pixel + b.conv2.flops_per_pixel) * (double)n_img * H * W;
-        if ((rc = bracket_launch(h, s, x_tid, x_max, flops, 1, "launch_conv_block32", [&] { return ut::launch_conv_block32(bl, s); })))
-          return rc;
-        if (y_max) *y_max = bl.out_max;
-        return UT_OK;
-      }
+    bl.tile_counter = h->counters + h->counter_next;      // the word it takes if it applies
+    if (ut::conv_block32_applicable(bl)) {
+      bl.out_max = h->counters + kMaxCounters + take_word(h);
+      const double flops = (b.conv1.flops_per_pixel + b.conv2.flops_per_pixel) * (double)n_img * H * W;
+      if ((rc = bracket_launch(h, s, x_tid, x_max, flops, 1, "conv_block32", [&] { return ut::launch_conv_block32(bl, s); })))
+        return rc;
+      if (y_max) *y_max = bl.out_max;
+      return UT_OK;
     }
   }
   // layer2's entry in split-fp16 mode: the stride-2 3x3 and the 1x1 shortcut from one pass over x (conv_c32s2.hip)
@@ -550,19 +540,14 @@ int run_block(ut_handle h, const Block& b, const float* x, float* tmp, float* ds
     sl.in = x; sl.out1 = tmp; sl.out2 = dsbuf; sl.w1_split = b.conv1.w_split; sl.wd_split = b.ds.w_split;
     sl.unscale1 = b.conv1.split_unscale; sl.unscale_d = b.ds.split_unscale;
     sl.bias1 = b.conv1.bias; sl.bias_d = b.ds.bias;
-    sl.in_max = xs.word; sl.in_obs = xs.obs; sl.split_adaptive = xs.adaptive; sl.adapt_count = xs.adapt_count; sl.status = h->status;
+    set_scale(sl, xs, h->status);
     sl.n_img = n_img; sl.H = H; sl.W = W; sl.device = h->device; sl.num_cu = h->num_cu;
     if (ut::conv_c32s2_applicable(sl)) {
-      int word = 0;
-      bool recycled = false;
-      if ((rc = next_launch_word(h, s, &word, &recycled))) return rc;
-      if (!recycled) {
-        sl.out1_max = h->counters + kMaxCounters + word;
-        const double flops = (b.conv1.flops_per_pixel + b.ds.flops_per_pixel) * (double)n_img * (H / 2) * (W / 2);
-        if ((rc = bracket_launch(h, s, x_tid, x_max, flops, 1, "launch_conv_c32s2", [&] { return ut::launch_conv_c32s2(sl, s); })))
-          return rc;
-        return run_conv(h, b.conv2, tmp, dsbuf, y, n_img, H / 2, W / 2, true, false, s, sl.out1_max, y_max, mid_tid);
-      }
+      sl.out1_max = h->counters + kMaxCounters + take_word(h);
+      const double flops = (b.conv1.flops_per_pixel + b.ds.flops_per_pixel) * (double)n_img * (H / 2) * (W / 2);
+      if ((rc = bracket_launch(h, s, x_tid, x_max, flops, 1, "conv_c32s2", [&] { return ut::launch_conv_c32s2(sl, s); })))
+        return rc;
+      return run_conv(h, b.conv2, tmp, dsbuf, y, n_img, H / 2, W / 2, true, false, s, sl.out1_max, y_max, mid_tid);
     }
   }
   unsigned* tmp_max = nullptr;
@@ -755,9 +740,9 @@ static int run_stem(ut_handle h, const float* crops, const uint8_t* crops_u8, fl
                     unsigned** out_max) {
   *out_max = nullptr;
   if (h->call_split && !h->latency_mode) {
-    int word = 0, rc = next_launch_word(h, st, &word);
+    const int rc = lease_words(h, st, 1);
     if (rc) return rc;
-    *out_max = h->counters + kMaxCounters + word;
+    *out_max = h->counters + kMaxCounters + take_word(h);
   }
   if (crops_u8) HIPCHK(h, ut::launch_stem_u8(crops_u8, h->stem_w, h->stem_b, out, n, *out_max, st));
   else HIPCHK(h, ut::launch_stem(crops, h->stem_w, h->stem_b, out, n, *out_max, st));
@@ -771,7 +756,7 @@ static int backbone_pass(ut_handle h, const float* crops, const uint8_t* crops_u
   int rc;
   const size_t a48 = (size_t)off * 48 * 48 * 32, a24 = (size_t)off * 24 * 24 * 64, a12 = (size_t)off * 12 * 12 * 128;
   // the words of one pass (<= 2 x 22 + 16 launches) come from one zeroing, so that none of them is recycled while live
-  if (h->counter_next + 256 > kMaxCounters && (rc = begin_call(h, s))) return rc;
+  if ((rc = lease_words(h, s, 256))) return rc;
   // ---- phase A: stem + layer1 (48x48x32) + layer2 (24x24x64), `chunk` crops per pass
   unsigned* l2_max = nullptr;      // max word of bufL2: the passes' words merged when phase A took more than one pass
   const unsigned l2_gen = h->word_gen;
@@ -1066,10 +1051,8 @@ static int run_head(ut_handle h, const ut::HeadArgs& a, const float* skel, int n
   const int tid0 = mode == UT_MODE_KNOWN_SKELETON ? 25 : 29;
   unsigned* in_word = nullptr;
   if (head_split) {
-    int word = 0;
-    if (h->counter_next + 16 > kMaxCounters && (rc = begin_call(h, s))) return rc;
-    if ((rc = next_launch_word(h, s, &word))) return rc;
-    in_word = h->counters + kMaxCounters + word;
+    if ((rc = lease_words(h, s, 16))) return rc;
+    in_word = h->counters + kMaxCounters + take_word(h);
   }
   HIPCHK(h, ut::launch_temporal_out(a, b.t92b, b.skel, n_skel, b.regin, reg.c, stride, in_word, s));
   // two BasicBlocks on the 6x6 map (lib/models/model_utils.py:195-208)

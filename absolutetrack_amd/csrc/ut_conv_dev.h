@@ -1,6 +1,6 @@
 // What the hand-written convolution kernels (conv_*.hip) share: vector types, buffer-resource words, the LDS-DMA piece, the
 // two-piece fp16 split, the tile-queue hand-over word, the accumulator-register constraints of the register-resident kernels
-// and the launchers' once-per-device LDS attribute.  Included after ut_kernels.h.  Everything sits in an anonymous namespace:
+// and the launchers' host tail.  Included after ut_kernels.h.  Everything sits in an anonymous namespace:
 // a translation unit has its own copy, so two builds of one kernel (tools/diag patches copies of the sources) link into one
 // library.  The device functions are forced inline: sharing them here costs a kernel no instruction.
 #pragma once
@@ -86,20 +86,32 @@ __device__ __forceinline__ int slot_read(unsigned lds_addr) {
   return __builtin_amdgcn_readfirstlane(v);
 }
 
-// Host: hipFuncAttributeMaxDynamicSharedMemorySize belongs to (kernel, device).  `attr_set` is the caller's static word for
-// these kernels (one per kernel instantiation, or one for kernels that are always set together), one bit per device: the
-// attribute is set on the first launch there.  A device index outside 0..63 has no bit and sets it every time.
-template <typename... Kernel>
-hipError_t set_dynamic_lds_once(std::atomic<unsigned long long>& attr_set, int device, int bytes, Kernel*... kernels) {
+// Host: the tail of every launcher here - the dynamic-LDS attribute, the launch, its error.
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to (kernel, device): the static word of this template (one per Kernel; SetWith
+// names the instantiations that are always set together with it) has one bit per device, and the attribute is set on the first
+// launch there.  A device index outside 0..63 has no bit and sets it every time.
+template <auto Kernel, auto... SetWith, typename... Args>
+hipError_t launch_with_lds(int device, int lds_bytes, int grid, int block, hipStream_t s, const Args&... args) {
+  static std::atomic<unsigned long long> attr_set{0};
   const unsigned long long dev_bit = (device >= 0 && device < 64) ? 1ull << device : 0ull;
-  if (dev_bit && (attr_set.load(std::memory_order_relaxed) & dev_bit)) return hipSuccess;
-  for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
-    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
+  if (!dev_bit || !(attr_set.load(std::memory_order_relaxed) & dev_bit)) {
+    for (const void* k : {reinterpret_cast<const void*>(Kernel), reinterpret_cast<const void*>(SetWith)...}) {
+      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+      if (e != hipSuccess) return e;
+    }
+    attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
   }
-  attr_set.fetch_or(dev_bit, std::memory_order_relaxed);
-  return hipSuccess;
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds_bytes, s, args...);
+  return hipGetLastError();
 }
+
+// Host: workgroups of a persistent grid that drains a tile queue - as many as stay resident, never more than tiles
+inline int persistent_grid(int num_cu, int n_tiles, int per_cu = 1) {
+  return num_cu * per_cu < n_tiles ? num_cu * per_cu : n_tiles;
+}
+
+// Host: an fp32 tensor of n x h x w x ch elements that the kernels address with 32-bit byte offsets (buffer descriptors)
+inline bool offsets_fit_32(size_t n, size_t h, size_t w, size_t ch) { return n * h * w * ch * sizeof(float) < 0x7FFFFF00ull; }
 
 }  // namespace
 }  // namespace ut

@@ -47,9 +47,8 @@ struct ConvLaunch {
   int device;          // HIP device the launch goes to (the dynamic-LDS attribute is set once per device)
   int num_cu;          // compute units of the device (persistent grid sizing)
   unsigned* tile_counter;   // device word, zero before the launch: dynamic tile queue of the persistent grid
-  int no_resident;     // split kernels, A/B tests (ut_set_resident_weights): bit 0 = not conv_c64k.hip, bit 1 = not conv_w4.hip, bit 2 =
-                       // not conv_w4.hip on the 24x24x64 maps (conv_c64k / the chunked conv_split kernels take those layers), bit 3 = not
-                       // conv_w4.hip's phase-plane form on the stride-2 entries of layer3 / layer4 (the chunked gather kernel takes them)
+  int no_resident;     // split kernels, A/B tests: the NO_* bits of the handle's ut_set_resident_weights kind (kResidentKinds below);
+                       // read by choose_conv alone - no kernel and no shape predicate looks at it
   int splits;          // > 1 (latency mode): K is cut in `splits` equal chunk ranges, out = [splits][M][cout_store] slabs;
                        // 1 = latency mode without a split (prefers small tiles); 0 = throughput dispatch
 };
@@ -107,7 +106,9 @@ bool conv_c32s2_applicable(const Stride2Launch& c);
 hipError_t launch_conv_c32s2(const Stride2Launch& c, hipStream_t s);
 // 3x3 stride-1 from >= 64 channels to a multiple of 128 channels: four waves of 128 x 64, weights straight from global memory into
 // registers, the patch split on its way into LDS, one barrier per slice (conv_w4.hip); conv_split_kernel<256, 128, 4, 2, true>'s bits
-bool conv_w4_applicable(const ConvLaunch& c);
+// the form a launch takes there: 128-channel tiles of the 12x12 / 6x6 maps, one 24x24 map x 64 channels, the phase planes of a stride-2 entry
+enum W4Form : int { W4_NONE = 0, W4_TILES128, W4_MAP24, W4_STRIDE2 };
+W4Form conv_w4_form(const ConvLaunch& c);
 hipError_t launch_conv_w4(const ConvLaunch& c, hipStream_t s);
 // 3x3 stride-1 64 -> 64 channels with the weights resident in registers, K split across the two waves of a SIMD (conv_c64k.hip)
 bool conv_c64k_applicable(const ConvLaunch& c);
@@ -150,6 +151,65 @@ hipError_t launch_calibration_crops(float* crops, int n, hipStream_t s);
 // 3x3 stride-1 32->32 channel convs with the halo patch resident in LDS (conv_patch.hip)
 bool conv_patch_applicable(const ConvLaunch& c);
 hipError_t launch_conv_patch(const ConvLaunch& c, hipStream_t s);
+
+// Which kernel runs a ConvLaunch: each launcher above runs its own kernel or refuses, choose_conv decides which one it is.
+enum ConvKernel : int { CONV_IGEMM = 0, CONV_PATCH, CONV_SPLIT, CONV_W4, CONV_C64K };
+constexpr const char* kConvKernelName[5] = {"conv_igemm", "conv_patch", "conv_split", "conv_w4", "conv_c64k"};
+
+// ConvLaunch::no_resident: what an A/B kind of ut_set_resident_weights keeps split-fp16 launches off
+enum : int {
+  NO_C64K = 1,         // conv_c64k.hip
+  NO_W4 = 2,           // conv_w4.hip in any form (its 128-channel tiles on the 12x12 / 6x6 maps have no bit of their own)
+  NO_W4_MAP24 = 4,     // conv_w4.hip on the 24x24x64 maps (conv_c64k / the chunked kernel take layer2)
+  NO_W4_STRIDE2 = 8,   // conv_w4.hip's phase-plane form on the stride-2 entries of layer3 / layer4 (the chunked gather kernel takes them)
+};
+constexpr int kResidentKinds[7] = {
+    NO_C64K | NO_W4 | NO_W4_MAP24 | NO_W4_STRIDE2,            // 0: the chunked kernels everywhere
+    0,                                                        // 1 (default): conv_w4 wherever it applies
+    NO_W4 | NO_W4_MAP24 | NO_W4_STRIDE2,                      // 2: conv_c64k on 24x24, chunked elsewhere
+    NO_C64K | NO_W4_STRIDE2,                                  // 3: conv_w4 on the stride-1 convolutions of all three sizes
+    NO_W4_MAP24 | NO_W4_STRIDE2,                              // 4: conv_w4 at 12x12 / 6x6, conv_c64k at 24x24
+    NO_C64K | NO_W4_MAP24 | NO_W4_STRIDE2,                    // 5: conv_w4 at 12x12 / 6x6, chunked at 24x24
+    NO_W4_STRIDE2,                                            // 6: as 1 with the stride-2 entries through the chunked gather kernel
+};
+
+// the patch kernel's row of the dispatch: layer1's shape, except that latency mode (splits == 1) keeps a launch of fewer 64x64
+// tiles than CUs on conv_igemm's small tiles (layer1 of a few crops: 144 small tiles beat 24 large ones)
+inline bool conv_prefers_patch(const ConvLaunch& c) {
+  const long m = (long)c.n_img * c.Ho * c.Wo;
+  const bool few_tiles = ((m + 63) / 64) * ((c.cout_store + 63) / 64) <= (long)c.num_cu;
+  return conv_patch_applicable(c) && !(c.splits == 1 && few_tiles);
+}
+
+// The one place that orders the kernels: first match wins (DESIGN.md section 4 reads it out by layer and mode).
+inline ConvKernel choose_conv(const ConvLaunch& c) {
+  if (c.splits > 1) return CONV_IGEMM;      // split-K launch of latency mode
+  if (c.w_split && conv_split_applicable(c)) {      // split-fp16: conv_w4 in a form the kind allows, else conv_c64k, else chunked
+    const int off = c.no_resident;      // the NO_* bits of the handle's kind
+    const W4Form form = conv_w4_form(c);
+    const int form_bit = form == W4_MAP24 ? NO_W4_MAP24 : form == W4_STRIDE2 ? NO_W4_STRIDE2 : 0;
+    if (form != W4_NONE && !(off & (NO_W4 | form_bit))) return CONV_W4;
+    if (conv_c64k_applicable(c) && !(off & NO_C64K)) return CONV_C64K;
+    return CONV_SPLIT;
+  }
+  return conv_prefers_patch(c) ? CONV_PATCH : CONV_IGEMM;
+}
+
+// one convolution on kernel k; launch_conv: on the kernel choose_conv names, *ran (optional) receives which
+inline hipError_t launch_conv_on(ConvKernel k, const ConvLaunch& c, hipStream_t s) {
+  switch (k) {
+    case CONV_PATCH: return launch_conv_patch(c, s);
+    case CONV_SPLIT: return launch_conv_split(c, s);
+    case CONV_W4: return launch_conv_w4(c, s);
+    case CONV_C64K: return launch_conv_c64k(c, s);
+    default: return launch_conv_igemm(c, s);
+  }
+}
+inline hipError_t launch_conv(const ConvLaunch& c, hipStream_t s, ConvKernel* ran = nullptr) {
+  const ConvKernel k = choose_conv(c);
+  if (ran) *ran = k;
+  return launch_conv_on(k, c, s);
+}
 
 // stem: conv3x3(1->32,pad 1)+BN+ReLU+maxpool2 ; crops [n,96,96] -> NHWC [n,48,48,32]
 // out_max: optional device word (zero before the launch) that receives the bits of the largest output

@@ -70,6 +70,29 @@ def test_backbone_matches_oracle(engine):
     assert torch.equal(got, got2)
 
 
+@pytest.mark.parametrize("which, n_crops", [("engine", 384), ("split_engine", 540)])
+def test_backbone_call_that_outlives_a_word_lease(request, which, n_crops):
+    """One backbone call of more convolution launches than the handle has per-launch words (4096 tile-queue words, 4096 max
+    words): at one crop per phase-A pass a crop costs 11 launches in fp32 and 8 in split-fp16 mode (calibrated scales, which do
+    not depend on the batch), phase B another 17, so the words are zeroed and handed out again in mid-call.  The features are
+    the bits of the same crops at the default chunk size, and nothing is reported."""
+    eng = request.getfixturevalue(which)
+    crops = _dev(synth.synthetic_crops(n_crops, seed=41))
+    want = eng.backbone(crops).cpu()
+    eng.set_backbone_chunk(1)
+    try:
+        eng.profile_begin()
+        got = eng.backbone(crops).cpu()
+        by_kind = eng.profile_end_by_kind()
+    finally:
+        eng.set_backbone_chunk(0)
+    launches = by_kind[0][1] + by_kind[1][1]
+    print(f"{which}: {n_crops} crops, convolution launches by kind {by_kind[0][1]} + {by_kind[1][1]} = {launches}")
+    assert launches >= 4096 + 64, by_kind
+    assert torch.equal(got, want)
+    eng.poll_status()
+
+
 def test_backbone_edge_batches(engine):
     assert engine.backbone(torch.empty(0, 96, 96, device=DEV)).shape == (0, 72, 6, 6)
     one = synth.synthetic_crops(1, seed=9)

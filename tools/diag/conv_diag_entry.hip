@@ -1,4 +1,6 @@
-// Diagnostic entry (not part of libumetrack_hip.so): one stride-1 3x3 convolution through launch_conv_igemm.
+// Diagnostic entry (not part of libumetrack_hip.so): one stride-1 3x3 fp32 convolution on the kernel the product picks for it.  Its
+// scripts link conv_igemm.hip and conv_patch.hip alone, so it follows the dispatcher's rows of those two (ut_kernels.h::choose_conv
+// ends in them for a launch without split planes) instead of calling launch_conv, which names every kernel.
 
 #include "ut_kernels.h"
 #ifdef DIAG_WS
@@ -20,6 +22,6 @@ extern "C" int conv_diag(const float* in, const float* w, const float* bias, con
 #ifdef DIAG_WS
   return (int)ut::launch_conv_ws(c, 0);
 #else
-  return (int)ut::launch_conv_igemm(c, 0);
+  return (int)(ut::conv_prefers_patch(c) ? ut::launch_conv_patch(c, 0) : ut::launch_conv_igemm(c, 0));
 #endif
 }

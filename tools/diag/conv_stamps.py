@@ -72,7 +72,8 @@ extern "C" int conv_diag(const float* in, const float* w, const float* bias, con
   if (!cnt) (void)hipMalloc((void**)&cnt, 4);
   (void)hipMemsetAsync(cnt, 0, 4, 0);
   c.tile_counter = cnt;
-  return (int)ut::launch_conv_igemm(c, 0);
+  // the product's choice between the two kernels linked here (ut_kernels.h::choose_conv without split planes): only conv_igemm stamps
+  return (int)(ut::conv_prefers_patch(c) ? ut::launch_conv_patch(c, 0) : ut::launch_conv_igemm(c, 0));
 }
 ''')
 so = "/tmp/libconvstamps.so"

@@ -1,5 +1,6 @@
-// Diagnostic entry (not part of libumetrack_hip.so): one convolution through launch_conv_igemm (mode 0) or
-// launch_conv_split (mode 1), and the host-side weight split.
+// Diagnostic entry (not part of libumetrack_hip.so): one convolution on the kernel the product's dispatcher picks for it
+// (ut_kernels.h::launch_conv) - without the split planes (mode 0) or with them (modes 1, 3, 4, under another A/B policy each) -
+// and the host-side weight split.
 #include <vector>
 
 #include "ut_kernels.h"
@@ -38,12 +39,12 @@ extern "C" int conv_diag2(const float* in, const float* w, const void* w_split, 
   (void)hipMemsetAsync(cnt, 0, 4, 0);
   c.tile_counter = cnt;
   if (!mode) c.w_split = nullptr;
-  c.no_resident = mode == 3 ? 15 : mode == 4 ? 14 : 0;      // 3: the chunked kernels only, 4: conv_c64k where applicable, no conv_w4      // 1: conv_c64k where applicable, 2: conv_c64r (lab), 3: the chunked kernel
+  // 1: the default policy, 2: conv_c64r (lab), 3: the chunked kernels only, 4: conv_c64k where applicable, no conv_w4
+  c.no_resident = mode == 3 ? ut::kResidentKinds[0] : mode == 4 ? ut::kResidentKinds[2] : ut::kResidentKinds[1];
   if (mode == 2 && ut::conv_c64r_applicable(c)) return (int)ut::launch_conv_c64r(c, 0);
 #ifdef C64_STAMPS
   if (!g_dbg) { (void)hipMalloc((void**)&g_dbg, 256 * 8 * 8); (void)hipMemset(g_dbg, 0, 256 * 8 * 8); }
   c.status = g_dbg;
 #endif
-  // mode 1: the split-fp16 kernel for the shape (conv_split.hip, or the split instantiation of the layer1 patch kernel)
-  return (int)(mode && ut::conv_split_applicable(c) ? ut::launch_conv_split(c, 0) : ut::launch_conv_igemm(c, 0));
+  return (int)ut::launch_conv(c, 0);
 }
