@@ -1000,7 +1000,9 @@ class HipEngine:
         stride-1 convolutions of layer2 .. layer4 and the stride-2 entries of layer3 / layer4; 0 / False the chunked conv_split
         kernels everywhere; 6 as 1 but the stride-2 entries through the chunked gather kernel; and, with those through the gather
         kernel as well: 3 conv_w4 on all stride-1 convolutions, 2 conv_c64k.hip on layer2 and chunked elsewhere, 4 conv_w4 on
-        layer3 / layer4 and conv_c64k on layer2, 5 conv_w4 on layer3 / layer4 and chunked on layer2."""
+        layer3 / layer4 and conv_c64k on layer2, 5 conv_w4 on layer3 / layer4 and chunked on layer2.  In every kind the
+        consecutive stride-1 convolutions that conv_w4 takes run as one launch per layer (a chain; calibrated scale mode, fusion
+        switch on); 7 as 1 with one launch per convolution."""
         self._check(self.lib.ut_set_resident_weights(self._h, int(kind)), "ut_set_resident_weights")
 
     def set_latency_mode(self, on: bool):

@@ -29,6 +29,8 @@
 // a k-step's instructions is pinned slot by slot (one MFMA per slot).
 // Same tensors, same weight planes and - per output element - the same products in the same order as
 // conv_split_kernel<256, 128, 4, 2, true>: bit-identical results (tests/test_gpu_parity.py::test_split_f16_four_wave_kernel_...).
+#include <type_traits>
+
 #include "ut_kernels.h"
 #include "ut_conv_dev.h"
 
@@ -62,11 +64,27 @@ constexpr int w4_cap(int pixels, int wi, int hi) { return ((pixels / (wi * hi)) 
 // is two loads and two conversions per k-step (18 per nine k-steps), every item converted four k-steps after its load, and the
 // buffers never change roles.  Per output element the same products as conv_split_kernel<256, 128, 4, 2, false>, summed plane
 // by plane instead of tap by tap: equal to fp32 rounding, not bit for bit.
-template <int WI, int HI, int SCH, int WPX, bool S2 = false>
-__global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles_n, int n_tiles) {
+//
+// CHAIN: the consecutive stride-1 convolutions of a layer (W4ChainLaunch: the shared shape in its ConvLaunch, one W4Layer per
+// convolution) in ONE launch.  A tile is whole maps, so a tile of convolution n + 1 reads the same tile of convolution n and nothing
+// else: a workgroup carries a UNIT - one row tile with its tiles_n column tiles - depth-first through all layers, with no grid
+// barrier, no flag and no wait on another workgroup.  An ITEM is one (unit, layer, column): what a tile is above, with its own
+// descriptors, weights, bias and scales.  A workgroup keeps TWO units in flight and alternates their items, so that the item
+// prefetched under the current item's last slices (patch, weights, fragments - the pipelining above, unchanged) was stored a whole
+// item ago; a unit that has finished its last layer is replaced from the ticket queue.  With ONE unit left (few crops, the last
+// round) the next layer's input does not exist while the current item runs: its in-stream patch requests take the out-of-range
+// offset (zeros, no memory access) and the item starts behind its producer's epilogue the way the prologue starts a tile.
+// Ordering: every wave waits for its stores (vmcnt(0): they have reached L2) in front of the barrier that ends the NEXT item's
+// first slice - or, one unit alone, in front of the restart's barrier -, and the first dependent load of the tile (the patch, two
+// layers on the residual) is issued behind that barrier, past L1 (sc1: every byte is read once per item).
+// n_tiles: the units; `steps` = layers x tiles_n items per unit.
+template <int WI, int HI, int SCH, int WPX, bool S2 = false, bool CHAIN = false>
+__global__ __launch_bounds__(256, 1) void conv_w4_kernel(typename std::conditional<CHAIN, W4ChainLaunch, ConvLaunch>::type p, int tiles_n, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int MI = W4_MI, PW = WI + 1, PH = HI + 1, HW = WI * HI;
   static_assert(!S2 || (SCH == 32 && WPX == 1), "phase planes: two 16-channel planes per buffer, four 32-channel blocks per tile");
+  static_assert(!(S2 && CHAIN), "chains: the stride-1 forms");
+  constexpr int LDAUX = CHAIN ? 16 : 0;        // sc1: the dependent loads of a chain miss L1
   constexpr int BM = W4_WPIX * WPX;            // pixels of a tile: whole maps
   constexpr int NCB = 4 / WPX, BN = 32 * NCB;  // 32-channel blocks / output channels of a tile
   constexpr int NG = SCH / 4, NHG = NG / 2;    // 16-byte groups of a patch row: NHG of first pieces, then NHG of remainders
@@ -78,7 +96,8 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
   constexpr int GSTRIDE = CAP * 16;            // bytes between two 16-byte groups of a row
   constexpr int STAGE = NG * GSTRIDE;          // one slice patch (12x12: 46 KB, 6x6: 52 KB, 24x24 in 16-channel slices: 43 KB)
   constexpr int SLOT = NBUF * STAGE;           // the next tile's index
-  constexpr int EPI = SLOT + 16;               // 4 KB per wave: a 32 x 32 block on its way from accumulator to row order (epilogue)
+  constexpr int KTAB = SLOT + 16;              // chains: the scale exponent of every layer's input (W4_MAX_CHAIN words)
+  constexpr int EPI = SLOT + (CHAIN ? 64 : 16);      // 4 KB per wave: a 32 x 32 block on its way from accumulator to row order (epilogue)
   static_assert(BM % HW == 0, "a tile is a whole number of maps: every tile has the same padded layout");
   static_assert(BM * NG == W4_NLOAD * 256 && KS % W4_NSET == 0 && (SCH == 32 || SCH == 16) && (WPX == 1 || WPX == 2), "shape");
   static_assert((NG - 2) * GSTRIDE + (2 * PW + 2) * 16 < 65536, "fragment reads: everything but the lane's base fits the immediate offset");
@@ -92,16 +111,16 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
 
   const int M = p.n_img * HW;
   // S2: 16-channel slices of nine k-steps.  Stride 1: the slices behind k_cin hold zeros on both sides and are not walked
-  const int n_slices = (!S2 && p.k_cin > 0 ? p.k_cin : p.cin) / (S2 ? 16 : SCH);
+  int n_slices = (!S2 && p.k_cin > 0 ? p.k_cin : p.cin) / (S2 ? 16 : SCH);      // (chains: of the current item)
   const int n_chunks = p.k_pad / 32;           // 9 per 32 input channels
 
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+  __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.in), 0, (int)((size_t)M * (S2 ? 4 : 1) * p.cin * sizeof(float)), 0x00020000);
-  const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+  __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(p.w_split), 0, (int)((size_t)(p.cout_pad / 32) * n_chunks * 4096), 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+  __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.res ? p.res : p.bias), 0, p.res ? (int)((size_t)M * p.cout_store * sizeof(float)) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t o_rsrc =
+  __amdgpu_buffer_rsrc_t o_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)((size_t)M * p.cout_store * sizeof(float)), 0x00020000);
   const __amdgpu_buffer_rsrc_t q_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.tile_counter, 0, 4, 0x00020000);
 
@@ -111,8 +130,15 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
     split_act_scale(p.in_max, p.in_obs, p.split_adaptive, x_scale, x_unscale, ok, adapted);
     split_scale_report(ok, adapted, p.status, p.adapt_count);
   }
-  const float tot_unscale = p.split_unscale * x_unscale;
-  const float floor_v = p.relu ? 0.f : -__builtin_huge_valf();
+  float tot_unscale = p.split_unscale * x_unscale;
+  float floor_v = p.relu ? 0.f : -__builtin_huge_valf();
+  const float* bias_c = p.bias;                // (chains: bias, output word and guard of the current item, scale of the next one)
+  unsigned* out_max_c = p.out_max;
+  int guard_k = 0;
+  bool guarded = false;
+  float xs_n = x_scale;
+  __amdgpu_buffer_rsrc_t a_rsrc_n = a_rsrc, w_rsrc_n = w_rsrc;
+  int n_slices_n = n_slices;
   const unsigned row_b = (unsigned)p.cout_store * 4u;
 
   const int grid = gridDim.x;
@@ -140,6 +166,7 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
   // per-lane byte offset of pixel t / NG of a tile (pixels behind the tensor are behind the descriptor's range: they load zeros);
   // + j h_step per load, + the slice's channel offset as the scalar offset
 #define W4_H_BASE(TILE) ((unsigned)((((TILE) / tiles_n) * BM + tid / NG) * p.cin + 4 * (tid % NG)) * 4u)
+#define W4_H_BASE_U(UNIT) ((unsigned)(((UNIT) * BM + tid / NG) * p.cin + 4 * (tid % NG)) * 4u)      /* chains: of a unit's row tile */
   // S2: the thread's group t % 8 is plane (t % 8) >> 2, channels 4 (t & 3) .. + 3 of the slice's sixteen; h_in[j]: the input pixel
   // (2Y, 2X) of its output pixel 32 j + t / 8 inside the tile's maps, po_a / po_b: its plane's pixel in buffer 0 / buffer 1
   unsigned h_in[S2 ? W4_NLOAD : 1], po_a = 0, po_b = 0, pb1[S2 ? MI : 1];
@@ -169,11 +196,12 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
 #define W4_READ_X(I, PC, S, TAP, BASE)                                                               \
   xp[I][PC] = *reinterpret_cast<const u32x4*>(smem + (BASE)[I] + (unsigned)(((PC) * NHG + (SCH == 32 ? 2 * (S) : 0)) * GSTRIDE + (((TAP) / 3) * PW + (TAP) % 3) * 16));
   // weight fragment of plane PL of chunk CH, k-step half S, of the wave's block of the tile column at byte offset WROW
-#define W4_LOAD_W(SET, PL, CH, S, WROW)                                                              \
+#define W4_LOAD_W_OF(RS, SET, PL, CH, S, WROW)                                                       \
   {                                                                                                  \
     const unsigned so_ = (WROW) + (unsigned)((wco * n_chunks + (CH)) * 4096 + ((S) * 2 + (PL)) * 1024); \
-    wf[SET][PL] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane, so_, 0)); \
+    wf[SET][PL] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(RS, w_lane, so_, 0)); \
   }
+#define W4_LOAD_W(SET, PL, CH, S, WROW) W4_LOAD_W_OF(w_rsrc, SET, PL, CH, S, WROW)
   // k-step Q of slice SL: its tap, its chunk of the weight planes and its half of the chunk
   // S2, k-step Q = 0 .. 8 of a 16-channel slice: its plane inside its buffer (buffer 1 from k-step 5 on), its shift in padded
   // coordinates ((dY + 1) * 3 + dX + 1) and the tap of the 3x3 whose weights it takes
@@ -208,6 +236,27 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
   int cur_buf = 0;                // patch buffer of the slice being computed
   unsigned out_bits = 0;
   const unsigned slot_addr = (unsigned)(unsigned long)(lds_char*)smem + (unsigned)SLOT;
+  // chains: the two units in flight - the current item's (u_c, step s_c = layer x tiles_n + column) and the other unit's next item
+  // (u_o < 0: none) -, the item that follows the current one (nx_u < 0: none; dep: it reads what the current one stores) and the
+  // scale exponents of the current and the next item's input
+  const int tn_sh = tiles_n == 2 ? 1 : 0, tn_mask = tiles_n - 1;
+  int u_c = slot, s_c = 0, u_o = -1, s_o = 0, nx_u = -1, nx_s = 0, adv_u = -1, adv_s = 0, k_c = 0, k_n = 0;
+  bool dep = false;
+  int steps = 0;
+  if constexpr (CHAIN) {
+    steps = p.n_layers << tn_sh;
+    u_o = grid + slot < n_tiles ? grid + slot : -1;
+    // (thread l: layer l's exponent from its calibrated word - split_act_scale's, without a producer's word; the first layer's
+    // guard is the launch's, above, the others' the producing item's, below.  A calibrated word that holds no finite value is
+    // reported as every launch of the layer would)
+    if (tid < p.n_layers) {
+      const unsigned bits = *p.lay[tid].in_max;
+      const int e = (int)(bits >> 23);
+      float sc_, un_;
+      *reinterpret_cast<int*>(smem + KTAB + 4 * tid) = split_pow2_for(e, bits == 0u || e == 255, sc_, un_);
+      if (tid > 0 && e == 255 && blockIdx.x == 0 && p.status) atomicOr(p.status, UT_SPLIT_RANGE);
+    }
+  }
 
   // ---- prologue (exposed once per workgroup): the patch buffers zeroed (their zero rows stay zero for the life of the workgroup),
   // the patches of the first tile's first AHEAD slices (of the last of them, with three buffers: only what the steady state would
@@ -215,15 +264,16 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
   // k-steps and the pixel fragments of the first
   for (int k = tid; k < NBUF * STAGE / 16; k += 256) *reinterpret_cast<u32x4*>(smem + k * 16) = u32x4{0, 0, 0, 0};
   __syncthreads();
-  unsigned h_base = S2 ? 0u : W4_H_BASE(tile);
-  unsigned w_row = (unsigned)((tile % tiles_n) * NCB) * (unsigned)n_chunks * 4096u;     // byte offset of the tile column's planes
+  unsigned h_base = S2 ? 0u : CHAIN ? W4_H_BASE_U(slot) : W4_H_BASE(tile);
+  unsigned w_row = CHAIN ? 0u : (unsigned)((tile % tiles_n) * NCB) * (unsigned)n_chunks * 4096u;     // byte offset of the tile column's planes
   unsigned w_row_next = w_row;
+  if constexpr (CHAIN) k_c = k_n = slot_read(slot_addr + (unsigned)(KTAB - SLOT));
   if constexpr (!S2) {
 #pragma unroll
     for (int a = 0; a < AHEAD; ++a)
 #pragma unroll
       for (int j = 0; j < W4_NLOAD; ++j) {
-        const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, h_base + (unsigned)j * h_step, (unsigned)(a * SCH * 4), 0));
+        const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, h_base + (unsigned)j * h_step, (unsigned)(a * SCH * 4), LDAUX));
         if (a == AHEAD - 1 && KS == 9 && j >= W4_NLOAD - 4) stg[j % W4_NSTG] = v;
         else W4_SPLIT_STORE(v, (unsigned)(a * STAGE) + h_wa[j])
       }
@@ -269,26 +319,26 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
           if ((N) >= 19 && (N) <= 26 && q1 < KS) { W4_READ_X(((N) + 8) % 9, 0, W4_HALF(sl, q1), W4_TAP(q1), rb) } \
           if ((N) >= 19 && (N) <= 26 && q1 == KS) { W4_READ_X(((N) + 8) % 9, 0, 0, 0, nb) }          \
           if (((N) == 10 || (N) == 11) && qd < KS) { W4_LOAD_W(qd % W4_NSET, (N) & 1, W4_CHUNK(sl, qd), W4_HALF(sl, qd), w_row) } \
-          if (((N) == 10 || (N) == 11) && qd >= KS) { W4_LOAD_W(qd % W4_NSET, (N) & 1, W4_CHUNK(sl_after, qd - KS), W4_HALF(sl_after, qd - KS), row_after) } \
-          if ((N) == 12 && q >= 4 && q < 4 + W4_NLOAD) { const float4 v_ = stg[(q + W4_NSTG - 4) % W4_NSTG]; split_pair_scaled(v_.x, v_.y, x_scale, cv0, cv1); } \
+          if (((N) == 10 || (N) == 11) && qd >= KS) { W4_LOAD_W_OF(wr_after, qd % W4_NSET, (N) & 1, W4_CHUNK(sl_after, qd - KS), W4_HALF(sl_after, qd - KS), row_after) } \
+          if ((N) == 12 && q >= 4 && q < 4 + W4_NLOAD) { const float4 v_ = stg[(q + W4_NSTG - 4) % W4_NSTG]; split_pair_scaled(v_.x, v_.y, xs_f, cv0, cv1); } \
           if ((N) == 13 && q >= 4 && q < 4 + W4_NLOAD) {                                             \
             const float4 v_ = stg[(q + W4_NSTG - 4) % W4_NSTG];                                      \
             unsigned a1_, b1_;                                                                       \
-            split_pair_scaled(v_.z, v_.w, x_scale, a1_, b1_);                                        \
+            split_pair_scaled(v_.z, v_.w, xs_f, a1_, b1_);                                           \
             *reinterpret_cast<u32x2*>(smem + wbuf + h_wa[(q + 5) % 9]) = u32x2{cv0, a1_};            \
             *reinterpret_cast<u32x2*>(smem + wbuf + h_wa[(q + 5) % 9] + NHG * GSTRIDE) = u32x2{cv1, b1_}; \
           }                                                                                          \
-          if (KS == 9 && (N) == 12 && q < 4) { const float4 v_ = stg[q % W4_NSTG]; split_pair_scaled(v_.x, v_.y, x_scale, cv0, cv1); } \
+          if (KS == 9 && (N) == 12 && q < 4) { const float4 v_ = stg[q % W4_NSTG]; split_pair_scaled(v_.x, v_.y, xs_p, cv0, cv1); } \
           if (KS == 9 && (N) == 13 && q < 4) {      /* values 5 .. 8 of the patch the slice before began: the buffer before wbuf */ \
             const float4 v_ = stg[q % W4_NSTG];                                                      \
             unsigned a1_, b1_;                                                                       \
-            split_pair_scaled(v_.z, v_.w, x_scale, a1_, b1_);                                        \
+            split_pair_scaled(v_.z, v_.w, xs_p, a1_, b1_);                                           \
             *reinterpret_cast<u32x2*>(smem + pbuf + h_wa[q + 5]) = u32x2{cv0, a1_};                  \
             *reinterpret_cast<u32x2*>(smem + pbuf + h_wa[q + 5] + NHG * GSTRIDE) = u32x2{cv1, b1_};  \
           }                                                                                          \
           if ((N) == 14 && q < W4_NLOAD)                                                             \
-            stg[q % W4_NSTG] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, h_base + (unsigned)q * h_step, f_soff, 0)); \
-          if ((N) == 16 && q == KS / 2 && sl == 0 && tid == 0) *reinterpret_cast<int*>(smem + SLOT) = grid + ticket; \
+            stg[q % W4_NSTG] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(f_rsrc, h_base + (unsigned)q * h_step, f_soff, LDAUX)); \
+          if ((N) == 16 && q == KS / 2 && sl == 0 && tid == 0) *reinterpret_cast<int*>(smem + SLOT) = (CHAIN ? 2 * grid : grid) + ticket; \
           W4_PIN();                                                                                  \
           W4_MFMA(ws, N);                                                                            \
           W4_PIN();                                                                                  \
@@ -303,10 +353,15 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
           /* every wave has written its part of the next slice's patch and has read its last fragments of this one: ONE barrier \
              per slice, in front of the first reads of the next patch */                             \
           W4_READ_X(MI - 1, 0, W4_HALF(sl, KS - 1), 8, rb)                                           \
+          /* chains: the stores of the item before this one have reached L2 in front of this barrier - the next item's patch is \
+             requested behind it */                                                                  \
+          if (CHAIN && sl == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     \
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                         \
           __builtin_amdgcn_s_barrier();                                                              \
           asm volatile("" ::: "memory");                                                             \
-          if (sl == 0) {                                                                             \
+          if constexpr (CHAIN) {                                                                     \
+            if (sl == 0) { W4_CHAIN_NEXT() }                                                         \
+          } else if (sl == 0) {                                                                      \
             next_tile = slot_read(slot_addr);                                                        \
             w_row_next = (unsigned)((next_tile % tiles_n) * NCB) * (unsigned)n_chunks * 4096u;       \
           }                                                                                          \
@@ -391,18 +446,63 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
         W4S_SLOT_BODY(18) W4S_SLOT_BODY(19) W4S_SLOT_BODY(20) W4S_SLOT_BODY(21) W4S_SLOT_BODY(22) W4S_SLOT_BODY(23) W4S_SLOT_BODY(24) W4S_SLOT_BODY(25) W4S_SLOT_BODY(26) \
       }
 
+  // chains, behind the barrier of an item's first slice (lgkmcnt(0) has just been waited for): the item that follows - the other
+  // unit's, or with one unit this unit's next step, or a new unit's first (the ticket) -, its layer's record for what is prefetched
+  // (input and weight descriptors, scale, slices), and the current layer's record for the epilogue
+#define W4_CHAIN_NEXT()                                                                              \
+  {                                                                                                  \
+    const int l_c = s_c >> tn_sh;                                                                    \
+    const bool fresh = s_c + 1 == steps, two = u_o >= 0;                                             \
+    adv_s = fresh ? 0 : s_c + 1;                                                                     \
+    nx_s = two ? s_o : adv_s;                                                                        \
+    const int l_n = nx_s >> tn_sh, l_g = l_c + 1 < p.n_layers ? l_c + 1 : l_c;                       \
+    int tk_, kn_, kg_;                                                                               \
+    asm volatile("ds_read_b32 %0, %3\n\tds_read_b32 %1, %4\n\tds_read_b32 %2, %5\n\ts_waitcnt lgkmcnt(0)" \
+                 : "=&v"(tk_), "=&v"(kn_), "=&v"(kg_)                                                \
+                 : "v"(slot_addr), "v"(slot_addr + (unsigned)(KTAB - SLOT + 4 * l_n)), "v"(slot_addr + (unsigned)(KTAB - SLOT + 4 * l_g)) : "memory"); \
+    const int tk = __builtin_amdgcn_readfirstlane(tk_);                                              \
+    adv_u = fresh ? ((unsigned)tk < (unsigned)n_tiles ? tk : -1) : u_c;                              \
+    nx_u = two ? u_o : adv_u;                                                                        \
+    dep = !two && !fresh && (adv_s & tn_mask) == 0;                                                  \
+    guarded = l_c + 1 < p.n_layers;                                                                  \
+    guard_k = __builtin_amdgcn_readfirstlane(kg_);                                                   \
+    const unsigned o_bytes = (unsigned)M * (unsigned)p.cout_store * 4u;                              \
+    {                                                                                                \
+      const W4Layer& lc = p.lay[l_c];                                                                \
+      r_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lc.res ? lc.res : lc.bias), 0, lc.res ? (int)o_bytes : 0, 0x00020000); \
+      o_rsrc = __builtin_amdgcn_make_buffer_rsrc(lc.out, 0, (int)o_bytes, 0x00020000);               \
+      bias_c = lc.bias;                                                                              \
+      out_max_c = lc.out_max;                                                                        \
+      tot_unscale = lc.split_unscale * __uint_as_float((unsigned)(127 - k_c) << 23);                 \
+      floor_v = lc.relu ? 0.f : -__builtin_huge_valf();                                              \
+      bb4 = *reinterpret_cast<const float4*>(bias_c + (s_c & tn_mask) * BN + wco * 32 + 4 * (lane & 7)); \
+    }                                                                                                \
+    if (nx_u >= 0) {                                                                                 \
+      const W4Layer& ln = p.lay[l_n];                                                                \
+      a_rsrc_n = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ln.in), 0, (int)((unsigned)M * (unsigned)p.cin * 4u), 0x00020000); \
+      w_rsrc_n = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ln.w_split), 0, (int)((size_t)(p.cout_pad / 32) * n_chunks * 4096), 0x00020000); \
+      k_n = __builtin_amdgcn_readfirstlane(kn_);                                                     \
+      xs_n = __uint_as_float((unsigned)(127 + k_n) << 23);                                           \
+      n_slices_n = (ln.k_cin > 0 ? ln.k_cin : p.cin) / SCH;                                          \
+      w_row_next = (unsigned)((nx_s & tn_mask) * NCB) * (unsigned)n_chunks * 4096u;                  \
+    }                                                                                                \
+  }
+
   for (;;) {
     // the tile after this one: the ticket is taken here, written to LDS by thread 0 in the middle of the tile's first slice and
     // read by everyone behind that slice's barrier (a tile has at least AHEAD + 1 slices)
+    // (chains: a unit's last item takes the ticket of the unit that replaces it)
     int ticket = 0;
-    if (tid == 0) ticket = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, q_rsrc, 0, 0, 0);
+    if (tid == 0 && (!CHAIN || s_c + 1 == steps)) ticket = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, q_rsrc, 0, 0, 0);
+    if constexpr (CHAIN) out_bits = 0;      // (of the item: every layer has its own word)
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
 
     // (the tile's bias, for the epilogue: requested here, long before it is needed)
-    const float4 bb4 = *reinterpret_cast<const float4*>(p.bias + (tile % tiles_n) * BN + wco * 32 + 4 * (lane & 7));
+    float4 bb4 = float4{0.f, 0.f, 0.f, 0.f};      // (chains: with the layer's record, behind the first slice)
+    if constexpr (!CHAIN) bb4 = *reinterpret_cast<const float4*>(p.bias + (tile % tiles_n) * BN + wco * 32 + 4 * (lane & 7));
     if constexpr (S2) {
       for (int sl = 0; sl < n_slices; ++sl) {
         const bool last_slice = sl == n_slices - 1;
@@ -426,11 +526,18 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
       asm volatile("" : "+s"(rbuf), "+s"(nbuf), "+s"(wbuf), "+s"(pbuf));      // (opaque per slice: nothing derived from them is carried across slices)
       // the patch begun during this slice: slice + AHEAD of this tile, or of the next
       const int f_sl = sl + AHEAD < n_slices ? sl + AHEAD : sl + AHEAD - n_slices;
-      if (sl + AHEAD == n_slices) h_base = W4_H_BASE(next_tile);
+      if constexpr (CHAIN) {      // (a next item whose input this item stores, or none: zeros without a memory access)
+        if (sl + AHEAD == n_slices) h_base = nx_u >= 0 && !dep ? W4_H_BASE_U(nx_u) : W4_HOOB;
+      } else if (sl + AHEAD == n_slices) h_base = W4_H_BASE(next_tile);
       const unsigned f_soff = (unsigned)f_sl * (SCH * 4);
       // the weight fragments of the k-steps behind this slice: the next slice's, or the next tile's first
       const int sl_after = last_slice ? 0 : sl + 1;
       const unsigned row_after = last_slice ? w_row_next : w_row;
+      // whose patch this slice begins (xs_f, f_rsrc) and - 9-step slices - finishes (xs_p), whose weights follow it: the same
+      // item's everywhere but in a chain, where the next item has its own tensor, scale and planes
+      const bool f_next = CHAIN && sl + AHEAD >= n_slices, p_next = CHAIN && sl > 0 && sl - 1 + AHEAD >= n_slices;
+      const float xs_f = f_next ? xs_n : x_scale, xs_p = p_next ? xs_n : x_scale;
+      const __amdgpu_buffer_rsrc_t f_rsrc = f_next ? a_rsrc_n : a_rsrc, wr_after = CHAIN && last_slice ? w_rsrc_n : w_rsrc;
       unsigned rb[MI], nb[MI];
 #pragma unroll
       for (int i = 0; i < MI; ++i) { rb[i] = pb[i] + rbuf; nb[i] = pb[i] + nbuf; }
@@ -444,10 +551,10 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
     // residual requests of a wave go out before the first value is needed: one memory latency per tile, not one per block.  The
     // scalar offset is not part of the descriptor's range check: the tile that reaches beyond the tensor takes per-access offsets.
     {
-      const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
+      const int tm = CHAIN ? u_c : tile / tiles_n, tn = CHAIN ? s_c & tn_mask : tile - tm * tiles_n;
       const bool ragged = tm * BM + BM > M;
       const int ch = tn * BN + wco * 32 + fr;
-      const float bb = p.bias[ch];
+      const float bb = bias_c[ch];
       const unsigned base = ch < p.cout_store ? (unsigned)((tm * BM + wm * W4_WPIX + 4 * fh) * p.cout_store + ch) * 4u : W4_HOOB;
       const unsigned keep_n = base != W4_HOOB ? 0x7FFFFFFFu : 0u;
       if (!ragged) {
@@ -472,7 +579,7 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
           for (int i = 0; i < 5; ++i)
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-              rr[i][t] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, base4, (unsigned)(32 * i + 8 * t) * row_bs, 0));
+              rr[i][t] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, base4, (unsigned)(32 * i + 8 * t) * row_bs, LDAUX));
         }
         // half a block (16 pixels x 32 channels, 2 KB) at a time, two regions in turn: the writes of one half go out while the reads
         // of the half before are on their way back
@@ -487,7 +594,7 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
           if (!S2 && (h & 1) == 0 && i + 5 < MI) {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-              rr[(i + 5) % 6][t] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, base4, (unsigned)(32 * (i + 5) + 8 * t) * row_bs, 0));
+              rr[(i + 5) % 6][t] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, base4, (unsigned)(32 * (i + 5) + 8 * t) * row_bs, LDAUX));
           }
           if (h + 1 < 2 * MI) { W4_EX_WRITE(h + 1) }
 #pragma unroll
@@ -514,7 +621,7 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
           unsigned off = base + (unsigned)(i * 32) * row_b;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            r1[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, off, 0, 0));
+            r1[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, off, 0, LDAUX));
             off += ((r & 3) == 3 ? 5u : 1u) * row_b;
           }
           off = base + (unsigned)(i * 32) * row_b;
@@ -529,12 +636,69 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(ConvLaunch p, int tiles
         }
       }
     }
-    if ((unsigned)next_tile >= (unsigned)n_tiles) break;
-    tile = next_tile;
-    w_row = w_row_next;
+    if constexpr (CHAIN) {
+      // the item's word, and the guard of the layer that reads it: the tensor's largest magnitude is beyond the calibrated range
+      // exactly when some item's is (split_act_scale's test, on the wave's share)
+      {
+        unsigned wb = out_bits;
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+          const unsigned other = (unsigned)__shfl_xor((int)wb, o);
+          wb = other > wb ? other : wb;
+        }
+        if (lane == 0) {
+          if (out_max_c && wb > __hip_atomic_load(out_max_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out_max_c, wb);
+          const int eo = (int)(wb >> 23);
+          if (guarded && (eo == 255 || eo + guard_k > 142) && p.status) atomicOr(p.status, UT_SPLIT_RANGE);
+        }
+      }
+      if (nx_u < 0) break;
+      // the next item becomes the current one; the other unit's next item is this unit's next step (or its replacement, or none)
+      const bool two = u_o >= 0;
+      u_c = nx_u; s_c = nx_s;
+      if (two) { u_o = adv_u; s_o = adv_s; }
+      a_rsrc = a_rsrc_n; w_rsrc = w_rsrc_n; x_scale = xs_n; k_c = k_n; n_slices = n_slices_n;
+      w_row = w_row_next;
+      if (dep) {
+        // one unit alone: its input has just been stored.  The stores are waited for, then the item starts the way the prologue
+        // starts a tile (the zero rows of the buffers are untouched; the weights came in the stream)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        h_base = W4_H_BASE_U(u_c);
+        int bo = cur_buf;
+#pragma unroll
+        for (int a = 0; a < AHEAD; ++a) {
+          const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane(bo * STAGE);
+#pragma unroll
+          for (int j = 0; j < W4_NLOAD; ++j) {
+            const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, h_base + (unsigned)j * h_step, (unsigned)(a * SCH * 4), LDAUX));
+            if (a == AHEAD - 1 && KS == 9 && j >= W4_NLOAD - 4) stg[j % W4_NSTG] = v;
+            else W4_SPLIT_STORE(v, dst + h_wa[j])
+          }
+          bo = bo + 1 == NBUF ? 0 : bo + 1;
+        }
+        __syncthreads();
+        const unsigned rb0 = (unsigned)__builtin_amdgcn_readfirstlane(cur_buf * STAGE);
+        unsigned rb[MI];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) rb[i] = pb[i] + rb0;
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          W4_READ_X(i, 1, 0, 0, rb)
+          if (i < MI - 1) { W4_READ_X(i, 0, 0, 0, rb) }
+        }
+      }
+    } else {
+      if ((unsigned)next_tile >= (unsigned)n_tiles) break;
+      tile = next_tile;
+      w_row = w_row_next;
+    }
   }
-  if (p.out_max) publish_abs_max(p.out_max, out_bits);
+  if constexpr (!CHAIN) { if (p.out_max) publish_abs_max(p.out_max, out_bits); }
 #undef W4_H_BASE
+#undef W4_H_BASE_U
+#undef W4_LOAD_W_OF
+#undef W4_CHAIN_NEXT
 #undef W4_READ_X
 #undef W4_LOAD_W
 #undef W4_TAP
@@ -570,6 +734,16 @@ hipError_t launch_w4_cfg(const ConvLaunch& c, hipStream_t s) {
   return launch_with_lds<&conv_w4_kernel<WI, HI, SCH, WPX, S2>>(c.device, lds, persistent_grid(c.num_cu, n_tiles), 256, s, c, tiles_n, n_tiles);
 }
 
+// a chain: one unit per row tile, `steps` = layers x column tiles items each; as many workgroups as stay resident, never more than units
+template <int WI, int HI, int SCH, int WPX>
+hipError_t launch_w4_chain_cfg(const W4ChainLaunch& c, hipStream_t s) {
+  constexpr int BM = W4_WPIX * WPX, BN = 128 / WPX;
+  const long M = (long)c.n_img * c.Ho * c.Wo;
+  const int units = (int)((M + BM - 1) / BM), tiles_n = c.cout_store / BN;
+  constexpr int lds = (SCH == 32 ? 2 : 3) * (SCH / 4) * w4_cap(BM, WI, HI) * 16 + 64 + 4 * 4096;
+  return launch_with_lds<&conv_w4_kernel<WI, HI, SCH, WPX, false, true>>(c.device, lds, persistent_grid(c.num_cu, units), 256, s, c, tiles_n, units);
+}
+
 }  // namespace
 
 // (the map sizes are template parameters - taps and padded rows are immediates of the fragment reads: the backbone's 12x12 and 6x6 maps
@@ -596,6 +770,43 @@ hipError_t launch_conv_w4(const ConvLaunch& c, hipStream_t s) {
   if (form == W4_STRIDE2) return c.Wo == 12 ? launch_w4_cfg<12, 12, 32, 1, true>(c, s) : launch_w4_cfg<6, 6, 32, 1, true>(c, s);
   if (form == W4_MAP24) return launch_w4_cfg<24, 24, 16, 2>(c, s);
   return c.W == 12 ? launch_w4_cfg<12, 12, 32, 1>(c, s) : launch_w4_cfg<6, 6, 32, 1>(c, s);
+}
+
+
+// b may follow a in a chain: both in a stride-1 form, the same shape, b reads what a writes under a calibrated scale that no launch
+// adapts, guarded by a's word.  (cout_store / 128 <= 2 column tiles: a unit's step index splits into layer and column by a shift.)
+bool conv_w4_chainable(const ConvLaunch& a, const ConvLaunch& b) {
+  const W4Form fa = conv_w4_form(a), fb = conv_w4_form(b);
+  if (fa != fb || (fa != W4_TILES128 && fa != W4_MAP24)) return false;
+  if (a.cout_store > 256 || a.cin != a.cout_store) return false;
+  return b.in == a.out && b.in_obs == a.out_max && a.out_max && b.in_max && a.in_max && !a.split_adaptive && !b.split_adaptive &&
+         a.n_img == b.n_img && a.H == b.H && a.W == b.W && a.cin == b.cin && a.cout_store == b.cout_store && a.cout_pad == b.cout_pad &&
+         a.k_pad == b.k_pad && a.status == b.status && a.device == b.device && a.num_cu == b.num_cu;
+}
+
+// A chain keeps the column tiles of a unit on ONE workgroup (layer n + 1 reads all channels of layer n).  Where a tile has all the
+// output channels that costs nothing; layer4's two column tiles run side by side in a launch of their own, so a chain of fewer
+// units than CUs would leave CUs idle that the per-layer launches fill (512 crops at 6x6: 64 units against 128 tiles).
+bool conv_w4_chain_fills(const ConvLaunch& c) {
+  const long units = ((long)c.n_img * c.Ho * c.Wo + W4_WPIX - 1) / W4_WPIX;      // (the two-column form has 288-pixel tiles)
+  return c.cout_store <= 128 || units >= (long)c.num_cu;
+}
+
+hipError_t launch_conv_w4_chain(const ConvLaunch* layers, int n_layers, hipStream_t s) {
+  if (n_layers < 1 || n_layers > W4_MAX_CHAIN) return hipErrorInvalidValue;
+  for (int l = 1; l < n_layers; ++l)
+    if (!conv_w4_chainable(layers[l - 1], layers[l])) return hipErrorInvalidValue;
+  const W4Form form = conv_w4_form(layers[0]);
+  if ((form != W4_TILES128 && form != W4_MAP24) || !layers[0].in_max || !layers[0].out_max) return hipErrorInvalidValue;
+  W4ChainLaunch c{};
+  static_cast<ConvLaunch&>(c) = layers[0];
+  c.n_layers = n_layers;
+  for (int l = 0; l < n_layers; ++l) {
+    const ConvLaunch& a = layers[l];
+    c.lay[l] = W4Layer{a.in, a.res, a.out, a.w_split, a.bias, a.in_max, a.out_max, a.split_unscale, a.k_cin, a.relu};
+  }
+  if (form == W4_MAP24) return launch_w4_chain_cfg<24, 24, 16, 2>(c, s);
+  return c.W == 12 ? launch_w4_chain_cfg<12, 12, 32, 1>(c, s) : launch_w4_chain_cfg<6, 6, 32, 1>(c, s);
 }
 
 }  // namespace ut

@@ -52,6 +52,7 @@ struct Regressor {
 };
 
 struct ProfEvent { hipEvent_t a, b; double flops;   int kind = 0;   // 0: fp32 matrix-instruction kernels, 1: split-fp16 kernels
+  int convs = 1;      // convolutions the bracket counts for: the layers of a conv_w4 chain (one launch, one pair of events)
 };
 
 }  // namespace
@@ -108,7 +109,12 @@ struct ut_context {
   unsigned word_gen = 0;            // bumped by every zeroing of the words: a max word kept across launches is stale after it
   bool block_fusion = true;         // ut_set_block_fusion: split-fp16 mode - layer1's BasicBlocks and layer2's entry as one launch each, the
                                     // regressor's zero K slice skipped; both arithmetics - the fp32 1x1 convolutions on conv_pw.hip (run_pw)
-  int resident_weights = 1;         // split-fp16 mode (ut_set_resident_weights): 1 conv_w4 wherever it applies, 0 the chunked kernels, 2 .. 6 A/B mixes
+  int resident_weights = 1;         // split-fp16 mode (ut_set_resident_weights): 1 conv_w4 wherever it applies, 0 the chunked kernels, 2 .. 7 A/B mixes
+  // conv_w4 chains (run_conv, flush_chain): consecutive launches of conv_w4's stride-1 forms, each reading what the one before
+  // wrote, wait here and go out as one launch in front of the next other launch on their stream
+  std::vector<ut::ConvLaunch> chain;
+  double chain_flops = 0;
+  hipStream_t chain_stream = nullptr;
   bool call_split = false;          // the running backbone call uses the split-fp16 kernels (decided once per call)
   // index checks: device status words ([0] sticky errors, [1] per call), their pinned host mirror, the duplicate-slot
   // scratch (slots_cap ints, allocated with the temporal state) and the mode (UT_CHECK_*)
@@ -356,8 +362,11 @@ static_assert(kScaleTensors < 63, "the adaptation counter is the last of the 64 
 constexpr int kCalibHeadroom = 4;      // calibrated scale words hold 2^4 x the calibration maximum: inputs up to 32 x that maximum
                                        // (the scale leaves another factor 2 under fp16's 65504) are inside the split's range
 
+int flush_chain(ut_handle h);
+
 // zero the per-launch words (tile queues, output maxima) used by the launches of one API call (stream ordered)
 int begin_call(ut_handle h, hipStream_t s) {
+  if (const int rc = flush_chain(h)) return rc;      // (a zeroing in mid-call: the collected launches own words)
   h->counter_next = 0;
   ++h->word_gen;
   HIPCHK(h, ut::launch_zero_words(h->counters, 2 * kMaxCounters, s));      // a kernel, not a memset node: see launch_zero_words
@@ -397,9 +406,10 @@ void set_scale(Launch& l, const ScaleRef& sr, int* status) {
 // and kind (ProfEvent).  (A calibration pass never profiles: calibrate_split turns profiling off.)
 template <class Launch>
 int bracket_launch(ut_handle h, hipStream_t s, int in_tid, const unsigned* in_max, double flops, int kind, const char* what,
-                   Launch launch) {
+                   Launch launch, int convs = 1) {
+  if (const int rc = flush_chain(h)) return rc;      // in stream order: what was collected goes first
   if (h->calibrating && in_max && in_tid >= 0 && in_tid < kScaleTensors) HIPCHK(h, ut::launch_merge_max(h->calib + in_tid, in_max, s));
-  ProfEvent pe{nullptr, nullptr, flops, kind};
+  ProfEvent pe{nullptr, nullptr, flops, kind, convs};
   if (h->profiling) {
     HIPCHK(h, hipEventCreateWithFlags(&pe.a, hipEventDisableSystemFence));   // timing only: no system-scope flush per kernel
     HIPCHK(h, hipEventCreateWithFlags(&pe.b, hipEventDisableSystemFence));
@@ -412,6 +422,22 @@ int bracket_launch(ut_handle h, hipStream_t s, int in_tid, const unsigned* in_ma
     h->prof.push_back(pe);
   }
   return UT_OK;
+}
+
+// The collected conv_w4 launches (run_conv) as one launch - a single one as itself -, bracketed as ONE launch of kind 1 with the
+// layers' summed flops.  Called in front of every other launch that could follow them on their stream, and where a pass or the
+// head ends.
+int flush_chain(ut_handle h) {
+  if (h->chain.empty()) return UT_OK;
+  std::vector<ut::ConvLaunch> layers;
+  layers.swap(h->chain);
+  const double flops = h->chain_flops;
+  h->chain_flops = 0;
+  hipStream_t s = h->chain_stream;
+  if (layers.size() == 1)
+    return bracket_launch(h, s, -1, nullptr, flops, 1, "conv_w4", [&] { return ut::launch_conv_w4(layers[0], s); });
+  return bracket_launch(h, s, -1, nullptr, flops, 1, "conv_w4 chain",
+                        [&] { return ut::launch_conv_w4_chain(layers.data(), (int)layers.size(), s); }, (int)layers.size());
 }
 
 // in_max: the max word of the launch that produced `in` (null: unknown); in_tid: the tensor id of `in` (< 0: not a tensor of the
@@ -471,7 +497,21 @@ int run_conv(ut_handle h, const ConvW& cw, const float* in, const float* res, fl
     c.out_max = h->counters + kMaxCounters + word;
     if (out_max) *out_max = c.out_max;
   }
-  return bracket_launch(h, s, kind ? in_tid : -1, in_max, cw.flops_per_pixel * (double)n_img * c.Ho * c.Wo, kind,
+  const double flops = cw.flops_per_pixel * (double)n_img * c.Ho * c.Wo;
+  // conv_w4's stride-1 forms under a calibrated scale that no launch adapts: collected, and issued with the launches that follow
+  // it as one chain (flush_chain).  Everything else - and kind 7 of ut_set_resident_weights - launches now, behind what was collected.
+  const ut::W4Form form = kernel == ut::CONV_W4 ? ut::conv_w4_form(c) : ut::W4_NONE;
+  if (kind && (form == ut::W4_TILES128 || form == ut::W4_MAP24) && !(c.no_resident & ut::NO_W4_CHAIN) && h->block_fusion &&
+      !h->calibrating && !h->latency_mode && h->scale_mode == UT_SPLIT_SCALE_CALIBRATED && c.in_max && !c.split_adaptive &&
+      ut::conv_w4_chain_fills(c)) {
+    if (!h->chain.empty() && (h->chain_stream != s || (int)h->chain.size() == ut::W4_MAX_CHAIN || !ut::conv_w4_chainable(h->chain.back(), c)))
+      if ((rc = flush_chain(h))) return rc;
+    h->chain.push_back(c);
+    h->chain_flops += flops;
+    h->chain_stream = s;
+    return UT_OK;
+  }
+  return bracket_launch(h, s, kind ? in_tid : -1, in_max, flops, kind,
                         ut::kConvKernelName[kernel], [&] { return ut::launch_conv_on(kernel, c, s); });
 }
 
@@ -570,6 +610,7 @@ void prof_clear(ut_handle h) {
 }
 
 // end profiling: per kind (ProfEvent::kind), the summed times, launch counts and flops of the launches since ut_profile_begin
+// (a conv_w4 chain: one time, its layers' flops, and one count per layer - the count stays the number of convolutions)
 int prof_reduce(ut_handle h, hipStream_t s, double ms[2], int64_t launches[2], double flops[2]) {
   h->profiling = false;
   HIPCHK(h, hipStreamSynchronize(s));
@@ -578,7 +619,7 @@ int prof_reduce(ut_handle h, hipStream_t s, double ms[2], int64_t launches[2], d
     float t = 0;
     HIPCHK(h, hipEventElapsedTime(&t, pe.a, pe.b));
     const int k = pe.kind ? 1 : 0;
-    ms[k] += t; flops[k] += pe.flops; launches[k] += 1;
+    ms[k] += t; flops[k] += pe.flops; launches[k] += pe.convs;
   }
   prof_clear(h);
   return UT_OK;
@@ -739,6 +780,7 @@ extern "C" int ut_warp_map(const double* cam_params, const double* crop_params, 
 static int run_stem(ut_handle h, const float* crops, const uint8_t* crops_u8, float* out, int n, hipStream_t st,
                     unsigned** out_max) {
   *out_max = nullptr;
+  if (const int rc = flush_chain(h)) return rc;
   if (h->call_split && !h->latency_mode) {
     const int rc = lease_words(h, st, 1);
     if (rc) return rc;
@@ -751,8 +793,17 @@ static int run_stem(ut_handle h, const float* crops, const uint8_t* crops_u8, fl
 
 // Crops c0 .. c0 + n - 1 of a call (fp32 `crops` or u8 `crops_u8`) through stem .. projection into their rows of `feat` on
 // stream s, in the workspace slices that start at crop `off`.
+static int backbone_pass_launches(ut_handle h, const float* crops, const uint8_t* crops_u8, float* feat, int c0, int n, int off,
+                                  int chunk, hipStream_t s);
 static int backbone_pass(ut_handle h, const float* crops, const uint8_t* crops_u8, float* feat, int c0, int n, int off,
                          int chunk, hipStream_t s) {
+  int rc = backbone_pass_launches(h, crops, crops_u8, feat, c0, n, off, chunk, s);
+  if (!rc) rc = flush_chain(h);      // (the projection has flushed layer4's chain already)
+  if (rc) { h->chain.clear(); h->chain_flops = 0; }      // a failed pass leaves nothing collected
+  return rc;
+}
+static int backbone_pass_launches(ut_handle h, const float* crops, const uint8_t* crops_u8, float* feat, int c0, int n, int off,
+                                  int chunk, hipStream_t s) {
   int rc;
   const size_t a48 = (size_t)off * 48 * 48 * 32, a24 = (size_t)off * 24 * 24 * 64, a12 = (size_t)off * 12 * 12 * 128;
   // the words of one pass (<= 2 x 22 + 16 launches) come from one zeroing, so that none of them is recycled while live
@@ -773,6 +824,7 @@ static int backbone_pass(ut_handle h, const float* crops, const uint8_t* crops_u
       hw = (hw + 2 - 3) / h->bb[b].conv1.stride + 1;
       float* t = x; x = y; y = t;
     }
+    if ((rc = flush_chain(h))) return rc;      // (layer2's chain: its last word is read next)
     if (done == 0) l2_max = xm;
     else if (l2_max && xm) HIPCHK(h, ut::launch_merge_max(l2_max, xm, s));
     else l2_max = nullptr;
@@ -1062,7 +1114,8 @@ static int run_head(ut_handle h, const ut::HeadArgs& a, const float* skel, int n
   rc = run_block(h, blocks[0], b.regin, b.rega, nullptr, b.regb, S, 6, 6, s, in_word, &mid_word, head_split ? tid0 : -1, head_split ? tid0 + 1 : -1);
   if (!rc) rc = run_block(h, blocks[1], b.regb, b.rega, nullptr, b.regin, S, 6, 6, s, mid_word, nullptr, head_split ? tid0 + 2 : -1, head_split ? tid0 + 3 : -1);
   h->call_split = false;
-  if (rc) return rc;
+  if (!rc) rc = flush_chain(h);      // the regressor's chain
+  if (rc) { h->chain.clear(); h->chain_flops = 0; return rc; }
   HIPCHK(h, ut::launch_pool_decode(a, b.regin, reg.c, stride, reg.w_out, reg.b_out, reg.d, out_pose, out_raw, b.rega, s));
   return UT_OK;
 }
@@ -1662,7 +1715,7 @@ int ut_set_block_fusion(ut_handle h, int on) {
 
 int ut_set_resident_weights(ut_handle h, int on) {
   if (!h) return UT_E_INVALID;
-  if (on < 0 || on > 6) return fail(h, UT_E_INVALID, "ut_set_resident_weights: bad argument");
+  if (on < 0 || on > 7) return fail(h, UT_E_INVALID, "ut_set_resident_weights: bad argument");
   h->resident_weights = on;
   return UT_OK;
 }

@@ -110,6 +110,25 @@ hipError_t launch_conv_c32s2(const Stride2Launch& c, hipStream_t s);
 enum W4Form : int { W4_NONE = 0, W4_TILES128, W4_MAP24, W4_STRIDE2 };
 W4Form conv_w4_form(const ConvLaunch& c);
 hipError_t launch_conv_w4(const ConvLaunch& c, hipStream_t s);
+// Consecutive convolutions of conv_w4's stride-1 forms, each reading what the one before wrote, as ONE launch: a tile there is whole
+// maps, so a workgroup takes its tiles depth-first through all layers (conv_w4.hip, CHAIN).  Per layer the bits of launch_conv_w4.
+// The launches share shape, status word and device; the first one's tile_counter is the chain's, every layer keeps its own out_max
+// word, and layer l + 1 is guarded against layer l's values as its own launch would be against layer l's word.
+constexpr int W4_MAX_CHAIN = 9;
+struct W4Layer {
+  const float* in; const float* res; float* out; const void* w_split; const float* bias;
+  const unsigned* in_max;   // the calibrated scale word of `in`
+  unsigned* out_max;
+  float split_unscale;
+  int k_cin, relu;
+};
+struct W4ChainLaunch : ConvLaunch {      // the first layer's launch (shape, queue word, status, its guard), then every layer's record
+  int n_layers;
+  W4Layer lay[W4_MAX_CHAIN];
+};
+bool conv_w4_chainable(const ConvLaunch& a, const ConvLaunch& b);      // b may follow a in a chain
+bool conv_w4_chain_fills(const ConvLaunch& c);      // a chain of launches like c keeps as many CUs busy as the launches themselves
+hipError_t launch_conv_w4_chain(const ConvLaunch* layers, int n_layers, hipStream_t s);
 // 3x3 stride-1 64 -> 64 channels with the weights resident in registers, K split across the two waves of a SIMD (conv_c64k.hip)
 bool conv_c64k_applicable(const ConvLaunch& c);
 hipError_t launch_conv_c64k(const ConvLaunch& c, hipStream_t s);
@@ -162,8 +181,9 @@ enum : int {
   NO_W4 = 2,           // conv_w4.hip in any form (its 128-channel tiles on the 12x12 / 6x6 maps have no bit of their own)
   NO_W4_MAP24 = 4,     // conv_w4.hip on the 24x24x64 maps (conv_c64k / the chunked kernel take layer2)
   NO_W4_STRIDE2 = 8,   // conv_w4.hip's phase-plane form on the stride-2 entries of layer3 / layer4 (the chunked gather kernel takes them)
+  NO_W4_CHAIN = 16,    // conv_w4.hip's chains: every convolution its own launch (read by the host's collector, not by choose_conv)
 };
-constexpr int kResidentKinds[7] = {
+constexpr int kResidentKinds[8] = {
     NO_C64K | NO_W4 | NO_W4_MAP24 | NO_W4_STRIDE2,            // 0: the chunked kernels everywhere
     0,                                                        // 1 (default): conv_w4 wherever it applies
     NO_W4 | NO_W4_MAP24 | NO_W4_STRIDE2,                      // 2: conv_c64k on 24x24, chunked elsewhere
@@ -171,7 +191,9 @@ constexpr int kResidentKinds[7] = {
     NO_W4_MAP24 | NO_W4_STRIDE2,                              // 4: conv_w4 at 12x12 / 6x6, conv_c64k at 24x24
     NO_C64K | NO_W4_MAP24 | NO_W4_STRIDE2,                    // 5: conv_w4 at 12x12 / 6x6, chunked at 24x24
     NO_W4_STRIDE2,                                            // 6: as 1 with the stride-2 entries through the chunked gather kernel
+    NO_W4_CHAIN,                                              // 7: as 1, one launch per convolution
 };
+// (kinds 1 .. 6 chain wherever they send consecutive convolutions to conv_w4's stride-1 forms)
 
 // the patch kernel's row of the dispatch: layer1's shape, except that latency mode (splits == 1) keeps a launch of fewer 64x64
 // tiles than CUs on conv_igemm's small tiles (layer1 of a few crops: 144 small tiles beat 24 large ones)

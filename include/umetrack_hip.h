@@ -211,7 +211,10 @@ int ut_set_block_fusion(ut_handle h, int on);
  * csrc/conv_split.hip: the chunked kernels (layer2's stride-2 entry is csrc/conv_c32s2.hip in any case).
  * 1: conv_w4 wherever it applies.  0: the chunked kernels everywhere.  6: as 1 with the stride-2 entries through the chunked gather
  * kernel.  With those through the gather kernel as well - 2: conv_c64k on 24x24, chunked elsewhere.  4: conv_w4 at 12x12 / 6x6,
- * conv_c64k at 24x24.  5: conv_w4 at 12x12 / 6x6, chunked at 24x24.  3: conv_w4 on the stride-1 convolutions of all three sizes. */
+ * conv_c64k at 24x24.  5: conv_w4 at 12x12 / 6x6, chunked at 24x24.  3: conv_w4 on the stride-1 convolutions of all three sizes.
+ * Consecutive stride-1 convolutions that conv_w4 takes run as ONE launch (a chain: a workgroup carries its tiles of whole maps
+ *    depth-first through the layers; per layer the same bits) under UT_SPLIT_SCALE_CALIBRATED with the fusion switch on, in every
+ *    kind that sends them there.  7: as 1, one launch per convolution. */
 int ut_set_resident_weights(ut_handle h, int on);
 
 /* Latency mode for calls on a handful of crops (the per-frame tracker): convolutions whose launch has far fewer tiles
@@ -481,7 +484,8 @@ int ut_keypoint_metrics(ut_handle h, const float* gt, const float* tracked, cons
 
 /* Names of the kernels launched by the calls above and the average duration in ms of the
  * dominant (implicit-GEMM convolution) kernel measured with hipEvents on `stream` between
- * ut_profile_begin and ut_profile_end (bench.py roofline leg). */
+ * ut_profile_begin and ut_profile_end (bench.py roofline leg).  A chain of convolutions that runs as one launch
+ * (ut_set_resident_weights) is timed as that launch, with its layers' summed flops, and counts one per layer. */
 int ut_profile_begin(ut_handle h, void* stream);
 int ut_profile_end(ut_handle h, void* stream, double* conv_ms_total, int64_t* conv_launches,
                    double* conv_flops_total);

@@ -26,7 +26,7 @@ ho = hw // stride
 
 ABL = {
     "nostore": [("            __builtin_amdgcn_raw_buffer_store_b32(o, o_rsrc, off, 0, 0);", "            if (p.k_pad < 0) __builtin_amdgcn_raw_buffer_store_b32(o, o_rsrc, off, 0, 0);")],
-    "nores": [("__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, off, 0, 0)", "__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, W4_HOOB, 0, 0)")],
+    "nores": [("__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, off, 0, LDAUX)", "__builtin_amdgcn_raw_buffer_load_b32(r_rsrc, W4_HOOB, 0, LDAUX)")],
     "nowload": [("    wf[SET][PL] = __builtin_bit_cast(", "    if (p.k_pad < 0) wf[SET][PL] = __builtin_bit_cast(")],
     "nopatch": [("          if ((N) == 14 && q < W4_NLOAD)  ", "          if ((N) == 14 && q < W4_NLOAD && p.k_pad < 0)  "),
                 ("          if ((N) == 13 && q >= 4 && q < 4 + W4_NLOAD) {", "          if ((N) == 13 && q >= 4 && q < 4 + W4_NLOAD && p.k_pad < 0) {")],

@@ -3,6 +3,8 @@
 maps the convolution launches (conv_igemm / conv_pw / conv_split / halo patch) of the LAST step to the network's convolutions by launch order and
 prints duration, FLOPs and TFLOP/s of each - and the launch's COMPULSORY bytes (input once, output once, the residual where there is one;
 fp32 tensors) over its duration: the HBM side of the same launch -, plus totals of every other kernel in that step.
+A conv_w4 chain (the consecutive stride-1 3x3 convolutions of a layer as one launch) is ONE row with its layers' summed FLOPs and
+compulsory bytes; the layers are listed under the table.
     python tools/layer_profile.py <kernel_trace.csv> <n_crops> <chunk>"""
 import collections
 import csv
@@ -52,6 +54,26 @@ if any("conv_pw" in r["Kernel_Name"] for r in rows):               # the two 1x1
     head = [("fus0-2 144->108->72->72", sum(h[1] for h in head[:3]), 144 + 72), ("tmp0-2 90->90 x3", sum(h[1] for h in head[3:6]), 180)] + head[6:]
 seq += [(nm, 2 * mac * 36 * s, 4 * ch * 36 * s) for nm, mac, ch in head]
 
+# conv_w4 chains: every maximal run of stride-1 3x3 convolutions from layer2 on (a block's conv2, a conv1 without a stride) and the
+# regressor's four convolutions are one launch each
+chained = any("conv_w4" in r["Kernel_Name"] and r["Kernel_Name"].split("<")[1].split(">")[0].split(", ")[5:6] == ["true"] for r in rows if "<" in r["Kernel_Name"])
+chain_layers = {}
+if chained:
+    in_chain = lambda nm: nm.startswith("reg") or (not nm.startswith(("b0.", "b1.")) and (".conv2 " in nm or (".conv1 " in nm and " s1 " in nm)))
+    merged = []
+    for nm, fl, by in seq:
+        if in_chain(nm) and merged and merged[-1][3]:
+            first, f0, b0, members = merged[-1]
+            merged[-1] = (first, f0 + fl, b0 + by, members + [nm])
+        else:
+            merged.append((nm, fl, by, [nm] if in_chain(nm) else None))
+    seq = []
+    for nm, fl, by, members in merged:
+        if members and len(members) > 1:
+            nm = f"{members[0].split(' ')[0]} .. {members[-1].split(' ')[0]} x{len(members)}"
+            chain_layers[nm] = members
+        seq.append((nm, fl, by))
+
 is_conv = lambda r: any(k in r["Kernel_Name"] for k in ("conv_igemm", "conv_pw", "conv3x3_c32_patch", "conv_split", "conv_block32", "conv_c64r", "conv_c64k", "conv_c32s2", "conv_w4"))
 
 
@@ -66,7 +88,7 @@ def label(name):
         a = args.split(", ")
         if len(a) > 4 and a[4] == "true":
             return f"split f16 phase planes -> {a[0]}x{a[1]} x 128 ch, 4 waves"
-        return f"split f16 whole maps {a[0]}x{a[1]} x {'128' if a[3] == '1' else '64'} ch, 4 waves"
+        return f"split f16 whole maps {a[0]}x{a[1]} x {'128' if a[3] == '1' else '64'} ch, 4 waves" + (", chain" if a[5:6] == ["true"] else "")
     if "conv_block32" in name:
         return "fused block 12x16 split f16"
     if "conv_c64r" in name:
@@ -92,6 +114,8 @@ print(f"{'conv':28s} {'kernel':28s} {'n':>3s} {'total us':>10s} {'TFLOP/s':>8s} 
 for nm, (n, t, fl, tile, by) in agg.items():
     print(f"{nm:28s} {tile:28s} {n:3d} {t:10.1f} {fl/t/1e6:8.1f} {by/1e9:6.2f} {by/t/1e6:6.2f} {100*t/tot_t:8.2f}")
 print(f"conv total {tot_t/1e3:.3f} ms, {tot_f/tot_t/1e6:.1f} TFLOP/s, {tot_b/1e9:.1f} GB of compulsory traffic = {tot_b/tot_t/1e6:.2f} TB/s")
+for nm, members in chain_layers.items():
+    print(f"chain {nm}: " + ", ".join(members))
 t0 = int(last[0]["Start_Timestamp"])
 others = collections.Counter()
 for r in rows:
