@@ -102,6 +102,12 @@ _VIEWS_PROTOTYPES = {
                                  _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
 }
 VIEWS_EXPORTS = tuple(_VIEWS_PROTOTYPES)
+# The entry of include/umetrack_hip_robust.h, in a table of its own like its header (tests/test_robust_host.py pins it).
+_ROBUST_PROTOTYPES = {
+    "ut_fit_pose_views_robust": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _f32,
+                                        _i32, _i32, _f32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+}
+ROBUST_EXPORTS = tuple(_ROBUST_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -126,7 +132,7 @@ def load_library() -> ctypes.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
-                                      **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES}.items():
+                                      **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES, **_ROBUST_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -650,7 +656,7 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
                    limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
                    max_iters: int = 32, *, n: Optional[int] = None, init_ja_stride: int = 22, init_xf_stride: int = 16,
                    out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22, xf_stride: int = 16,
-                   info: Optional[torch.Tensor] = None, residual=False, engine: Optional["HipEngine"] = None):
+                   info: Optional[torch.Tensor] = None, residual=False, engine: Optional["HipEngine"] = None, _robust=None):
     """ut_fit_pose_views: the pose whose landmarks, projected into the views, meet the detections - fit_pose on the
     reprojection cost sum_v sum_l w_vl |project_v(landmark_l) - window_vl|^2 instead of 3-D targets.  window f64 [n,V,21,2] px,
     cam_rows i32 [n,V] (-1 = unused view), table f64 [R,32] Fisheye62 source cameras or [R,24] pinhole crop cameras (told apart
@@ -660,7 +666,8 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
     pose outputs as for fit_pose.  Returns (joint_angles, wrist_xf, info [n,4]: rms reprojection residual px, largest
     reprojection distance px, iterations, status bits UT_FIT_*) and, with residual=True or a preallocated f32 [n,V,21], the
     reprojection distance of every used observation as a fourth item.  A cam_rows entry outside [-1, R) raises IndexError and
-    writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks."""
+    writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks.  _robust = (loss
+    code, loss_scale, inlier) is fit_pose_views_robust's: the same marshalling into ut_fit_pose_views_robust."""
     if init_angles is None or init_wrist_xf is None:
         raise ValueError("init_angles and init_wrist_xf are required: ut_fit_pose_views has no cold start")
     if window.dim() != 4 or tuple(window.shape[2:]) != (21, 2) or window.dtype != torch.float64:
@@ -686,11 +693,54 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
         residual = _out(None if residual is True else residual, (n, v, 21), torch.float32, d, "residual")
     else:
         residual = None
-    _fit_call("ut_fit_pose_views", d, h, _ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v,
-              _ptr(table), table.shape[0], kind, _ptr(limits), _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf),
-              init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale), int(max_iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]),
-              xf_stride, _ptr(info), _ptr(residual))
-    return (out[0], out[1], info) if residual is None else (out[0], out[1], info, residual)
+    front = (_ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind,
+             _ptr(limits), _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale),
+             int(max_iters))
+    back = (n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride, _ptr(info), _ptr(residual))
+    result = (out[0], out[1], info) if residual is None else (out[0], out[1], info, residual)
+    if _robust is None:
+        _fit_call("ut_fit_pose_views", d, h, *front, *back)
+        return result
+    loss, loss_scale, inlier = _robust
+    if inlier is True or isinstance(inlier, torch.Tensor):
+        inlier = _out(None if inlier is True else inlier, (n, v, 21), torch.float32, d, "inlier")
+    else:
+        inlier = None
+    _fit_call("ut_fit_pose_views_robust", d, h, *front, int(loss), ctypes.c_float(loss_scale), *back, _ptr(inlier))
+    return result if inlier is None else result + (inlier,)
+
+
+UT_LOSS_SQUARED, UT_LOSS_HUBER, UT_LOSS_GEMAN_MCCLURE = 0, 1, 2
+LOSSES = {"squared": UT_LOSS_SQUARED, "huber": UT_LOSS_HUBER, "geman_mcclure": UT_LOSS_GEMAN_MCCLURE}
+
+
+def loss_code(loss) -> int:
+    """A loss by its name in LOSSES or by its UT_LOSS_* code."""
+    if isinstance(loss, str):
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be one of {sorted(LOSSES)}, got {loss!r}")
+        return LOSSES[loss]
+    if loss not in LOSSES.values():
+        raise ValueError(f"loss must be one of {sorted(LOSSES)} or a UT_LOSS_* code, got {loss!r}")
+    return int(loss)
+
+
+def fit_pose_views_robust(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                          init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                          limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                          max_iters: int = 32, loss="geman_mcclure", loss_scale: float = 3.0, *, inlier=False, **kw):
+    """ut_fit_pose_views_robust: fit_pose_views on the cost sum_v sum_l w_vl c^2 rho(d_vl^2 / c^2), d the reprojection distance and
+    c = loss_scale in px - a fit that survives a few grossly wrong detections in one launch.  loss: "squared" (fit_pose_views, bit
+    for bit), "huber" or "geman_mcclure", or a UT_LOSS_* code; loss_scale must be finite and > 0 with a robust loss.  Everything
+    else, **kw included (n, the strides, out, info, residual, engine), as for fit_pose_views, whose tuple comes back - info[0] is
+    sqrt(robust cost / sum of the used weights), info[1] and residual stay raw distances - and, with inlier=True or a preallocated
+    f32 [n,V,21], psi of every used observation at the returned pose as its last item: 1 for an inlier, towards 0 for an
+    outlier, 0 where unused or refused."""
+    code = loss_code(loss)
+    if code != UT_LOSS_SQUARED and not (np.isfinite(loss_scale) and loss_scale > 0):
+        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
+    return fit_pose_views(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters,
+                          _robust=(code, float(loss_scale), inlier), **kw)
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

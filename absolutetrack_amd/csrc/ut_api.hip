@@ -4,6 +4,7 @@
 #include "../../include/umetrack_hip.h"
 #include "../../include/umetrack_hip_fit.h"
 #include "../../include/umetrack_hip_info.h"
+#include "../../include/umetrack_hip_robust.h"
 #include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_triangulate.h"
 #include "../../include/umetrack_hip_views.h"
@@ -1527,17 +1528,26 @@ int ut_triangulate_points_info(ut_handle h, const double* window, const float* w
                             n_points, n, max_iters, points, points_f32, point_stride, info, residual, sqrt_info, stream);
 }
 
-int ut_fit_pose_views(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
-                      const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind, const float* limits,
-                      const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
-                      const int64_t* mirror, float t_scale, int max_iters, int n, float* joint_angles, int ja_stride,
-                      float* wrist_xf, int xf_stride, float* info, float* residual, void* stream) {
-  const char* who = "ut_fit_pose_views";
+static_assert(UT_LOSS_SQUARED == ut::FITV_LOSS_SQUARED && UT_LOSS_HUBER == ut::FITV_LOSS_HUBER &&
+              UT_LOSS_GEMAN_MCCLURE == ut::FITV_LOSS_GEMAN_MCCLURE, "umetrack_hip_robust.h and ut_kernels.h");
+
+namespace {
+// ut_fit_pose_views and ut_fit_pose_views_robust: one set of checks, one status path.  UT_LOSS_SQUARED without `inlier` launches
+// fit_views.hip's kernels (launch_fit_pose_views_robust hands it on).
+int fit_pose_views(ut_handle h, const char* who, const float* hand_model, int n_models, const double* window, const float* weights,
+                   const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind, const float* limits,
+                   const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
+                   const int64_t* mirror, float t_scale, int max_iters, int loss, float loss_scale, int n, float* joint_angles,
+                   int ja_stride, float* wrist_xf, int xf_stride, float* info, float* residual, float* inlier, void* stream) {
   if (!window || !cam_rows || !table) return fail_as(h, who, "null argument");
   if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
     return fail_as(h, who, "table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
   if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS) return fail_as(h, who, "max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
   if (n_rows < 1) return fail_as(h, who, "bad argument");
+  if (loss != UT_LOSS_SQUARED && loss != UT_LOSS_HUBER && loss != UT_LOSS_GEMAN_MCCLURE)
+    return fail_as(h, who, "loss must be UT_LOSS_SQUARED, UT_LOSS_HUBER or UT_LOSS_GEMAN_MCCLURE");
+  if (loss != UT_LOSS_SQUARED && (!(loss_scale > 0.f) || !(loss_scale <= 3.0e38f)))
+    return fail_as(h, who, "loss_scale must be positive and finite");
   const int rc = fit_pose_args(h, who, hand_model, n_models, nullptr, 0, init_angles, init_ja_stride, init_wrist_xf,
                                init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride, false);
   if (rc) return rc;
@@ -1553,12 +1563,35 @@ int ut_fit_pose_views(ut_handle h, const float* hand_model, int n_models, const 
   DeviceScope scope(st.device);
   if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
   hipStream_t s = (hipStream_t)stream;
-  const ut::FitViewsArgs a{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride,
-                            mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
-                           window, weights, cam_rows, max_views, table, n_rows,
-                           table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE, info, residual, st.dev};
-  HIPCHK(h, ut::launch_fit_pose_views(a, s));
+  const ut::FitViewsRobustArgs a{{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride,
+                                   mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                                  window, weights, cam_rows, max_views, table, n_rows,
+                                  table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE, info, residual, st.dev},
+                                 loss, loss_scale, inlier};
+  HIPCHK(h, ut::launch_fit_pose_views_robust(a, s));
   return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, who) : UT_OK;
+}
+}  // namespace
+
+int ut_fit_pose_views(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
+                      const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind, const float* limits,
+                      const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
+                      const int64_t* mirror, float t_scale, int max_iters, int n, float* joint_angles, int ja_stride,
+                      float* wrist_xf, int xf_stride, float* info, float* residual, void* stream) {
+  return fit_pose_views(h, "ut_fit_pose_views", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows, table_kind,
+                        limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
+                        UT_LOSS_SQUARED, 0.f, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, nullptr, stream);
+}
+
+int ut_fit_pose_views_robust(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
+                             const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind,
+                             const float* limits, const float* init_angles, int init_ja_stride, const float* init_wrist_xf,
+                             int init_xf_stride, const int64_t* mirror, float t_scale, int max_iters, int loss, float loss_scale,
+                             int n, float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride, float* info,
+                             float* residual, float* inlier, void* stream) {
+  return fit_pose_views(h, "ut_fit_pose_views_robust", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
+                        table_kind, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
+                        loss, loss_scale, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, inlier, stream);
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

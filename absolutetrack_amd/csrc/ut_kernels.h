@@ -430,6 +430,17 @@ struct FitViewsArgs {
 };
 hipError_t launch_fit_pose_views(const FitViewsArgs& a, hipStream_t s);
 
+// fit_views_robust.hip: the same fit under a robust loss (ut_fit_pose_views_robust).  FitViewsArgs itself is a kernel argument of
+// fit_views.hip, whose device code stays what it is, so the loss's three fields stand behind it here and not inside it.
+enum : int { FITV_LOSS_SQUARED = 0, FITV_LOSS_HUBER = 1, FITV_LOSS_GEMAN_MCCLURE = 2 };
+struct FitViewsRobustArgs {
+  FitViewsArgs views;
+  int loss;                             // FITV_LOSS_*
+  float loss_scale;                     // px, finite and > 0; not read by FITV_LOSS_SQUARED
+  float* inlier;                        // [n,max_views,21] or null: psi of every used observation at the returned pose, 0 elsewhere
+};
+hipError_t launch_fit_pose_views_robust(const FitViewsRobustArgs& a, hipStream_t s);
+
 // fit_scale.hip: fit.hip's cost with ln(scale) of the hand as a 27th parameter, and the pool of per-pose scales, one wave per
 // group.  Pointers as ut_fit_pose_scale / ut_pool_scale document them; the constants are public as UT_SCALE_* / UT_FITS_*.
 constexpr int FITS_MODE_FREE = 0, FITS_MODE_FIXED = 1;

@@ -244,7 +244,8 @@ def fit_landmarks_info(hand_model: HandModel, landmarks: torch.Tensor, sqrt_info
 
 def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, init,
                         weights: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, limits=None,
-                        max_iters: int = 32, with_residual: bool = False):
+                        max_iters: int = 32, with_residual: bool = False, loss="squared", loss_scale: float = 3.0,
+                        return_inliers: bool = False):
     """fit_landmarks on 2-D keypoints in camera views instead of 3-D landmarks, on the HIP kernel csrc/fit_views.hip (no CPU
     implementation): the pose that minimises sum_v sum_l w_vl |project_v(landmark_l) - window_vl|^2 through the exact camera
     model.  window f64 [...,V,21,2] px; cam_rows i32 [...,V] rows of `table`, -1 = unused view; table f64 [R,32] Fisheye62
@@ -255,18 +256,26 @@ def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: t
     angles inside hand_model.joint_limits.  Returns (joint_angles [...,22], wrist_transforms [...,4,4], info [...,4]: rms
     reprojection residual px, largest reprojection distance px, iterations, status as for fit_landmarks) and, with
     with_residual=True, the reprojection distance [...,V,21] of every used detection - zero an outlier's weight and call
-    again.  Leading dims, devices and mirror as for fit_landmarks."""
+    again.  loss = "huber" or "geman_mcclure" fits the robust cost sum w c^2 rho(d^2 / c^2) with c = loss_scale px instead
+    (_native.fit_pose_views_robust, csrc/fit_views_robust.hip): a few grossly wrong detections then cost one launch; info[0] is
+    the robust cost's rms, the distances stay raw.  return_inliers=True appends psi [...,V,21] of every used detection at the
+    returned pose - 1 an inlier, towards 0 an outlier; with the default "squared", which is the plain fit bit for bit, 1 at every
+    used detection.  Leading dims, devices and mirror as for fit_landmarks."""
     if init is None:
         raise ValueError("init = (joint_angles, wrist_transforms) is required: fit_landmarks_views has no cold start")
     if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
         raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
     v = window.shape[-3]
     s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, limits, "limits")
-    res = _native.fit_pose_views(s.blob, s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32),
-                                 table.to(s.dev, torch.float64), *s.init(init), s.f32(weights, (v, 21)), s.box, s.flags(mirror),
-                                 max_iters=max_iters, residual=with_residual)
+    args = (s.blob, s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32), table.to(s.dev, torch.float64),
+            *s.init(init), s.f32(weights, (v, 21)), s.box, s.flags(mirror))
+    if _native.loss_code(loss) == _native.UT_LOSS_SQUARED and not return_inliers:
+        res = _native.fit_pose_views(*args, max_iters=max_iters, residual=with_residual)
+    else:
+        res = _native.fit_pose_views_robust(*args, max_iters=max_iters, loss=loss, loss_scale=loss_scale, residual=with_residual,
+                                            inlier=return_inliers)
     out = (s.back(res[0], (22,)), s.back(res[1], (4, 4)), s.back(res[2], (4,)))
-    return out + (s.back(res[3], (v, 21)),) if with_residual else out
+    return out + tuple(s.back(r, (v, 21)) for r in res[3:])
 
 
 FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FITS_CONVERGED, _native.UT_FITS_AT_MAX_ITERS,

@@ -231,7 +231,8 @@ def triangulate_keypoints(window: torch.Tensor, cam_params: torch.Tensor, src_ro
 def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
                            init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
                            mirror: Optional[torch.Tensor] = None, limits: Optional[torch.Tensor] = None, t_scale: float = 1.0,
-                           max_iters: int = 32, with_residual: bool = False, engine: Optional[_native.HipEngine] = None, **strided):
+                           max_iters: int = 32, with_residual: bool = False, engine: Optional[_native.HipEngine] = None,
+                           loss="squared", loss_scale: float = 3.0, with_inliers: bool = False, **strided):
     """Batched tracker.refine_hand_pose_in_views over frames and hands: the poses of n hand-samples whose landmarks meet their
     window keypoints in the cameras that see them, ONE ut_fit_pose_views launch.  hand_model f32 [1|n,321] packed models
     (hand.device_blob); window f64 [n,V,21,2] px on the device (what project_keypoints returns, or detections); cam_params f64
@@ -240,9 +241,14 @@ def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_p
     triangulate_keypoints' points; weights f32 [n,V,21] or None, e.g. (flags == 3).float() of project_keypoints or detection
     confidences, 0 where a landmark is not seen.  **strided: n, init_ja_stride, init_xf_stride, out, ja_stride, xf_stride of
     _native.fit_pose_views - poses inside HotPath records, read and written in place.  Returns (joint_angles, wrist_xf, info
-    f32 [n,4]) and, with with_residual=True, residual f32 [n,V,21]."""
-    return _native.fit_pose_views(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, weights=weights, limits=limits,
-                                  mirror=mirror, t_scale=t_scale, max_iters=max_iters, residual=with_residual, engine=engine, **strided)
+    f32 [n,4]) and, with with_residual=True, residual f32 [n,V,21].  loss "huber" / "geman_mcclure" with loss_scale px: ONE
+    ut_fit_pose_views_robust launch on the robust cost instead, for detections some of which are grossly wrong; with_inliers=True
+    appends psi f32 [n,V,21] of every used detection at the returned pose (1 an inlier, towards 0 an outlier)."""
+    kw = dict(weights=weights, limits=limits, mirror=mirror, t_scale=t_scale, max_iters=max_iters, residual=with_residual, engine=engine, **strided)
+    if _native.loss_code(loss) == _native.UT_LOSS_SQUARED and not with_inliers:
+        return _native.fit_pose_views(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, **kw)
+    return _native.fit_pose_views_robust(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, loss=loss,
+                                         loss_scale=loss_scale, inlier=with_inliers, **kw)
 
 
 def view_rows(src_index: torch.Tensor, sample_range: torch.Tensor, max_views: int = MAX_VIEW_NUM) -> torch.Tensor:

@@ -234,7 +234,8 @@ def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weight
 def hand_pose_from_window_keypoints(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray,
                                     hand_idx: int, weights: Optional[np.ndarray] = None,
                                     init: Optional[SingleHandPose] = None, use_information: bool = False,
-                                    refine_in_views: bool = False) -> Tuple[SingleHandPose, np.ndarray]:
+                                    refine_in_views: bool = False, loss="squared", loss_scale: float = 3.0
+                                    ) -> Tuple[SingleHandPose, np.ndarray]:
     """From 2-D detections to a pose: window_keypoints [n_cams,21,2] of one hand in the cameras -> (SingleHandPose, the
     triangulation's info [21,4]).  triangulate_landmarks first, then the pose fit of hand_pose_from_landmarks with each
     landmark weighted by (smallest finite sigma / its sigma)^2, in (0, 1]: a landmark the views pin down badly counts
@@ -244,22 +245,25 @@ def hand_pose_from_window_keypoints(hand_model: HandModel, cameras: List[CameraM
     landmarks that carry information (from `init` when given), then the information fit started from it - so that depth,
     which a narrow baseline measures badly, is fixed by the hand's known size.  refine_in_views=True: the pose of either
     chain is then refined on ALL given detections by refine_hand_pose_in_views - the landmarks that one camera alone sees, which
-    the triangulation refuses, included; the default leaves the chain's result as it is."""
+    the triangulation refuses, included; the default leaves the chain's result as it is.  loss, loss_scale: the
+    refinement's, as for refine_hand_pose_in_views; not read without it."""
     pose, info = _chain_pose_from_window_keypoints(hand_model, cameras, window_keypoints, hand_idx, weights, init, use_information)
     if refine_in_views:
-        pose = refine_hand_pose_in_views(hand_model, cameras, window_keypoints, hand_idx, pose, weights)[0]
+        pose = refine_hand_pose_in_views(hand_model, cameras, window_keypoints, hand_idx, pose, weights, loss=loss, loss_scale=loss_scale)[0]
     return pose, info
 
 
 def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray, hand_idx: int,
-                              init: SingleHandPose, weights: Optional[np.ndarray] = None
-                              ) -> Tuple[SingleHandPose, np.ndarray, np.ndarray]:
+                              init: SingleHandPose, weights: Optional[np.ndarray] = None, loss="squared", loss_scale: float = 3.0):
     """The pose that meets the detections themselves: window_keypoints [n_cams,21,2] of one hand in the cameras and a start
     `init` (the previous frame's pose, or hand_pose_from_window_keypoints') -> (SingleHandPose, info [4]: rms reprojection
     residual px, largest reprojection distance px, iterations, status bits FIT_*, residual [n_cams,21]: the reprojection
     distance of every used detection), one ut_fit_pose_views launch (hand.fit_landmarks_views, csrc/fit_views.hip).  weights
     [n_cams,21] >= 0, 0 where the camera does not see the landmark (the window there is not read); None = all 1.  One camera
-    is enough: the hand's known size fixes its depth.  Cameras as for triangulate_landmarks."""
+    is enough: the hand's known size fixes its depth.  Cameras as for triangulate_landmarks.  loss "huber" / "geman_mcclure" with
+    loss_scale px: the robust cost of hand.fit_landmarks_views, for detections some of which are grossly wrong (a fingertip on the
+    wrong finger); a fourth item then, inlier [n_cams,21]: psi of every used detection at the returned pose, 1 an inlier, towards
+    0 an outlier.  The default "squared" returns the three items it always did."""
     table = _native_camera_table(cameras, "refine_hand_pose_in_views")
     win = np.ascontiguousarray(window_keypoints, np.float64)
     if win.shape != (len(cameras), 21, 2):
@@ -269,12 +273,13 @@ def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel],
         if weights.shape != win.shape[:2]:
             raise ValueError(f"weights must be {win.shape[:2]}, got {weights.shape}")
     start = (torch.from_numpy(np.asarray(init.joint_angles, np.float32)), torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
-    ja, xf, fit_info, residual = fit_landmarks_views(
+    robust = _native.loss_code(loss) != _native.UT_LOSS_SQUARED
+    ja, xf, fit_info, residual, *inlier = fit_landmarks_views(
         hand_model, torch.from_numpy(win), torch.arange(len(cameras), dtype=torch.int32), torch.from_numpy(table), start,
         weights=None if weights is None else torch.from_numpy(weights), mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0),
-        with_residual=True)
+        with_residual=True, loss=loss, loss_scale=loss_scale, return_inliers=robust)
     pose = SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(), hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0)
-    return pose, fit_info.numpy(), residual.numpy()
+    return (pose, fit_info.numpy(), residual.numpy()) + tuple(r.numpy() for r in inlier)
 
 
 def _chain_pose_from_window_keypoints(hand_model, cameras, window_keypoints, hand_idx, weights, init, use_information):

@@ -1,0 +1,9 @@
+/* Compiled as C99 by tests/test_robust_host.py: umetrack_hip_robust.h must be usable from C. */
+#include "umetrack_hip_robust.h"
+
+int robust_c99_probe(void) {
+  int (*fit)(ut_handle, const float*, int, const double*, const float*, const int32_t*, int, const double*, int, int, const float*,
+             const float*, int, const float*, int, const int64_t*, float, int, int, float, int, float*, int, float*, int, float*,
+             float*, float*, void*) = ut_fit_pose_views_robust;
+  return (fit != 0) + UT_LOSS_SQUARED + UT_LOSS_HUBER + UT_LOSS_GEMAN_MCCLURE + UT_FIT_CONVERGED + UT_TRI_MAX_VIEWS;
+}
