@@ -85,7 +85,8 @@ __global__ __launch_bounds__(256) void render_check_kernel(const int64_t* __rest
 //      Triangles are strided over the threads; each walks the pixels of its bounding box inside the pass and offers its word
 //      with one LDS atomicMin per covered pixel.  Depths are positive, so their bit patterns order like the numbers, and the
 //      smaller triangle index wins on equal depth: the minimum does not depend on the order of arrival.
-//      A triangle with a marked vertex is skipped whole; one with zero area covers nothing.  No culling: a triangle is brought to
+//      A triangle with a marked vertex is skipped whole; one whose fp32 area is zero, infinite or not a number (a vertex that
+//      projects to a NaN or an infinity, or an overflowing product) covers nothing.  No culling: a triangle is brought to
 //      positive area by exchanging two vertices first (crop cameras of right hands are mirrored).  With
 //         E_ab(p) = (xb - xa) (py - ya) - (yb - ya) (px - xa)
 //      evaluated from the edge's own start vertex, a pixel centre is covered when E_01, E_12, E_20 >= 0, and a zero counts only
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(256) void render_mesh_kernel(RenderArgs g) {
       float x2 = c[0], y2 = c[1], w2 = c[2];
       if (w0 < 0.f || w1 < 0.f || w2 < 0.f) continue;
       float area = (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0);
-      if (!(area != 0.f)) continue;                                     // zero area, or not a number
+      if (!(fabsf(area) > 0.f && fabsf(area) < INFINITY)) continue;     // zero area, infinite (fp32 overflow), or not a number
       if (area < 0.f) {
         float s;
         s = x1; x1 = x2; x2 = s;

@@ -379,7 +379,8 @@ int ut_project_points(ut_handle h, const float* points, int point_stride, int n_
  * Rules: a vertex is projected in fp64 (world_to_eye, / z, * f + c) and rounded to fp32 (x, y, 1 / z); the rest is fp32 with every
  * operation rounded on its own.  A triangle with a vertex at eye z < 1e-4 is skipped whole (lib/common/crop.py:25).  No
  * culling.  With E_ab(p) = (xb - xa)(py - ya) - (yb - ya)(px - xa), taken from the edge's start vertex, and the vertices
- * ordered so that the area E_01(v2) is positive (zero area covers nothing), a pixel is covered when E_01, E_12 and E_20 are >= 0,
+ * ordered so that the area E_01(v2) is positive (an fp32 area that is zero, infinite or not a number covers nothing: degenerate
+ * triangles, and triangles with a vertex whose projection is not finite or overflows), a pixel is covered when E_01, E_12 and E_20 are >= 0,
  * a zero counting only on a top or left edge (yb - ya < 0, or yb == ya and xb - xa > 0; y grows downwards), so a pixel centre
  * on an edge shared by two triangles belongs to exactly one.  Depth is perspective correct:
  * 1 / z = w0 + (E_20 (w1 - w0) + E_01 (w2 - w0)) / area with w = 1 / z of the vertices.  The smallest depth wins, the smaller
