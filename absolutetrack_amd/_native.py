@@ -1,5 +1,6 @@
 """ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension headers include/umetrack_hip_fit.h,
-include/umetrack_hip_triangulate.h, include/umetrack_hip_scale.h and include/umetrack_hip_info.h).
+include/umetrack_hip_triangulate.h, include/umetrack_hip_scale.h, include/umetrack_hip_info.h, include/umetrack_hip_views.h,
+include/umetrack_hip_robust.h and include/umetrack_hip_views_scale.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, every entry point raises.  PyTorch-ROCm is used for device memory and
@@ -108,6 +109,12 @@ _ROBUST_PROTOTYPES = {
                                         _i32, _i32, _f32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
 ROBUST_EXPORTS = tuple(_ROBUST_PROTOTYPES)
+# The entry of include/umetrack_hip_views_scale.h, in a table of its own like its header (tests/test_views_scale_host.py pins it).
+_VIEWS_SCALE_PROTOTYPES = {
+    "ut_fit_pose_views_scale": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp,
+                                       _f32, _i32, _i32, _f32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+VIEWS_SCALE_EXPORTS = tuple(_VIEWS_SCALE_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -132,7 +139,8 @@ def load_library() -> ctypes.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
-                                      **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES, **_ROBUST_PROTOTYPES}.items():
+                                      **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES, **_ROBUST_PROTOTYPES,
+                                      **_VIEWS_SCALE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -656,7 +664,8 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
                    limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
                    max_iters: int = 32, *, n: Optional[int] = None, init_ja_stride: int = 22, init_xf_stride: int = 16,
                    out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22, xf_stride: int = 16,
-                   info: Optional[torch.Tensor] = None, residual=False, engine: Optional["HipEngine"] = None, _robust=None):
+                   info: Optional[torch.Tensor] = None, residual=False, engine: Optional["HipEngine"] = None, _robust=None,
+                   _scale=None):
     """ut_fit_pose_views: the pose whose landmarks, projected into the views, meet the detections - fit_pose on the
     reprojection cost sum_v sum_l w_vl |project_v(landmark_l) - window_vl|^2 instead of 3-D targets.  window f64 [n,V,21,2] px,
     cam_rows i32 [n,V] (-1 = unused view), table f64 [R,32] Fisheye62 source cameras or [R,24] pinhole crop cameras (told apart
@@ -667,7 +676,9 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
     reprojection distance px, iterations, status bits UT_FIT_*) and, with residual=True or a preallocated f32 [n,V,21], the
     reprojection distance of every used observation as a fourth item.  A cam_rows entry outside [-1, R) raises IndexError and
     writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks.  _robust = (loss
-    code, loss_scale, inlier) is fit_pose_views_robust's: the same marshalling into ut_fit_pose_views_robust."""
+    code, loss_scale, inlier) is fit_pose_views_robust's: the same marshalling into ut_fit_pose_views_robust; with _scale =
+    (init_scale, scale_mode, scale) as well it is fit_pose_views_scale's, into ut_fit_pose_views_scale: info is [n,6] and the
+    scale follows the wrist in the result."""
     if init_angles is None or init_wrist_xf is None:
         raise ValueError("init_angles and init_wrist_xf are required: ut_fit_pose_views has no cold start")
     if window.dim() != 4 or tuple(window.shape[2:]) != (21, 2) or window.dtype != torch.float64:
@@ -688,7 +699,7 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
         weights = _need(weights, torch.float32, d, "weights")
     hand_model, init_angles, init_wrist_xf, n, out, limits, mirror, h = _fit_args(
         d, hand_model, init_angles, init_wrist_xf, n, nw, [], out, limits, mirror, engine, windows=True)
-    info = _out(info, (n, 4), torch.float32, d, "info")
+    info = _out(info, (n, 4 if _scale is None else 6), torch.float32, d, "info")
     if residual is True or isinstance(residual, torch.Tensor):
         residual = _out(None if residual is True else residual, (n, v, 21), torch.float32, d, "residual")
     else:
@@ -706,7 +717,18 @@ def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: tor
         inlier = _out(None if inlier is True else inlier, (n, v, 21), torch.float32, d, "inlier")
     else:
         inlier = None
-    _fit_call("ut_fit_pose_views_robust", d, h, *front, int(loss), ctypes.c_float(loss_scale), *back, _ptr(inlier))
+    if _scale is None:
+        _fit_call("ut_fit_pose_views_robust", d, h, *front, int(loss), ctypes.c_float(loss_scale), *back, _ptr(inlier))
+        return result if inlier is None else result + (inlier,)
+    init_scale, scale_mode, scale = _scale
+    if init_scale is not None:
+        init_scale = _need(init_scale, torch.float32, d, "init_scale").reshape(-1)
+        if init_scale.shape[0] != n:
+            raise ValueError("init_scale batch mismatch")
+    scale = _out(scale, (n,), torch.float32, d, "scale")
+    _fit_call("ut_fit_pose_views_scale", d, h, *front[:10], _ptr(init_scale), int(scale_mode), *front[10:], int(loss),
+              ctypes.c_float(loss_scale), *back[:5], _ptr(scale), *back[5:], _ptr(inlier))
+    result = result[:2] + (scale,) + result[2:]
     return result if inlier is None else result + (inlier,)
 
 
@@ -741,6 +763,28 @@ def fit_pose_views_robust(hand_model: torch.Tensor, window: torch.Tensor, cam_ro
         raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
     return fit_pose_views(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters,
                           _robust=(code, float(loss_scale), inlier), **kw)
+
+
+def fit_pose_views_scale(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                         init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                         limits: Optional[torch.Tensor] = None, init_scale: Optional[torch.Tensor] = None,
+                         scale_mode: int = UT_SCALE_FREE, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                         max_iters: int = 32, loss="squared", loss_scale: float = 3.0, *, inlier=False,
+                         scale: Optional[torch.Tensor] = None, **kw):
+    """ut_fit_pose_views_scale, fit_pose_views_robust with the hand's scale as a parameter: (joint_angles, wrist_xf, scale [n],
+    info [n,6]: rms px of the (robust) cost, largest raw reprojection distance px, iterations, status bits UT_FITS_*, scale
+    information, 0 - the rows pool_scale reads) and then, as for fit_pose_views_robust, the residual (residual=True or a buffer) and
+    the inliers (inlier=True or a buffer).  init_scale [n] or None (= 1); scale_mode UT_SCALE_FREE fits the scale, UT_SCALE_FIXED
+    keeps init_scale.  One camera cannot see the hand's size: a free fit on one view returns a scale that means nothing with an
+    information near 0 - fix the scale there.  Every other argument, **kw included (n, the strides, out, info, residual, engine),
+    as for fit_pose_views_robust; `scale` and `info` may be the caller's buffers."""
+    code = loss_code(loss)
+    if code != UT_LOSS_SQUARED and not (np.isfinite(loss_scale) and loss_scale > 0):
+        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
+    if scale_mode not in (UT_SCALE_FREE, UT_SCALE_FIXED):
+        raise ValueError(f"scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED, got {scale_mode!r}")
+    return fit_pose_views(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters,
+                          _robust=(code, float(loss_scale), inlier), _scale=(init_scale, int(scale_mode), scale), **kw)
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

@@ -8,6 +8,7 @@
 #include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_triangulate.h"
 #include "../../include/umetrack_hip_views.h"
+#include "../../include/umetrack_hip_views_scale.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -1532,14 +1533,25 @@ static_assert(UT_LOSS_SQUARED == ut::FITV_LOSS_SQUARED && UT_LOSS_HUBER == ut::F
               UT_LOSS_GEMAN_MCCLURE == ut::FITV_LOSS_GEMAN_MCCLURE, "umetrack_hip_robust.h and ut_kernels.h");
 
 namespace {
-// ut_fit_pose_views and ut_fit_pose_views_robust: one set of checks, one status path.  UT_LOSS_SQUARED without `inlier` launches
-// fit_views.hip's kernels (launch_fit_pose_views_robust hands it on).
+// What ut_fit_pose_views_scale adds to the arguments of the fits in the views; null for the other two entries.
+struct ViewsScale {
+  const float* init_scale;
+  int scale_mode;
+  float* scale;
+};
+
+// ut_fit_pose_views, ut_fit_pose_views_robust and ut_fit_pose_views_scale: one set of checks, one status path.  UT_LOSS_SQUARED
+// without `inlier` launches fit_views.hip's kernels (launch_fit_pose_views_robust hands it on); with `sc` every loss is
+// fit_views_scale.hip's and `info` is [n,6].
 int fit_pose_views(ut_handle h, const char* who, const float* hand_model, int n_models, const double* window, const float* weights,
                    const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind, const float* limits,
                    const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
                    const int64_t* mirror, float t_scale, int max_iters, int loss, float loss_scale, int n, float* joint_angles,
-                   int ja_stride, float* wrist_xf, int xf_stride, float* info, float* residual, float* inlier, void* stream) {
-  if (!window || !cam_rows || !table) return fail_as(h, who, "null argument");
+                   int ja_stride, float* wrist_xf, int xf_stride, float* info, float* residual, float* inlier, void* stream,
+                   const ViewsScale* sc = nullptr) {
+  if (!window || !cam_rows || !table || (sc && !sc->scale)) return fail_as(h, who, "null argument");
+  if (sc && sc->scale_mode != UT_SCALE_FREE && sc->scale_mode != UT_SCALE_FIXED)
+    return fail_as(h, who, "scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED");
   if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
     return fail_as(h, who, "table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
   if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS) return fail_as(h, who, "max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
@@ -1568,7 +1580,12 @@ int fit_pose_views(ut_handle h, const char* who, const float* hand_model, int n_
                                   window, weights, cam_rows, max_views, table, n_rows,
                                   table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE, info, residual, st.dev},
                                  loss, loss_scale, inlier};
-  HIPCHK(h, ut::launch_fit_pose_views_robust(a, s));
+  if (sc) {
+    const ut::FitViewsScaleArgs b{a, sc->init_scale, sc->scale_mode, sc->scale};
+    HIPCHK(h, ut::launch_fit_pose_views_scale(b, s));
+  } else {
+    HIPCHK(h, ut::launch_fit_pose_views_robust(a, s));
+  }
   return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, who) : UT_OK;
 }
 }  // namespace
@@ -1592,6 +1609,18 @@ int ut_fit_pose_views_robust(ut_handle h, const float* hand_model, int n_models,
   return fit_pose_views(h, "ut_fit_pose_views_robust", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
                         table_kind, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
                         loss, loss_scale, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, inlier, stream);
+}
+
+int ut_fit_pose_views_scale(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
+                            const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind,
+                            const float* limits, const float* init_scale, int scale_mode, const float* init_angles,
+                            int init_ja_stride, const float* init_wrist_xf, int init_xf_stride, const int64_t* mirror, float t_scale,
+                            int max_iters, int loss, float loss_scale, int n, float* joint_angles, int ja_stride, float* wrist_xf,
+                            int xf_stride, float* scale, float* info, float* residual, float* inlier, void* stream) {
+  const ViewsScale sc{init_scale, scale_mode, scale};
+  return fit_pose_views(h, "ut_fit_pose_views_scale", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
+                        table_kind, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
+                        loss, loss_scale, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, inlier, stream, &sc);
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

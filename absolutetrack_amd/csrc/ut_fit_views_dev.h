@@ -1,6 +1,7 @@
 // The cost of the pose fits on 2-D keypoints in camera views, written once: fit_views.hip (ut_fit_pose_views, the squared
 // reprojection cost) and fit_views_robust.hip (ut_fit_pose_views_robust, Huber and Geman-McClure) instantiate it in
-// ut_fit_dev.h's fit_pose().  fit_views.hip's header comment describes the reduction to 63 rows, the region and the registers.
+// ut_fit_dev.h's fit_pose(), and fit_views_scale.hip (ut_fit_pose_views_scale) derives the same cost on 27 parameters from it.
+// fit_views.hip's header comment describes the reduction to 63 rows, the region and the registers.
 //
 // The loss is a compile-time parameter.  The cost is sum_v sum_l w_vl c^2 rho(d_vl^2 / c^2), d the reprojection distance and c
 // a scale, both in px:
@@ -52,10 +53,12 @@ __device__ inline double fitv_rho(double d2, double c2, double inv_c2) {
   return d2 / (1.0 + s);
 }
 
-template <int KIND, int LOSS = FITV_LOSS_SQUARED>
+// REGION, PARAMS and STRIDE are the problem's P::Lds, P::NP and P::LD: fit_views_scale.hip derives the same cost on 27 parameters
+// in fit_scale.hip's region from it.  The defaults are what fit_views.hip and fit_views_robust.hip instantiate.
+template <int KIND, int LOSS = FITV_LOSS_SQUARED, class REGION = FitViewsLds, int PARAMS = 26, int STRIDE = 27>
 struct FitViewsCost {
-  using Lds = FitViewsLds;
-  static constexpr int NP = 26, LD = 27;
+  using Lds = REGION;
+  static constexpr int NP = PARAMS, LD = STRIDE;
   static constexpr bool PIVOT_FROM_START = true;
   static constexpr int ROW = KIND == PROJECT_FISHEYE62 ? 32 : 24;
   const FitViewsArgs& a;
@@ -170,6 +173,10 @@ struct FitViewsCost {
       s.worst = worst;
       fit_store_info(a.info + (size_t)i * 4, s, st.wsum, st.status);
     }
+    report_observations(S, i, lane, st);
+  }
+  // report's `residual` and `inlier`; needs the region's model to be the returned state's
+  __device__ inline void report_observations(Lds& S, int i, int lane, const FitState& st) {
     if (!a.residual && !inlier) return;
     if (!st.refused) {                 // S.p holds the last trial: the landmarks of the returned pose once more
       float unused;

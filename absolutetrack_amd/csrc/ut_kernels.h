@@ -458,6 +458,17 @@ hipError_t launch_fit_pose_scale(const FitScaleArgs& a, hipStream_t s);
 hipError_t launch_pool_scale(const float* scale, const float* info, int n_groups, int group_size, float* group,
                              float* pose_scale, hipStream_t s);
 
+// fit_views_scale.hip: the fit in the views, every loss, with ln(scale) as a 27th parameter (ut_fit_pose_views_scale).  The scale's
+// fields stand behind FitViewsRobustArgs as the loss's stand behind FitViewsArgs; robust.views.info is [n,6] here, the row layout
+// launch_pool_scale reads.
+struct FitViewsScaleArgs {
+  FitViewsRobustArgs robust;
+  const float* init_scale;              // [n] or null = 1
+  int scale_mode;                       // FITS_MODE_*
+  float* scale;                         // [n]
+};
+hipError_t launch_fit_pose_views_scale(const FitViewsScaleArgs& a, hipStream_t s);
+
 // Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
 //  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
 //           bone, unused slots weight 0 / bone 0

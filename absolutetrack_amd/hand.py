@@ -349,6 +349,79 @@ def calibrate_scale(hand_model: HandModel, landmarks: torch.Tensor, weights: Opt
     return ScaleCalibration(pooled, stats, model, s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(info, (6,)), s.back(pose_scale, ()))
 
 
+def _views_scale_inputs(hand_model: HandModel, window, cam_rows, table, init, init_scale, weights, mirror, limits, who):
+    """What fit_landmarks_views_scale and calibrate_scale_in_views hand to _native.fit_pose_views_scale, flattened to n poses on
+    the device: (staging, V, positional arguments, keyword arguments)."""
+    if init is None:
+        raise ValueError(f"init = (joint_angles, wrist_transforms) is required: {who} has no cold start")
+    if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
+        raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
+    v = window.shape[-3]
+    s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, limits, "limits")
+    if init_scale is not None:
+        init_scale = torch.as_tensor(init_scale).expand(s.lead)
+    args = (s.blob, s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32), table.to(s.dev, torch.float64),
+            *s.init(init))
+    return s, v, args, dict(weights=s.f32(weights, (v, 21)), limits=s.box, init_scale=s.f32(init_scale, ()), mirror=s.flags(mirror))
+
+
+def fit_landmarks_views_scale(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, init,
+                              init_scale=None, fixed: bool = False, weights: Optional[torch.Tensor] = None,
+                              mirror: Optional[torch.Tensor] = None, limits=None, max_iters: int = 32, with_residual: bool = False,
+                              loss="squared", loss_scale: float = 3.0, return_inliers: bool = False):
+    """fit_landmarks_views with the hand's scale as a parameter, on the HIP kernel csrc/fit_views_scale.hip (no CPU
+    implementation): the pose AND the scale whose landmarks, projected into the views, meet the detections.  Returns
+    (joint_angles [...,22], wrist_transforms [...,4,4], scale [...], info [...,6]: rms px of the (robust) cost, largest raw
+    reprojection distance px, iterations, status - FITS_CONVERGED | FITS_AT_MAX_ITERS | FITS_REFUSED | FITS_AT_BOUND -, scale
+    information (1 / variance of ln scale per px^2 of detection noise; 0 with fixed=True), 0) and then, as for
+    fit_landmarks_views, the reprojection distances (with_residual=True) and psi of every used detection (return_inliers=True).
+    init_scale [...] (or a number) is where the scale starts, 1 by default; fixed=True keeps it there, which fits the poses of a
+    calibrated model without building it.  One camera cannot see the hand's size: with one view a free fit returns a scale that
+    means nothing and an information near 0 - use fixed=True on one-view frames.  window, cam_rows, table, init (required),
+    weights, mirror, limits, loss and loss_scale as for fit_landmarks_views."""
+    s, v, args, kw = _views_scale_inputs(hand_model, window, cam_rows, table, init, init_scale, weights, mirror, limits,
+                                         "fit_landmarks_views_scale")
+    res = _native.fit_pose_views_scale(*args, scale_mode=_native.UT_SCALE_FIXED if fixed else _native.UT_SCALE_FREE, max_iters=max_iters,
+                                       loss=loss, loss_scale=loss_scale, residual=with_residual, inlier=return_inliers, **kw)
+    out = (s.back(res[0], (22,)), s.back(res[1], (4, 4)), s.back(res[2], ()), s.back(res[3], (6,)))
+    return out + tuple(s.back(r, (v, 21)) for r in res[4:])
+
+
+def calibrate_scale_in_views(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, init,
+                             init_scale=None, weights: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None,
+                             refit: bool = True, loss="squared", loss_scale: float = 3.0, max_iters: int = 32) -> ScaleCalibration:
+    """calibrate_scale on the detections themselves: one scale for each group of N poses of one person from window
+    [...,N,V,21,2], cam_rows [...,N,V] and table as for fit_landmarks_views (weights [...,N,V,21], mirror [...,N]) ->
+    ScaleCalibration, whose sigma and scatter are per px of detection noise.  init = (joint_angles [...,N,22], wrist_transforms
+    [...,N,4,4]) and init_scale [...,N] (or a number; 1 by default) are the start - the 3-D chain's free pass, e.g.
+    calibrate_scale(..., refit=False).  A free pass of fit_landmarks_views_scale over all poses, the information-weighted pool
+    over the N axis (ut_pool_scale: poses that did not converge, were refused or ended at a scale bound do not count, and a pose
+    one camera alone sees carries next to no information), and with refit=True a fixed pass at the pooled scale, warm-started
+    from the first.  Three launches, no host work in between.  loss, loss_scale: both passes'.  ValueError when a group has no
+    usable pose."""
+    if window.dim() < 4:
+        raise ValueError(f"window must be [...,N,V,21,2], got {tuple(window.shape)}")
+    s, _v, args, kw = _views_scale_inputs(hand_model, window, cam_rows, table, init, init_scale, weights, mirror, None,
+                                          "calibrate_scale_in_views")
+    group_lead, n_per = s.lead[:-1], s.lead[-1]
+    common = dict(max_iters=max_iters, loss=loss, loss_scale=loss_scale)
+    ja, xf, scale, info = _native.fit_pose_views_scale(*args, **common, **kw)
+    group, pose_scale = _native.pool_scale(scale, info, n_per)
+    if refit:
+        kw.update(init_scale=pose_scale)
+        ja, xf, pose_scale, info = _native.fit_pose_views_scale(*args[:4], ja, xf, scale_mode=_native.UT_SCALE_FIXED, **common, **kw)
+    else:
+        pose_scale = scale
+    stats = group.reshape(group_lead + (4,)).to(s.src_device)
+    if bool((stats[..., 3] == 0).any()):
+        raise ValueError("calibrate_scale_in_views: a group has no usable pose (none converged away from the scale bounds)")
+    pooled = stats[..., 0]
+    model = None
+    if group_lead == () and hand_model.joint_rest_positions.dim() == 2:
+        model = scaled_hand_model(hand_model, float(pooled))
+    return ScaleCalibration(pooled, stats, model, s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(info, (6,)), s.back(pose_scale, ()))
+
+
 _MESH_FIELDS = ("mesh_vertices", "mesh_triangles", "dense_bone_weights")
 _mesh_cache: list = []      # [(key, tensors kept alive, _native.Mesh)], most recent first
 

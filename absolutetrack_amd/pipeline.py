@@ -251,6 +251,37 @@ def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_p
                                          loss_scale=loss_scale, inlier=with_inliers, **kw)
 
 
+def calibrate_scale_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
+                             init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, init_scale: Optional[torch.Tensor] = None,
+                             group_size: Optional[int] = None, weights: Optional[torch.Tensor] = None,
+                             mirror: Optional[torch.Tensor] = None, limits: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                             max_iters: int = 32, refit: bool = True, loss="squared", loss_scale: float = 3.0,
+                             engine: Optional[_native.HipEngine] = None):
+    """Batched hand.calibrate_scale_in_views, device resident, next to fit_keypoints_in_views: the scale of each group of
+    group_size consecutive hand-samples (one person's; default: all n as one group) from their window keypoints in the cameras
+    that see them.  A free ut_fit_pose_views_scale pass, ut_pool_scale, and with refit=True a fixed pass at the pooled scale
+    warm-started from the first: three launches, nothing read back, capturable with an engine that runs deferred checks.
+    hand_model, window, cam_params, src_row, weights, mirror, limits, t_scale, loss and loss_scale as for fit_keypoints_in_views;
+    init_angles [n,22] / init_wrist_xf [n,4,4] / init_scale [n] or None (= 1): the start, e.g. _native.fit_pose_scale on
+    triangulate_keypoints' points.  Returns (group f32 [n / group_size,4]: pooled scale, sigma of ln scale per px of detection
+    noise, scatter, poses used - 1, +inf, 0, 0 for a group without a usable pose -, joint_angles, wrist_xf, pose_scale f32 [n],
+    info f32 [n,6]): the poses of the fixed pass at their group's scale, or with refit=False those of the free pass with their
+    own scales.  A hand-sample one camera alone sees carries next to no scale information and does not move its group's scale."""
+    n = window.shape[0]
+    group_size = n if group_size is None else int(group_size)
+    kw = dict(weights=weights, limits=limits, mirror=mirror, t_scale=t_scale, max_iters=max_iters, loss=loss, loss_scale=loss_scale,
+              engine=engine)
+    ja, xf, scale, info = _native.fit_pose_views_scale(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf,
+                                                       init_scale=init_scale, **kw)
+    group, pose_scale = _native.pool_scale(scale, info, group_size)
+    if refit:
+        ja, xf, pose_scale, info = _native.fit_pose_views_scale(hand_model, window, src_row, cam_params, ja, xf, init_scale=pose_scale,
+                                                                scale_mode=_native.UT_SCALE_FIXED, **kw)
+    else:
+        pose_scale = scale
+    return group, ja, xf, pose_scale, info
+
+
 def view_rows(src_index: torch.Tensor, sample_range: torch.Tensor, max_views: int = MAX_VIEW_NUM) -> torch.Tensor:
     """[S,max_views] i32: the entries of a per-crop tensor (FrameBatch.src_index, or arange(n_crops) for the crop cameras
     themselves) that belong to each sample's views, -1 where the sample has fewer - the cam_rows of project_keypoints."""

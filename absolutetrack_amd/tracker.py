@@ -19,7 +19,7 @@ from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
 from .hand import FIT_CONVERGED, fit_landmarks, fit_landmarks_info, fit_landmarks_views
-from .hand import ScaleCalibration, calibrate_scale
+from .hand import ScaleCalibration, calibrate_scale, calibrate_scale_in_views
 from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
 
@@ -339,12 +339,17 @@ def calibrate_hand_model_from_keypoints(hand_model: HandModel, keypoints: np.nda
 
 
 def calibrate_hand_model_from_window_keypoints(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray,
-                                               hand_idx: int, weights: Optional[np.ndarray] = None) -> ScaleCalibration:
+                                               hand_idx: int, weights: Optional[np.ndarray] = None, refine_in_views: bool = False,
+                                               loss="squared", loss_scale: float = 3.0) -> ScaleCalibration:
     """From 2-D detections to a calibrated model: window_keypoints [n_frames, n_cams, 21, 2] of one hand in the cameras,
     weights [n_frames, n_cams, 21] as for triangulate_landmarks -> hand.ScaleCalibration (its hand_model is the calibrated
     model, its poses are refitted at the calibrated scale).  One ut_triangulate_points launch for all frames, each
     landmark weighted as in hand_pose_from_window_keypoints - (the frame's smallest finite sigma / its sigma)^2 -, then
-    hand.calibrate_scale over the frames."""
+    hand.calibrate_scale over the frames.  refine_in_views=True: that chain's free pass - its poses and per-pose scales - is
+    the start of hand.calibrate_scale_in_views on ALL given detections (free pass in the views -> pool -> fixed pass in the
+    views), which roughly halves the scale's error on the same detections and keeps the frames the 3-D chain cannot use; sigma
+    and scatter of the result are then per px.  loss, loss_scale: the passes' in the views, as for refine_hand_pose_in_views; not
+    read without refine_in_views.  The cameras must see the hand from two places: one camera cannot see its size."""
     table = _native_camera_table(cameras, "calibrate_hand_model_from_window_keypoints")
     win = np.ascontiguousarray(window_keypoints, np.float64)
     if win.ndim != 4 or win.shape[1:] != (len(cameras), 21, 2):
@@ -363,7 +368,14 @@ def calibrate_hand_model_from_window_keypoints(hand_model: HandModel, cameras: L
     best = torch.where(ok, sigma, torch.full_like(sigma, float("inf"))).amin(1, keepdim=True)
     lw = torch.where(ok, (best / torch.where(ok, sigma, torch.ones_like(sigma))) ** 2, torch.zeros_like(sigma)).float()
     mirror = torch.full((n,), 1 if hand_idx == RIGHT_HAND_INDEX else 0, dtype=torch.int64, device=dev)
-    cal = calibrate_scale(hand_model, pts.float(), lw, mirror)
+    if refine_in_views:
+        start = calibrate_scale(hand_model, pts.float(), lw, mirror, refit=False)
+        cal = calibrate_scale_in_views(hand_model, torch.from_numpy(win).to(dev), rows, torch.from_numpy(table).to(dev),
+                                       (start.joint_angles, start.wrist_transforms), start.pose_scale,
+                                       weights=None if weights is None else torch.from_numpy(weights).to(dev), mirror=mirror,
+                                       loss=loss, loss_scale=loss_scale)
+    else:
+        cal = calibrate_scale(hand_model, pts.float(), lw, mirror)
     return ScaleCalibration(*(t.cpu() if isinstance(t, torch.Tensor) else t for t in cal))
 
 
