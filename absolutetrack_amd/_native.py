@@ -1,6 +1,6 @@
 """ctypes binding of libumetrack_hip.so (include/umetrack_hip.h and its extension headers include/umetrack_hip_fit.h,
 include/umetrack_hip_triangulate.h, include/umetrack_hip_scale.h, include/umetrack_hip_info.h, include/umetrack_hip_views.h,
-include/umetrack_hip_robust.h and include/umetrack_hip_views_scale.h).
+include/umetrack_hip_robust.h, include/umetrack_hip_views_scale.h and include/umetrack_hip_uncertainty.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, every entry point raises.  PyTorch-ROCm is used for device memory and
@@ -115,6 +115,12 @@ _VIEWS_SCALE_PROTOTYPES = {
                                        _f32, _i32, _i32, _f32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 VIEWS_SCALE_EXPORTS = tuple(_VIEWS_SCALE_PROTOTYPES)
+# The entry of include/umetrack_hip_uncertainty.h, in a table of its own like its header (tests/test_uncertainty_host.py pins it).
+_UNCERTAINTY_PROTOTYPES = {
+    "ut_pose_information_views": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _f32,
+                                         _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+UNCERTAINTY_EXPORTS = tuple(_UNCERTAINTY_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -140,7 +146,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
                                       **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES, **_ROBUST_PROTOTYPES,
-                                      **_VIEWS_SCALE_PROTOTYPES}.items():
+                                      **_VIEWS_SCALE_PROTOTYPES, **_UNCERTAINTY_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -785,6 +791,71 @@ def fit_pose_views_scale(hand_model: torch.Tensor, window: torch.Tensor, cam_row
         raise ValueError(f"scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED, got {scale_mode!r}")
     return fit_pose_views(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters,
                           _robust=(code, float(loss_scale), inlier), _scale=(init_scale, int(scale_mode), scale), **kw)
+
+
+UT_COV_OK, UT_COV_SINGULAR, UT_COV_REFUSED = 1, 2, 4
+UT_COV_MIN_PIVOT = 2.0 ** -16
+
+
+def pose_information_views(hand_model: torch.Tensor, joint_angles: torch.Tensor, wrist_xf: torch.Tensor, window: torch.Tensor,
+                           cam_rows: torch.Tensor, table: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                           angle_sigma: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                           loss="squared", loss_scale: float = 3.0, *, n: Optional[int] = None, ja_stride: int = 22,
+                           xf_stride: int = 16, pose_info=True, pivot=True, param_sigma=True, landmark_cov=True, info=True,
+                           engine: Optional["HipEngine"] = None):
+    """ut_pose_information_views: how well the pose (joint_angles [n,22], wrist_xf [n,4,4]) is known under the cost of
+    fit_pose_views_robust on these detections - window, cam_rows, table, weights (informations, px^-2), mirror, t_scale, loss and
+    loss_scale exactly as there.  Nothing is fitted.  Returns (pose_info f32 [n,351]: the lower triangle, row-major, of H = sum w
+    psi J^T J + the prior on the solver's 26 parameters; pivot [n,3] the rotation increment turns about; param_sigma [n,26] =
+    sqrt(diag H^-1); landmark_cov [n,21,6]: (xx, yx, yy, zx, zy, zz) of G_l H^-1 G_l^T; info [n,4]: rms of the cost at the pose,
+    the largest landmark sigma, the smallest pivot of the unit-diagonal factor, status UT_COV_OK | UT_COV_SINGULAR (sigmas and
+    covariances +inf) | UT_COV_REFUSED (everything 0)).  Each output: True = a fresh tensor, False = left out (None comes back;
+    not all five), or a preallocated contiguous f32 tensor.  angle_sigma f32 [1|n,20] (one row per model row) or None: the
+    sigma in rad of a Gaussian prior on each joint angle.  With n given, joint_angles / wrist_xf are fp32 views read in place with
+    the strides given in floats - pose records, or a fit's strided outputs.  A cam_rows entry outside [-1, R) raises IndexError
+    and writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks."""
+    if joint_angles is None or wrist_xf is None:
+        raise ValueError("joint_angles and wrist_xf are required")
+    if window.dim() != 4 or tuple(window.shape[2:]) != (21, 2) or window.dtype != torch.float64:
+        raise ValueError(f"window must be f64 [n,V,21,2], got {window.dtype} {tuple(window.shape)}")
+    nw, v = window.shape[:2]
+    if not 1 <= v <= TRI_MAX_VIEWS:
+        raise ValueError(f"window [n,V,21,2] needs 1 <= V <= {TRI_MAX_VIEWS}, got V = {v}")
+    if table.dim() != 2 or table.shape[1] not in (24, 32) or table.shape[0] < 1 or table.dtype != torch.float64:
+        raise ValueError(f"table must be f64 [R,32] source cameras or [R,24] crop cameras, got {table.dtype} {tuple(table.shape)}")
+    if cam_rows.dtype != torch.int32 or tuple(cam_rows.shape) != (nw, v):
+        raise ValueError(f"cam_rows must be i32 [{nw},{v}], got {cam_rows.dtype} {tuple(cam_rows.shape)}")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (nw, v, 21)):
+        raise ValueError(f"weights must be f32 [{nw},{v},21], got {weights.dtype} {tuple(weights.shape)}")
+    code = loss_code(loss)
+    if code != UT_LOSS_SQUARED and not (np.isfinite(loss_scale) and loss_scale > 0):
+        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
+    kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
+    d = _hip_device(window, "pose_information_views")
+    window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
+    if weights is not None:
+        weights = _need(weights, torch.float32, d, "weights")
+    hand_model, joint_angles, wrist_xf, mirror, n = _fk_args(d, hand_model, joint_angles, wrist_xf, mirror, n)
+    if n != nw:
+        raise ValueError(f"{n} poses for {nw} poses' windows")
+    if angle_sigma is not None:
+        angle_sigma = _need(angle_sigma, torch.float32, d, "angle_sigma").reshape(-1, 20)
+        if angle_sigma.shape[0] != hand_model.shape[0]:
+            raise ValueError(f"angle_sigma has {angle_sigma.shape[0]} rows for {hand_model.shape[0]} model rows")
+    outs = []
+    for name, want, shape in (("pose_info", pose_info, (n, 351)), ("pivot", pivot, (n, 3)), ("param_sigma", param_sigma, (n, 26)),
+                              ("landmark_cov", landmark_cov, (n, 21, 6)), ("info", info, (n, 4))):
+        if want is True or isinstance(want, torch.Tensor):
+            outs.append(_out(None if want is True else want, shape, torch.float32, d, name))
+        else:
+            outs.append(None)
+    if all(o is None for o in outs):
+        raise ValueError("at least one output is needed")
+    h = engine._h if engine is not None else None
+    _fit_call("ut_pose_information_views", d, h, _ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v,
+              _ptr(table), table.shape[0], kind, _ptr(angle_sigma), _ptr(joint_angles), ja_stride, _ptr(wrist_xf), xf_stride,
+              _ptr(mirror), ctypes.c_float(t_scale), code, ctypes.c_float(loss_scale), n, *[_ptr(o) for o in outs])
+    return tuple(outs)
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

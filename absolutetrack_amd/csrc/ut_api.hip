@@ -7,6 +7,7 @@
 #include "../../include/umetrack_hip_robust.h"
 #include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_triangulate.h"
+#include "../../include/umetrack_hip_uncertainty.h"
 #include "../../include/umetrack_hip_views.h"
 #include "../../include/umetrack_hip_views_scale.h"
 
@@ -1539,17 +1540,25 @@ struct ViewsScale {
   int scale_mode;
   float* scale;
 };
+// What ut_pose_information_views has where the fits have their outputs; null for the fits.
+struct ViewsCov {
+  const float* angle_sigma;
+  float *pose_info, *pivot, *param_sigma, *landmark_cov, *info;
+};
 
-// ut_fit_pose_views, ut_fit_pose_views_robust and ut_fit_pose_views_scale: one set of checks, one status path.  UT_LOSS_SQUARED
-// without `inlier` launches fit_views.hip's kernels (launch_fit_pose_views_robust hands it on); with `sc` every loss is
-// fit_views_scale.hip's and `info` is [n,6].
+// ut_fit_pose_views, ut_fit_pose_views_robust, ut_fit_pose_views_scale and ut_pose_information_views: one set of checks, one
+// status path.  UT_LOSS_SQUARED without `inlier` launches fit_views.hip's kernels (launch_fit_pose_views_robust hands it on); with
+// `sc` every loss is fit_views_scale.hip's and `info` is [n,6]; with `cov` the init pointers are the pose, nothing is fitted and
+// pose_info_views.hip's kernels write cov's outputs.
 int fit_pose_views(ut_handle h, const char* who, const float* hand_model, int n_models, const double* window, const float* weights,
                    const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind, const float* limits,
                    const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
                    const int64_t* mirror, float t_scale, int max_iters, int loss, float loss_scale, int n, float* joint_angles,
                    int ja_stride, float* wrist_xf, int xf_stride, float* info, float* residual, float* inlier, void* stream,
-                   const ViewsScale* sc = nullptr) {
+                   const ViewsScale* sc = nullptr, const ViewsCov* cov = nullptr) {
   if (!window || !cam_rows || !table || (sc && !sc->scale)) return fail_as(h, who, "null argument");
+  if (cov && !cov->pose_info && !cov->pivot && !cov->param_sigma && !cov->landmark_cov && !cov->info)
+    return fail_as(h, who, "all five outputs are NULL");
   if (sc && sc->scale_mode != UT_SCALE_FREE && sc->scale_mode != UT_SCALE_FIXED)
     return fail_as(h, who, "scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED");
   if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
@@ -1580,7 +1589,10 @@ int fit_pose_views(ut_handle h, const char* who, const float* hand_model, int n_
                                   window, weights, cam_rows, max_views, table, n_rows,
                                   table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE, info, residual, st.dev},
                                  loss, loss_scale, inlier};
-  if (sc) {
+  if (cov) {
+    const ut::PoseInfoViewsArgs b{a, cov->angle_sigma, cov->pose_info, cov->pivot, cov->param_sigma, cov->landmark_cov, cov->info};
+    HIPCHK(h, ut::launch_pose_information_views(b, s));
+  } else if (sc) {
     const ut::FitViewsScaleArgs b{a, sc->init_scale, sc->scale_mode, sc->scale};
     HIPCHK(h, ut::launch_fit_pose_views_scale(b, s));
   } else {
@@ -1621,6 +1633,23 @@ int ut_fit_pose_views_scale(ut_handle h, const float* hand_model, int n_models, 
   return fit_pose_views(h, "ut_fit_pose_views_scale", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
                         table_kind, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
                         loss, loss_scale, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, inlier, stream, &sc);
+}
+
+static_assert(UT_COV_OK == ut::COV_OK && UT_COV_SINGULAR == ut::COV_SINGULAR && UT_COV_REFUSED == ut::COV_REFUSED &&
+              UT_COV_REFUSED == UT_FIT_REFUSED && UT_COV_MIN_PIVOT == ut::COV_MIN_PIVOT, "umetrack_hip_uncertainty.h and ut_kernels.h");
+
+int ut_pose_information_views(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
+                              const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind,
+                              const float* angle_sigma, const float* joint_angles, int ja_stride, const float* wrist_xf,
+                              int xf_stride, const int64_t* mirror, float t_scale, int loss, float loss_scale, int n,
+                              float* pose_info, float* pivot, float* param_sigma, float* landmark_cov, float* info,
+                              void* stream) {
+  // the pose is the fit's start, and stands for the fit's outputs in the shared checks: nothing is written through it
+  const ViewsCov cov{angle_sigma, pose_info, pivot, param_sigma, landmark_cov, info};
+  return fit_pose_views(h, "ut_pose_information_views", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
+                        table_kind, nullptr, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale, 1, loss, loss_scale, n,
+                        const_cast<float*>(joint_angles), ja_stride, const_cast<float*>(wrist_xf), xf_stride, nullptr, nullptr,
+                        nullptr, stream, nullptr, &cov);
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

@@ -264,10 +264,10 @@ __device__ inline void fit_cold_start(Lds& S, int lane, const FitState& st) {
 
 // ---- (1)
 
-// J into S.jl - per used landmark the joint, wrist and residual columns scaled by P::row_scale, then P::finish_rows - and the
-// lower triangle of [J r]^T [J r] into S.a.  Needs S.prefix / frame / p of the accepted state.
+// J into S.jl - per used landmark the joint, wrist and residual columns scaled by P::row_scale, then P::finish_rows.  Needs
+// S.prefix / frame / p of the accepted state.  The first half of fit_linearise, on its own for a caller that wants the rows alone.
 template <class P>
-__device__ inline void fit_linearise(P& prob, typename P::Lds& S, int lane, const FitState& st) {
+__device__ inline void fit_rows(P& prob, typename P::Lds& S, int lane, const FitState& st) {
   constexpr int NP = P::NP, LD = P::LD;
   for (int e = lane; e < 63 * LD; e += 64) S.jl[e] = 0.f;
   if (lane < 20) joint_axis_in_world(S.prefix[lane], S.hm + 3 * lane, S.hm + 66 + 3 * lane, S.omega[lane], S.cw[lane]);
@@ -313,6 +313,13 @@ __device__ inline void fit_linearise(P& prob, typename P::Lds& S, int lane, cons
     prob.finish_rows(S, lane, row, sw, px, py, pz);
   }
   wave_sync();
+}
+
+// fit_rows, and the lower triangle of [J r]^T [J r] into S.a.
+template <class P>
+__device__ inline void fit_linearise(P& prob, typename P::Lds& S, int lane, const FitState& st) {
+  constexpr int NP = P::NP, LD = P::LD;
+  fit_rows(prob, S, lane, st);
   // (NP + 1) (NP + 2) / 2 entries (i, j <= i): 378 are 6 per lane, 406 are 7
   for (int e = lane; e < (NP + 1) * (NP + 2) / 2; e += 64) {
     int i = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);

@@ -469,6 +469,22 @@ struct FitViewsScaleArgs {
 };
 hipError_t launch_fit_pose_views_scale(const FitViewsScaleArgs& a, hipStream_t s);
 
+// pose_info_views.hip: the information of a pose under the cost of the fits in the views (ut_pose_information_views).  The pose
+// stands where the fit has its start (robust.views.pose.init_ja / init_xf); the pose outputs, limits, max_iters, views.info and
+// views.residual are not read.  Pointers as ut_pose_information_views documents them; the constants are public as UT_COV_*.
+enum : int { COV_OK = 1, COV_SINGULAR = 2, COV_REFUSED = FIT_REFUSED };
+constexpr float COV_MIN_PIVOT = 0x1p-16f;
+struct PoseInfoViewsArgs {
+  FitViewsRobustArgs robust;
+  const float* angle_sigma;             // [n_models,20] or null
+  float* pose_info;                     // [n,351] or null
+  float* pivot;                         // [n,3] or null
+  float* param_sigma;                   // [n,26] or null
+  float* landmark_cov;                  // [n,21,6] or null
+  float* info;                          // [n,4] or null
+};
+hipError_t launch_pose_information_views(const PoseInfoViewsArgs& a, hipStream_t s);
+
 // Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
 //  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
 //           bone, unused slots weight 0 / bone 0

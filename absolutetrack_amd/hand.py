@@ -278,6 +278,82 @@ def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: t
     return out + tuple(s.back(r, (v, 21)) for r in res[3:])
 
 
+COV_OK, COV_SINGULAR, COV_REFUSED = _native.UT_COV_OK, _native.UT_COV_SINGULAR, _native.UT_COV_REFUSED
+
+
+class PoseUncertainty(NamedTuple):
+    """How well a pose is known (pose_uncertainty_views).  The 26 parameters are the solver's: 20 joint angle increments (rad),
+    a rotation increment about `pivot` in world axes (rad), a translation in the landmarks' units."""
+    pose_info: torch.Tensor        # [...,26,26] H = sum w psi J^T J (+ the prior): the information matrix of the pose
+    pivot: torch.Tensor            # [...,3] the point the rotation increment turns about
+    param_sigma: torch.Tensor      # [...,26] sqrt(diag H^-1); +inf when singular
+    landmark_cov: torch.Tensor     # [...,21,3,3] covariance of every landmark in the world; +inf on the diagonal when singular
+    landmark_sigma: torch.Tensor   # [...,21] sqrt(trace landmark_cov)
+    status: torch.Tensor           # [...] i64: COV_OK, COV_SINGULAR or COV_REFUSED (everything 0)
+
+
+_TRIL = np.tril_indices(26)
+_COV6 = ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))
+
+
+def unpack_uncertainty(pose_info, pivot, param_sigma, landmark_cov, info, lead=None, device=None) -> PoseUncertainty:
+    """The five packed outputs of _native.pose_information_views ([n,351], [n,3], [n,26], [n,21,6], [n,4]) as a PoseUncertainty
+    with leading dims `lead` (default (n,)) on `device` (default: where they are)."""
+    n = pose_info.shape[0]
+    lead = (n,) if lead is None else tuple(lead)
+    h = pose_info.new_zeros(n, 26, 26)
+    h[:, _TRIL[0], _TRIL[1]] = pose_info
+    h[:, _TRIL[1], _TRIL[0]] = pose_info
+    cov = landmark_cov.new_zeros(n, 21, 3, 3)
+    for k, (a, b) in enumerate(_COV6):
+        cov[:, :, a, b] = landmark_cov[:, :, k]
+        cov[:, :, b, a] = landmark_cov[:, :, k]
+    sigma = torch.sqrt(landmark_cov[:, :, 0] + landmark_cov[:, :, 2] + landmark_cov[:, :, 5])
+    out = (h.reshape(lead + (26, 26)), pivot.reshape(lead + (3,)), param_sigma.reshape(lead + (26,)), cov.reshape(lead + (21, 3, 3)),
+           sigma.reshape(lead + (21,)), info[:, 3].to(torch.int64).reshape(lead))
+    return PoseUncertainty(*(t if device is None else t.to(device) for t in out))
+
+
+def angle_sigma_from_limits(hand_model: HandModel) -> torch.Tensor:
+    """[...,20] (hi - lo) / sqrt(12) of hand_model.joint_limits: the sigma of a uniform law over each angle's box, what
+    pose_uncertainty_views takes as `angle_sigma` when nothing better is known about an angle."""
+    if hand_model.joint_limits is None:
+        raise ValueError("angle_sigma_from_limits needs hand_model.joint_limits")
+    box = hand_model.joint_limits[..., :20, :].to(torch.float32)
+    return (box[..., 1] - box[..., 0]) / float(np.sqrt(12.0))
+
+
+def pose_uncertainty_views(hand_model: HandModel, joint_angles: torch.Tensor, wrist_transforms: torch.Tensor, window: torch.Tensor,
+                           cam_rows: torch.Tensor, table: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                           angle_sigma: Optional[torch.Tensor] = None, loss="squared", loss_scale: float = 3.0,
+                           mirror: Optional[torch.Tensor] = None) -> PoseUncertainty:
+    """How well the pose (joint_angles [...,22], wrist_transforms [...,4,4]) is known from the detections fit_landmarks_views
+    fitted it to, on the HIP kernel csrc/pose_info_views.hip (no CPU implementation): window, cam_rows, table, weights, loss,
+    loss_scale and mirror as there, evaluated at the pose as given - one launch, nothing is fitted.  weights are informations:
+    with 1 / sigma^2 of each detection in px^-2 the result is absolute, with None it is per px^2 of detection noise.
+    angle_sigma [...,20] or [20] rad: a Gaussian prior on each joint angle (angle_sigma_from_limits), the whole answer for an
+    angle no used detection depends on, negligible for the others; without it such a pose is COV_SINGULAR and its sigmas are
+    +inf.  The covariance is the Gauss-Newton one of the unconstrained linearisation (no second-order term; under a robust loss
+    that of the reweighted problem): it means something at a minimum of the cost - at the pose a fit returned.  A hand that
+    one camera sees comes back several times less certain along that camera's rays than across them."""
+    if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
+        raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
+    v = window.shape[-3]
+    s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, False)
+    if angle_sigma is not None:
+        rows = s.blob.shape[0]
+        angle_sigma = torch.as_tensor(angle_sigma, dtype=torch.float32)      # one row per model row, as the kernel reads it
+        angle_sigma = angle_sigma.reshape(1, 20) if angle_sigma.numel() == 20 and rows == 1 else angle_sigma.expand(s.lead + (20,)).reshape(s.n, 20)
+        if angle_sigma.shape[0] != rows:
+            raise ValueError("angle_sigma must be [20] with an unbatched hand_model")
+        angle_sigma = angle_sigma.to(s.dev).contiguous()
+    outs = _native.pose_information_views(s.blob, s.f32(joint_angles, (22,)), s.f32(wrist_transforms, (4, 4)),
+                                          s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32),
+                                          table.to(s.dev, torch.float64), s.f32(weights, (v, 21)), angle_sigma, s.flags(mirror),
+                                          loss=loss, loss_scale=loss_scale)
+    return unpack_uncertainty(*outs, lead=s.lead, device=s.src_device)
+
+
 FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FITS_CONVERGED, _native.UT_FITS_AT_MAX_ITERS,
                                                                   _native.UT_FITS_REFUSED, _native.UT_FITS_AT_BOUND)
 

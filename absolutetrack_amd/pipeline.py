@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native, arch, geometry
-from .hand import HandModel, device_blob, device_mesh
+from .hand import HandModel, device_blob, device_mesh, unpack_uncertainty
 from .tracker import (HandTrackerOpts, MAX_VIEW_NUM, SingleHandPose, gen_crop_cameras_from_pose,
                       network_camera_inputs)
 
@@ -232,7 +232,8 @@ def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_p
                            init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
                            mirror: Optional[torch.Tensor] = None, limits: Optional[torch.Tensor] = None, t_scale: float = 1.0,
                            max_iters: int = 32, with_residual: bool = False, engine: Optional[_native.HipEngine] = None,
-                           loss="squared", loss_scale: float = 3.0, with_inliers: bool = False, **strided):
+                           loss="squared", loss_scale: float = 3.0, with_inliers: bool = False, with_uncertainty: bool = False,
+                           angle_sigma: Optional[torch.Tensor] = None, **strided):
     """Batched tracker.refine_hand_pose_in_views over frames and hands: the poses of n hand-samples whose landmarks meet their
     window keypoints in the cameras that see them, ONE ut_fit_pose_views launch.  hand_model f32 [1|n,321] packed models
     (hand.device_blob); window f64 [n,V,21,2] px on the device (what project_keypoints returns, or detections); cam_params f64
@@ -243,12 +244,22 @@ def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_p
     _native.fit_pose_views - poses inside HotPath records, read and written in place.  Returns (joint_angles, wrist_xf, info
     f32 [n,4]) and, with with_residual=True, residual f32 [n,V,21].  loss "huber" / "geman_mcclure" with loss_scale px: ONE
     ut_fit_pose_views_robust launch on the robust cost instead, for detections some of which are grossly wrong; with_inliers=True
-    appends psi f32 [n,V,21] of every used detection at the returned pose (1 an inlier, towards 0 an outlier)."""
+    appends psi f32 [n,V,21] of every used detection at the returned pose (1 an inlier, towards 0 an outlier).
+    with_uncertainty=True: one ut_pose_information_views launch more, at the returned poses with the same loss, weights and views
+    (and angle_sigma f32 [1|n,20] or None, the prior of _native.pose_information_views); its hand.PoseUncertainty is the last
+    item.  Off, the result is what it was without the keyword."""
     kw = dict(weights=weights, limits=limits, mirror=mirror, t_scale=t_scale, max_iters=max_iters, residual=with_residual, engine=engine, **strided)
     if _native.loss_code(loss) == _native.UT_LOSS_SQUARED and not with_inliers:
-        return _native.fit_pose_views(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, **kw)
-    return _native.fit_pose_views_robust(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, loss=loss,
-                                         loss_scale=loss_scale, inlier=with_inliers, **kw)
+        res = _native.fit_pose_views(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, **kw)
+    else:
+        res = _native.fit_pose_views_robust(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, loss=loss,
+                                            loss_scale=loss_scale, inlier=with_inliers, **kw)
+    if not with_uncertainty:
+        return res
+    outs = _native.pose_information_views(hand_model, res[0], res[1], window, src_row, cam_params, weights=weights, angle_sigma=angle_sigma,
+                                          mirror=mirror, t_scale=t_scale, loss=loss, loss_scale=loss_scale, engine=engine,
+                                          **{k: strided[k] for k in ("n", "ja_stride", "xf_stride") if k in strided})
+    return res + (unpack_uncertainty(*outs),)
 
 
 def calibrate_scale_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,

@@ -18,7 +18,7 @@ import torch
 from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
-from .hand import FIT_CONVERGED, fit_landmarks, fit_landmarks_info, fit_landmarks_views
+from .hand import FIT_CONVERGED, fit_landmarks, fit_landmarks_info, fit_landmarks_views, pose_uncertainty_views
 from .hand import ScaleCalibration, calibrate_scale, calibrate_scale_in_views
 from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
@@ -234,8 +234,8 @@ def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weight
 def hand_pose_from_window_keypoints(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray,
                                     hand_idx: int, weights: Optional[np.ndarray] = None,
                                     init: Optional[SingleHandPose] = None, use_information: bool = False,
-                                    refine_in_views: bool = False, loss="squared", loss_scale: float = 3.0
-                                    ) -> Tuple[SingleHandPose, np.ndarray]:
+                                    refine_in_views: bool = False, loss="squared", loss_scale: float = 3.0,
+                                    return_uncertainty: bool = False) -> tuple:
     """From 2-D detections to a pose: window_keypoints [n_cams,21,2] of one hand in the cameras -> (SingleHandPose, the
     triangulation's info [21,4]).  triangulate_landmarks first, then the pose fit of hand_pose_from_landmarks with each
     landmark weighted by (smallest finite sigma / its sigma)^2, in (0, 1]: a landmark the views pin down badly counts
@@ -246,15 +246,43 @@ def hand_pose_from_window_keypoints(hand_model: HandModel, cameras: List[CameraM
     which a narrow baseline measures badly, is fixed by the hand's known size.  refine_in_views=True: the pose of either
     chain is then refined on ALL given detections by refine_hand_pose_in_views - the landmarks that one camera alone sees, which
     the triangulation refuses, included; the default leaves the chain's result as it is.  loss, loss_scale: the
-    refinement's, as for refine_hand_pose_in_views; not read without it."""
+    refinement's, as for refine_hand_pose_in_views; not read without it.  return_uncertainty=True: a third item, the
+    hand.PoseUncertainty of the returned pose on ALL given detections under loss / loss_scale (hand_pose_uncertainty_in_views)."""
     pose, info = _chain_pose_from_window_keypoints(hand_model, cameras, window_keypoints, hand_idx, weights, init, use_information)
     if refine_in_views:
         pose = refine_hand_pose_in_views(hand_model, cameras, window_keypoints, hand_idx, pose, weights, loss=loss, loss_scale=loss_scale)[0]
+    if return_uncertainty:
+        return pose, info, hand_pose_uncertainty_in_views(hand_model, cameras, window_keypoints, hand_idx, pose, weights, loss, loss_scale)
     return pose, info
 
 
+def hand_pose_uncertainty_in_views(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray, hand_idx: int,
+                                   pose: SingleHandPose, weights: Optional[np.ndarray] = None, loss="squared", loss_scale: float = 3.0,
+                                   angle_sigma=None):
+    """How well `pose` is known from the detections window_keypoints [n_cams,21,2] of one hand in the cameras: the
+    hand.PoseUncertainty of hand.pose_uncertainty_views (numpy fields), one ut_pose_information_views launch.  weights [n_cams,21]
+    are informations (1 / sigma^2 in px^-2 makes the result absolute; None = per px^2 of detection noise), loss / loss_scale those
+    of the fit that produced the pose, angle_sigma [20] rad an optional prior on the joint angles.  Cameras as for
+    triangulate_landmarks."""
+    table = _native_camera_table(cameras, "hand_pose_uncertainty_in_views")
+    win = np.ascontiguousarray(window_keypoints, np.float64)
+    if win.shape != (len(cameras), 21, 2):
+        raise ValueError(f"window_keypoints must be [{len(cameras)},21,2], got {win.shape}")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float32)
+        if weights.shape != win.shape[:2]:
+            raise ValueError(f"weights must be {win.shape[:2]}, got {weights.shape}")
+    unc = pose_uncertainty_views(
+        hand_model, torch.from_numpy(np.asarray(pose.joint_angles, np.float32)), torch.from_numpy(np.asarray(pose.wrist_xform, np.float32)),
+        torch.from_numpy(win), torch.arange(len(cameras), dtype=torch.int32), torch.from_numpy(table),
+        weights=None if weights is None else torch.from_numpy(weights), angle_sigma=angle_sigma, loss=loss, loss_scale=loss_scale,
+        mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
+    return type(unc)(*(t.numpy() for t in unc))
+
+
 def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray, hand_idx: int,
-                              init: SingleHandPose, weights: Optional[np.ndarray] = None, loss="squared", loss_scale: float = 3.0):
+                              init: SingleHandPose, weights: Optional[np.ndarray] = None, loss="squared", loss_scale: float = 3.0,
+                              return_uncertainty: bool = False):
     """The pose that meets the detections themselves: window_keypoints [n_cams,21,2] of one hand in the cameras and a start
     `init` (the previous frame's pose, or hand_pose_from_window_keypoints') -> (SingleHandPose, info [4]: rms reprojection
     residual px, largest reprojection distance px, iterations, status bits FIT_*, residual [n_cams,21]: the reprojection
@@ -263,7 +291,8 @@ def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel],
     is enough: the hand's known size fixes its depth.  Cameras as for triangulate_landmarks.  loss "huber" / "geman_mcclure" with
     loss_scale px: the robust cost of hand.fit_landmarks_views, for detections some of which are grossly wrong (a fingertip on the
     wrong finger); a fourth item then, inlier [n_cams,21]: psi of every used detection at the returned pose, 1 an inlier, towards
-    0 an outlier.  The default "squared" returns the three items it always did."""
+    0 an outlier.  The default "squared" returns the three items it always did.  return_uncertainty=True: a last item more, the
+    hand.PoseUncertainty of the returned pose under the same loss, weights and views (hand_pose_uncertainty_in_views)."""
     table = _native_camera_table(cameras, "refine_hand_pose_in_views")
     win = np.ascontiguousarray(window_keypoints, np.float64)
     if win.shape != (len(cameras), 21, 2):
@@ -279,7 +308,10 @@ def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel],
         weights=None if weights is None else torch.from_numpy(weights), mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0),
         with_residual=True, loss=loss, loss_scale=loss_scale, return_inliers=robust)
     pose = SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(), hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0)
-    return (pose, fit_info.numpy(), residual.numpy()) + tuple(r.numpy() for r in inlier)
+    out = (pose, fit_info.numpy(), residual.numpy()) + tuple(r.numpy() for r in inlier)
+    if return_uncertainty:
+        out += (hand_pose_uncertainty_in_views(hand_model, cameras, win, hand_idx, pose, weights, loss, loss_scale),)
+    return out
 
 
 def _chain_pose_from_window_keypoints(hand_model, cameras, window_keypoints, hand_idx, weights, init, use_information):
