@@ -665,79 +665,6 @@ def _triangulate_points(window, cam_rows, table, weights, max_iters, out, engine
     return points, info, residual, sqrt_info
 
 
-def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
-                   init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
-                   limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
-                   max_iters: int = 32, *, n: Optional[int] = None, init_ja_stride: int = 22, init_xf_stride: int = 16,
-                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22, xf_stride: int = 16,
-                   info: Optional[torch.Tensor] = None, residual=False, engine: Optional["HipEngine"] = None, _robust=None,
-                   _scale=None):
-    """ut_fit_pose_views: the pose whose landmarks, projected into the views, meet the detections - fit_pose on the
-    reprojection cost sum_v sum_l w_vl |project_v(landmark_l) - window_vl|^2 instead of 3-D targets.  window f64 [n,V,21,2] px,
-    cam_rows i32 [n,V] (-1 = unused view), table f64 [R,32] Fisheye62 source cameras or [R,24] pinhole crop cameras (told apart
-    by the row length), weights f32 [n,V,21] >= 0 or None = all 1 (a window of weight 0 is not read: it may be NaN); V <=
-    TRI_MAX_VIEWS.  init_angles [n,22] / init_wrist_xf [n,4,4] are required: the previous frame's pose, or fit_pose on the
-    triangulated landmarks.  hand_model, limits, mirror, t_scale, the strided form (n, init_*_stride, out, *_stride) and the
-    pose outputs as for fit_pose.  Returns (joint_angles, wrist_xf, info [n,4]: rms reprojection residual px, largest
-    reprojection distance px, iterations, status bits UT_FIT_*) and, with residual=True or a preallocated f32 [n,V,21], the
-    reprojection distance of every used observation as a fourth item.  A cam_rows entry outside [-1, R) raises IndexError and
-    writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks.  _robust = (loss
-    code, loss_scale, inlier) is fit_pose_views_robust's: the same marshalling into ut_fit_pose_views_robust; with _scale =
-    (init_scale, scale_mode, scale) as well it is fit_pose_views_scale's, into ut_fit_pose_views_scale: info is [n,6] and the
-    scale follows the wrist in the result."""
-    if init_angles is None or init_wrist_xf is None:
-        raise ValueError("init_angles and init_wrist_xf are required: ut_fit_pose_views has no cold start")
-    if window.dim() != 4 or tuple(window.shape[2:]) != (21, 2) or window.dtype != torch.float64:
-        raise ValueError(f"window must be f64 [n,V,21,2], got {window.dtype} {tuple(window.shape)}")
-    nw, v = window.shape[:2]
-    if not 1 <= v <= TRI_MAX_VIEWS:
-        raise ValueError(f"window [n,V,21,2] needs 1 <= V <= {TRI_MAX_VIEWS}, got V = {v}")
-    if table.dim() != 2 or table.shape[1] not in (24, 32) or table.shape[0] < 1 or table.dtype != torch.float64:
-        raise ValueError(f"table must be f64 [R,32] source cameras or [R,24] crop cameras, got {table.dtype} {tuple(table.shape)}")
-    if cam_rows.dtype != torch.int32 or tuple(cam_rows.shape) != (nw, v):
-        raise ValueError(f"cam_rows must be i32 [{nw},{v}], got {cam_rows.dtype} {tuple(cam_rows.shape)}")
-    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (nw, v, 21)):
-        raise ValueError(f"weights must be f32 [{nw},{v},21], got {weights.dtype} {tuple(weights.shape)}")
-    kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
-    d = _hip_device(window, "fit_pose_views")
-    window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
-    if weights is not None:
-        weights = _need(weights, torch.float32, d, "weights")
-    hand_model, init_angles, init_wrist_xf, n, out, limits, mirror, h = _fit_args(
-        d, hand_model, init_angles, init_wrist_xf, n, nw, [], out, limits, mirror, engine, windows=True)
-    info = _out(info, (n, 4 if _scale is None else 6), torch.float32, d, "info")
-    if residual is True or isinstance(residual, torch.Tensor):
-        residual = _out(None if residual is True else residual, (n, v, 21), torch.float32, d, "residual")
-    else:
-        residual = None
-    front = (_ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind,
-             _ptr(limits), _ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride, _ptr(mirror), ctypes.c_float(t_scale),
-             int(max_iters))
-    back = (n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride, _ptr(info), _ptr(residual))
-    result = (out[0], out[1], info) if residual is None else (out[0], out[1], info, residual)
-    if _robust is None:
-        _fit_call("ut_fit_pose_views", d, h, *front, *back)
-        return result
-    loss, loss_scale, inlier = _robust
-    if inlier is True or isinstance(inlier, torch.Tensor):
-        inlier = _out(None if inlier is True else inlier, (n, v, 21), torch.float32, d, "inlier")
-    else:
-        inlier = None
-    if _scale is None:
-        _fit_call("ut_fit_pose_views_robust", d, h, *front, int(loss), ctypes.c_float(loss_scale), *back, _ptr(inlier))
-        return result if inlier is None else result + (inlier,)
-    init_scale, scale_mode, scale = _scale
-    if init_scale is not None:
-        init_scale = _need(init_scale, torch.float32, d, "init_scale").reshape(-1)
-        if init_scale.shape[0] != n:
-            raise ValueError("init_scale batch mismatch")
-    scale = _out(scale, (n,), torch.float32, d, "scale")
-    _fit_call("ut_fit_pose_views_scale", d, h, *front[:10], _ptr(init_scale), int(scale_mode), *front[10:], int(loss),
-              ctypes.c_float(loss_scale), *back[:5], _ptr(scale), *back[5:], _ptr(inlier))
-    result = result[:2] + (scale,) + result[2:]
-    return result if inlier is None else result + (inlier,)
-
-
 UT_LOSS_SQUARED, UT_LOSS_HUBER, UT_LOSS_GEMAN_MCCLURE = 0, 1, 2
 LOSSES = {"squared": UT_LOSS_SQUARED, "huber": UT_LOSS_HUBER, "geman_mcclure": UT_LOSS_GEMAN_MCCLURE}
 
@@ -753,6 +680,97 @@ def loss_code(loss) -> int:
     return int(loss)
 
 
+def _loss_args(loss, loss_scale) -> Tuple[int, float]:
+    """(UT_LOSS_* code, loss_scale) of a loss and its scale, which must be finite and > 0 with a robust loss."""
+    code = loss_code(loss)
+    if code != UT_LOSS_SQUARED and not (np.isfinite(loss_scale) and loss_scale > 0):
+        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
+    return code, float(loss_scale)
+
+
+def _optional_out(want, shape, d, name: str) -> Optional[torch.Tensor]:
+    """An optional f32 output: True = a fresh tensor, a tensor = the caller's own (checked by _out), anything else = None."""
+    wanted = want is True or isinstance(want, torch.Tensor)
+    return _out(None if want is True else want, shape, torch.float32, d, name) if wanted else None
+
+
+def _views_inputs(who: str, window, cam_rows, table, weights, loss=None):
+    """The detections of the entries in the views, checked: window, table, cam_rows, weights; then `loss` = (loss, loss_scale) where
+    the entry checks it here; then the windows' HIP device, `who` naming the entry, and the four tensors on it.  Returns (device,
+    window, cam_rows, table, weights, n, V, UT_CAMERA_* kind, _loss_args' pair or None)."""
+    if window.dim() != 4 or tuple(window.shape[2:]) != (21, 2) or window.dtype != torch.float64:
+        raise ValueError(f"window must be f64 [n,V,21,2], got {window.dtype} {tuple(window.shape)}")
+    nw, v = window.shape[:2]
+    if not 1 <= v <= TRI_MAX_VIEWS:
+        raise ValueError(f"window [n,V,21,2] needs 1 <= V <= {TRI_MAX_VIEWS}, got V = {v}")
+    if table.dim() != 2 or table.shape[1] not in (24, 32) or table.shape[0] < 1 or table.dtype != torch.float64:
+        raise ValueError(f"table must be f64 [R,32] source cameras or [R,24] crop cameras, got {table.dtype} {tuple(table.shape)}")
+    if cam_rows.dtype != torch.int32 or tuple(cam_rows.shape) != (nw, v):
+        raise ValueError(f"cam_rows must be i32 [{nw},{v}], got {cam_rows.dtype} {tuple(cam_rows.shape)}")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (nw, v, 21)):
+        raise ValueError(f"weights must be f32 [{nw},{v},21], got {weights.dtype} {tuple(weights.shape)}")
+    if loss is not None:
+        loss = _loss_args(*loss)
+    kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
+    d = _hip_device(window, who)
+    window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
+    weights = None if weights is None else _need(weights, torch.float32, d, "weights")
+    return d, window, cam_rows, table, weights, nw, v, kind, loss
+
+
+def _fit_pose_views(entry, hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters,
+                    loss=None, scale=None, *, n=None, init_ja_stride=22, init_xf_stride=16, out=None, ja_stride=22, xf_stride=16,
+                    info=None, residual=False, engine=None):
+    """The three fits in the views into the C `entry`: loss = (code, loss_scale, inlier) for the robust and the scale entry, scale =
+    (init_scale, scale_mode, scale) for the scale entry (info [n,6]).  Returns (ja, xf[, scale], info[, residual][, inlier])."""
+    if init_angles is None or init_wrist_xf is None:
+        raise ValueError("init_angles and init_wrist_xf are required: ut_fit_pose_views has no cold start")
+    d, window, cam_rows, table, weights, nw, v, kind, _ = _views_inputs("fit_pose_views", window, cam_rows, table, weights)
+    hand_model, init_angles, init_wrist_xf, n, out, limits, mirror, h = _fit_args(
+        d, hand_model, init_angles, init_wrist_xf, n, nw, [], out, limits, mirror, engine, windows=True)
+    info = _out(info, (n, 4 if scale is None else 6), torch.float32, d, "info")
+    residual = _optional_out(residual, (n, v, 21), d, "residual")
+    scale_in = loss_in = scale_out = inlier_out = ()
+    if loss is not None:
+        loss_in, inlier_out = (int(loss[0]), ctypes.c_float(loss[1])), (_optional_out(loss[2], (n, v, 21), d, "inlier"),)
+    if scale is not None:
+        init_scale, scale_mode, scale = scale
+        if init_scale is not None:
+            init_scale = _need(init_scale, torch.float32, d, "init_scale").reshape(-1)
+            if init_scale.shape[0] != n:
+                raise ValueError("init_scale batch mismatch")
+        scale_in, scale_out = (_ptr(init_scale), int(scale_mode)), (_out(scale, (n,), torch.float32, d, "scale"),)
+    model = (_ptr(hand_model), hand_model.shape[0])      # the C arguments in the header's order, each entry with the pieces it has
+    observations = (_ptr(window), _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind)
+    start = (_ptr(init_angles), init_ja_stride, _ptr(init_wrist_xf), init_xf_stride)
+    solver = (_ptr(mirror), ctypes.c_float(t_scale), int(max_iters))
+    pose_out = (n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride)
+    _fit_call(entry, d, h, *model, *observations, _ptr(limits), *scale_in, *start, *solver, *loss_in, *pose_out,
+              *map(_ptr, scale_out), _ptr(info), _ptr(residual), *map(_ptr, inlier_out))
+    return (out[0], out[1]) + scale_out + (info,) + tuple(t for t in (residual,) + inlier_out if t is not None)
+
+
+def fit_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                   init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                   limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                   max_iters: int = 32, *, n: Optional[int] = None, init_ja_stride: int = 22, init_xf_stride: int = 16,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22, xf_stride: int = 16,
+                   info: Optional[torch.Tensor] = None, residual=False, engine: Optional["HipEngine"] = None):
+    """ut_fit_pose_views: the pose whose landmarks, projected into the views, meet the detections - fit_pose on the
+    reprojection cost sum_v sum_l w_vl |project_v(landmark_l) - window_vl|^2 instead of 3-D targets.  window f64 [n,V,21,2] px,
+    cam_rows i32 [n,V] (-1 = unused view), table f64 [R,32] Fisheye62 source cameras or [R,24] pinhole crop cameras (told apart
+    by the row length), weights f32 [n,V,21] >= 0 or None = all 1 (a window of weight 0 is not read: it may be NaN); V <=
+    TRI_MAX_VIEWS.  init_angles [n,22] / init_wrist_xf [n,4,4] are required: the previous frame's pose, or fit_pose on the
+    triangulated landmarks.  hand_model, limits, mirror, t_scale, the strided form (n, init_*_stride, out, *_stride) and the
+    pose outputs as for fit_pose.  Returns (joint_angles, wrist_xf, info [n,4]: rms reprojection residual px, largest
+    reprojection distance px, iterations, status bits UT_FIT_*) and, with residual=True or a preallocated f32 [n,V,21], the
+    reprojection distance of every used observation as a fourth item.  A cam_rows entry outside [-1, R) raises IndexError and
+    writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks."""
+    return _fit_pose_views("ut_fit_pose_views", hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror,
+                           t_scale, max_iters, n=n, init_ja_stride=init_ja_stride, init_xf_stride=init_xf_stride, out=out,
+                           ja_stride=ja_stride, xf_stride=xf_stride, info=info, residual=residual, engine=engine)
+
+
 def fit_pose_views_robust(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
                           init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, weights: Optional[torch.Tensor] = None,
                           limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
@@ -764,11 +782,17 @@ def fit_pose_views_robust(hand_model: torch.Tensor, window: torch.Tensor, cam_ro
     sqrt(robust cost / sum of the used weights), info[1] and residual stay raw distances - and, with inlier=True or a preallocated
     f32 [n,V,21], psi of every used observation at the returned pose as its last item: 1 for an inlier, towards 0 for an
     outlier, 0 where unused or refused."""
-    code = loss_code(loss)
-    if code != UT_LOSS_SQUARED and not (np.isfinite(loss_scale) and loss_scale > 0):
-        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
-    return fit_pose_views(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters,
-                          _robust=(code, float(loss_scale), inlier), **kw)
+    return _fit_pose_views("ut_fit_pose_views_robust", hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits,
+                           mirror, t_scale, max_iters, _loss_args(loss, loss_scale) + (inlier,), **kw)
+
+
+def fit_pose_views_any_loss(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights=None, limits=None, mirror=None,
+                            t_scale: float = 1.0, max_iters: int = 32, loss="squared", loss_scale: float = 3.0, *, inlier=False, **kw):
+    """The fit in the views by the entry that serves `loss`: fit_pose_views for squared without inliers, else fit_pose_views_robust."""
+    if loss_code(loss) == UT_LOSS_SQUARED and not inlier:
+        return fit_pose_views(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters, **kw)
+    return fit_pose_views_robust(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale,
+                                 max_iters, loss, loss_scale, inlier=inlier, **kw)
 
 
 def fit_pose_views_scale(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
@@ -784,13 +808,11 @@ def fit_pose_views_scale(hand_model: torch.Tensor, window: torch.Tensor, cam_row
     keeps init_scale.  One camera cannot see the hand's size: a free fit on one view returns a scale that means nothing with an
     information near 0 - fix the scale there.  Every other argument, **kw included (n, the strides, out, info, residual, engine),
     as for fit_pose_views_robust; `scale` and `info` may be the caller's buffers."""
-    code = loss_code(loss)
-    if code != UT_LOSS_SQUARED and not (np.isfinite(loss_scale) and loss_scale > 0):
-        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
+    robust = _loss_args(loss, loss_scale) + (inlier,)
     if scale_mode not in (UT_SCALE_FREE, UT_SCALE_FIXED):
         raise ValueError(f"scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED, got {scale_mode!r}")
-    return fit_pose_views(hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits, mirror, t_scale, max_iters,
-                          _robust=(code, float(loss_scale), inlier), _scale=(init_scale, int(scale_mode), scale), **kw)
+    return _fit_pose_views("ut_fit_pose_views_scale", hand_model, window, cam_rows, table, init_angles, init_wrist_xf, weights, limits,
+                           mirror, t_scale, max_iters, robust, (init_scale, int(scale_mode), scale), **kw)
 
 
 UT_COV_OK, UT_COV_SINGULAR, UT_COV_REFUSED = 1, 2, 4
@@ -816,25 +838,8 @@ def pose_information_views(hand_model: torch.Tensor, joint_angles: torch.Tensor,
     and writes nothing for its pose - at once, or from engine.poll_status() when `engine` runs deferred checks."""
     if joint_angles is None or wrist_xf is None:
         raise ValueError("joint_angles and wrist_xf are required")
-    if window.dim() != 4 or tuple(window.shape[2:]) != (21, 2) or window.dtype != torch.float64:
-        raise ValueError(f"window must be f64 [n,V,21,2], got {window.dtype} {tuple(window.shape)}")
-    nw, v = window.shape[:2]
-    if not 1 <= v <= TRI_MAX_VIEWS:
-        raise ValueError(f"window [n,V,21,2] needs 1 <= V <= {TRI_MAX_VIEWS}, got V = {v}")
-    if table.dim() != 2 or table.shape[1] not in (24, 32) or table.shape[0] < 1 or table.dtype != torch.float64:
-        raise ValueError(f"table must be f64 [R,32] source cameras or [R,24] crop cameras, got {table.dtype} {tuple(table.shape)}")
-    if cam_rows.dtype != torch.int32 or tuple(cam_rows.shape) != (nw, v):
-        raise ValueError(f"cam_rows must be i32 [{nw},{v}], got {cam_rows.dtype} {tuple(cam_rows.shape)}")
-    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (nw, v, 21)):
-        raise ValueError(f"weights must be f32 [{nw},{v},21], got {weights.dtype} {tuple(weights.shape)}")
-    code = loss_code(loss)
-    if code != UT_LOSS_SQUARED and not (np.isfinite(loss_scale) and loss_scale > 0):
-        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale}")
-    kind = UT_CAMERA_FISHEYE62 if table.shape[1] == 32 else UT_CAMERA_PINHOLE
-    d = _hip_device(window, "pose_information_views")
-    window, table, cam_rows = _need(window, torch.float64, d, "window"), _need(table, torch.float64, d, "table"), _need(cam_rows, torch.int32, d, "cam_rows")
-    if weights is not None:
-        weights = _need(weights, torch.float32, d, "weights")
+    d, window, cam_rows, table, weights, nw, v, kind, (code, loss_scale) = _views_inputs(
+        "pose_information_views", window, cam_rows, table, weights, (loss, loss_scale))
     hand_model, joint_angles, wrist_xf, mirror, n = _fk_args(d, hand_model, joint_angles, wrist_xf, mirror, n)
     if n != nw:
         raise ValueError(f"{n} poses for {nw} poses' windows")
@@ -842,20 +847,15 @@ def pose_information_views(hand_model: torch.Tensor, joint_angles: torch.Tensor,
         angle_sigma = _need(angle_sigma, torch.float32, d, "angle_sigma").reshape(-1, 20)
         if angle_sigma.shape[0] != hand_model.shape[0]:
             raise ValueError(f"angle_sigma has {angle_sigma.shape[0]} rows for {hand_model.shape[0]} model rows")
-    outs = []
-    for name, want, shape in (("pose_info", pose_info, (n, 351)), ("pivot", pivot, (n, 3)), ("param_sigma", param_sigma, (n, 26)),
-                              ("landmark_cov", landmark_cov, (n, 21, 6)), ("info", info, (n, 4))):
-        if want is True or isinstance(want, torch.Tensor):
-            outs.append(_out(None if want is True else want, shape, torch.float32, d, name))
-        else:
-            outs.append(None)
+    outs = tuple(_optional_out(want, shape, d, name) for name, want, shape in (("pose_info", pose_info, (n, 351)), ("pivot", pivot, (n, 3)), (
+        "param_sigma", param_sigma, (n, 26)), ("landmark_cov", landmark_cov, (n, 21, 6)), ("info", info, (n, 4))))
     if all(o is None for o in outs):
         raise ValueError("at least one output is needed")
     h = engine._h if engine is not None else None
     _fit_call("ut_pose_information_views", d, h, _ptr(hand_model), hand_model.shape[0], _ptr(window), _ptr(weights), _ptr(cam_rows), v,
               _ptr(table), table.shape[0], kind, _ptr(angle_sigma), _ptr(joint_angles), ja_stride, _ptr(wrist_xf), xf_stride,
-              _ptr(mirror), ctypes.c_float(t_scale), code, ctypes.c_float(loss_scale), n, *[_ptr(o) for o in outs])
-    return tuple(outs)
+              _ptr(mirror), ctypes.c_float(t_scale), code, ctypes.c_float(loss_scale), n, *map(_ptr, outs))
+    return outs
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

@@ -1215,22 +1215,25 @@ int fail_as(ut_handle h, const char* who, const char* what) {
   return fail(h, UT_E_INVALID, msg);
 }
 
-// The argument checks the pose fits share; `who` names the entry in the message.  with_targets false: ut_fit_pose_views, which has
-// no 3-D targets and needs its start.
-int fit_pose_args(ut_handle h, const char* who, const float* hand_model, int n_models, const float* targets, int target_stride,
-                  const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride, float t_scale,
-                  int max_iters, int n, const float* joint_angles, int ja_stride, const float* wrist_xf, int xf_stride,
-                  bool with_targets = true) {
-  if (!hand_model || (with_targets && !targets) || !joint_angles || !wrist_xf || n < 0 || (n_models != 1 && n_models != n))
+// The argument checks the pose fits share, on the arguments as the kernels get them; `who` names the entry in the message.
+// FIT_NO_TARGETS: the fits in the views, which have no 3-D targets and need their start.  FIT_POSE_IS_INPUT: ut_pose_information_views,
+// whose pose stands where the fits have their start - it is checked as their outputs are; a.ja / a.xf and a.max_iters are not read.
+enum : int { FIT_NO_TARGETS = 1, FIT_POSE_IS_INPUT = 2 };
+int fit_pose_args(ut_handle h, const char* who, const ut::FitPoseArgs& a, int flags = 0) {
+  const bool with_targets = !(flags & FIT_NO_TARGETS), fitted = !(flags & FIT_POSE_IS_INPUT);
+  const float *ja = fitted ? a.ja : a.init_ja, *xf = fitted ? a.xf : a.init_xf;
+  const int ja_stride = fitted ? a.ja_stride : a.init_ja_stride, xf_stride = fitted ? a.xf_stride : a.init_xf_stride;
+  if (!a.hand_model || (with_targets && !a.targets) || !ja || !xf || a.n < 0 || (a.n_models != 1 && a.n_models != a.n))
     return fail_as(h, who, "bad argument");
-  if (!with_targets && (!init_angles || !init_wrist_xf))
+  if (!with_targets && (!a.init_ja || !a.init_xf))
     return fail_as(h, who, "init_angles and init_wrist_xf are required: there is no cold start");
-  if ((init_angles == nullptr) != (init_wrist_xf == nullptr))
+  if ((a.init_ja == nullptr) != (a.init_xf == nullptr))
     return fail_as(h, who, "init_angles and init_wrist_xf must both be given or both be NULL");
-  if ((with_targets && target_stride < 63) || ja_stride < 22 || xf_stride < 12 || (init_angles && (init_ja_stride < 22 || init_xf_stride < 12)))
+  if ((with_targets && a.target_stride < 63) || ja_stride < 22 || xf_stride < 12 ||
+      (a.init_ja && (a.init_ja_stride < 22 || a.init_xf_stride < 12)))
     return fail_as(h, who, "a stride is below 63 (targets) / 22 (angles) / 12 (wrist)");
-  if (max_iters < 1 || max_iters > 256) return fail_as(h, who, "max_iters must be in 1..256");
-  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f)) return fail_as(h, who, "t_scale must be positive and finite");
+  if (fitted && (a.max_iters < 1 || a.max_iters > 256)) return fail_as(h, who, "max_iters must be in 1..256");
+  if (!(a.t_scale > 0.f) || !(a.t_scale <= 3.0e38f)) return fail_as(h, who, "t_scale must be positive and finite");
   return UT_OK;
 }
 }  // namespace
@@ -1241,13 +1244,12 @@ int ut_fit_pose(ut_handle h, const float* hand_model, int n_models, const float*
                 float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride, float* info, void* stream) {
   // stateless like ut_fk: h may be NULL
   if (n == 0) return UT_OK;
-  const int rc = fit_pose_args(h, "ut_fit_pose", hand_model, n_models, targets, target_stride, init_angles, init_ja_stride,
-                               init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
-  if (rc) return rc;
-  ON_DEVICE_IF(h);
   const ut::FitArgs a{{hand_model, n_models, targets, target_stride, limits, init_angles, init_ja_stride, init_wrist_xf,
                        init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
                       weights, info};
+  const int rc = fit_pose_args(h, "ut_fit_pose", a.pose);
+  if (rc) return rc;
+  ON_DEVICE_IF(h);
   HIPCHK(h, ut::launch_fit_pose(a, (hipStream_t)stream));
   return UT_OK;
 }
@@ -1259,13 +1261,12 @@ int ut_fit_pose_info(ut_handle h, const float* hand_model, int n_models, const f
   // stateless like ut_fit_pose: h may be NULL
   if (n == 0) return UT_OK;
   if (!sqrt_info) return fail(h, UT_E_INVALID, "ut_fit_pose_info: bad argument");
-  const int rc = fit_pose_args(h, "ut_fit_pose_info", hand_model, n_models, targets, target_stride, init_angles, init_ja_stride,
-                               init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
-  if (rc) return rc;
-  ON_DEVICE_IF(h);
   const ut::FitInfoArgs a{{hand_model, n_models, targets, target_stride, limits, init_angles, init_ja_stride, init_wrist_xf,
                            init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
                           sqrt_info, info};
+  const int rc = fit_pose_args(h, "ut_fit_pose_info", a.pose);
+  if (rc) return rc;
+  ON_DEVICE_IF(h);
   HIPCHK(h, ut::launch_fit_pose_info(a, (hipStream_t)stream));
   return UT_OK;
 }
@@ -1285,13 +1286,12 @@ int ut_fit_pose_scale(ut_handle h, const float* hand_model, int n_models, const 
   if (!scale) return fail(h, UT_E_INVALID, "ut_fit_pose_scale: bad argument");
   if (scale_mode != UT_SCALE_FREE && scale_mode != UT_SCALE_FIXED)
     return fail(h, UT_E_INVALID, "ut_fit_pose_scale: scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED");
-  const int rc = fit_pose_args(h, "ut_fit_pose_scale", hand_model, n_models, targets, target_stride, init_angles, init_ja_stride,
-                               init_wrist_xf, init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride);
-  if (rc) return rc;
-  ON_DEVICE_IF(h);
   const ut::FitScaleArgs a{{hand_model, n_models, targets, target_stride, limits, init_angles, init_ja_stride, init_wrist_xf,
                             init_xf_stride, mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
                            weights, init_scale, scale_mode, scale, info};
+  const int rc = fit_pose_args(h, "ut_fit_pose_scale", a.pose);
+  if (rc) return rc;
+  ON_DEVICE_IF(h);
   HIPCHK(h, ut::launch_fit_pose_scale(a, (hipStream_t)stream));
   return UT_OK;
 }
@@ -1534,48 +1534,33 @@ static_assert(UT_LOSS_SQUARED == ut::FITV_LOSS_SQUARED && UT_LOSS_HUBER == ut::F
               UT_LOSS_GEMAN_MCCLURE == ut::FITV_LOSS_GEMAN_MCCLURE, "umetrack_hip_robust.h and ut_kernels.h");
 
 namespace {
-// What ut_fit_pose_views_scale adds to the arguments of the fits in the views; null for the other two entries.
-struct ViewsScale {
-  const float* init_scale;
-  int scale_mode;
-  float* scale;
-};
-// What ut_pose_information_views has where the fits have their outputs; null for the fits.
-struct ViewsCov {
-  const float* angle_sigma;
-  float *pose_info, *pivot, *param_sigma, *landmark_cov, *info;
-};
-
-// ut_fit_pose_views, ut_fit_pose_views_robust, ut_fit_pose_views_scale and ut_pose_information_views: one set of checks, one
-// status path.  UT_LOSS_SQUARED without `inlier` launches fit_views.hip's kernels (launch_fit_pose_views_robust hands it on); with
-// `sc` every loss is fit_views_scale.hip's and `info` is [n,6]; with `cov` the init pointers are the pose, nothing is fitted and
-// pose_info_views.hip's kernels write cov's outputs.
-int fit_pose_views(ut_handle h, const char* who, const float* hand_model, int n_models, const double* window, const float* weights,
-                   const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind, const float* limits,
-                   const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
-                   const int64_t* mirror, float t_scale, int max_iters, int loss, float loss_scale, int n, float* joint_angles,
-                   int ja_stride, float* wrist_xf, int xf_stride, float* info, float* residual, float* inlier, void* stream,
-                   const ViewsScale* sc = nullptr, const ViewsCov* cov = nullptr) {
-  if (!window || !cam_rows || !table || (sc && !sc->scale)) return fail_as(h, who, "null argument");
-  if (cov && !cov->pose_info && !cov->pivot && !cov->param_sigma && !cov->landmark_cov && !cov->info)
-    return fail_as(h, who, "all five outputs are NULL");
-  if (sc && sc->scale_mode != UT_SCALE_FREE && sc->scale_mode != UT_SCALE_FIXED)
-    return fail_as(h, who, "scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED");
+// The argument checks the four entries in the views share, on the arguments as the kernels get them, in the order the messages
+// have always had.  An entry's own checks come second and third in that order, so the entry states them and they are reported
+// from here: null_own - a required pointer of its own is NULL; own - the message of its own first broken rule, or null.
+int fit_views_args(ut_handle h, const char* who, const ut::FitViewsRobustArgs& a, int table_kind, int flags = FIT_NO_TARGETS,
+                   bool null_own = false, const char* own = nullptr) {
+  const ut::FitViewsArgs& g = a.views;
+  if (!g.window || !g.cam_rows || !g.table || null_own) return fail_as(h, who, "null argument");
+  if (own) return fail_as(h, who, own);
   if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
     return fail_as(h, who, "table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
-  if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS) return fail_as(h, who, "max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
-  if (n_rows < 1) return fail_as(h, who, "bad argument");
-  if (loss != UT_LOSS_SQUARED && loss != UT_LOSS_HUBER && loss != UT_LOSS_GEMAN_MCCLURE)
+  if (g.max_views < 1 || g.max_views > UT_TRI_MAX_VIEWS) return fail_as(h, who, "max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
+  if (g.n_rows < 1) return fail_as(h, who, "bad argument");
+  if (a.loss != UT_LOSS_SQUARED && a.loss != UT_LOSS_HUBER && a.loss != UT_LOSS_GEMAN_MCCLURE)
     return fail_as(h, who, "loss must be UT_LOSS_SQUARED, UT_LOSS_HUBER or UT_LOSS_GEMAN_MCCLURE");
-  if (loss != UT_LOSS_SQUARED && (!(loss_scale > 0.f) || !(loss_scale <= 3.0e38f)))
+  if (a.loss != UT_LOSS_SQUARED && (!(a.loss_scale > 0.f) || !(a.loss_scale <= 3.0e38f)))
     return fail_as(h, who, "loss_scale must be positive and finite");
-  const int rc = fit_pose_args(h, who, hand_model, n_models, nullptr, 0, init_angles, init_ja_stride, init_wrist_xf,
-                               init_xf_stride, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride, false);
-  if (rc) return rc;
-  if (n == 0) return UT_OK;
+  return fit_pose_args(h, who, g.pose, flags);
+}
+
+// What follows the checks of an entry in the views: nothing for n = 0; the windows' device against the handle's; the status words,
+// the device, the status word into the arguments; `launch` (it returns the entry's code); the index check's answer if synchronous.
+extern "C++" template <class Launch>
+int launch_in_views(ut_handle h, const char* who, ut::FitViewsArgs& g, void* stream, Launch launch) {
+  if (g.pose.n == 0) return UT_OK;
   if (h) {
     hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, window) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device != h->device)
+    if (hipPointerGetAttributes(&attr, g.window) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device != h->device)
       return fail_as(h, who, "the windows live on another device than the handle");
   }
   StatusTarget st;
@@ -1584,21 +1569,20 @@ int fit_pose_views(ut_handle h, const char* who, const float* hand_model, int n_
   DeviceScope scope(st.device);
   if (scope.err != hipSuccess) return fail(h, UT_E_HIP, "hipSetDevice", scope.err);
   hipStream_t s = (hipStream_t)stream;
-  const ut::FitViewsRobustArgs a{{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride,
-                                   mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
-                                  window, weights, cam_rows, max_views, table, n_rows,
-                                  table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE, info, residual, st.dev},
-                                 loss, loss_scale, inlier};
-  if (cov) {
-    const ut::PoseInfoViewsArgs b{a, cov->angle_sigma, cov->pose_info, cov->pivot, cov->param_sigma, cov->landmark_cov, cov->info};
-    HIPCHK(h, ut::launch_pose_information_views(b, s));
-  } else if (sc) {
-    const ut::FitViewsScaleArgs b{a, sc->init_scale, sc->scale_mode, sc->scale};
-    HIPCHK(h, ut::launch_fit_pose_views_scale(b, s));
-  } else {
-    HIPCHK(h, ut::launch_fit_pose_views_robust(a, s));
-  }
+  g.status = st.dev;
+  const int rc = launch(s);
+  if (rc) return rc;
   return st.mode == UT_CHECK_SYNC ? check_status(h, st.dev, st.host, s, who) : UT_OK;
+}
+
+int camera_kind(int table_kind) { return table_kind == UT_CAMERA_FISHEYE62 ? ut::PROJECT_FISHEYE62 : ut::PROJECT_PINHOLE; }
+
+// ut_fit_pose_views and ut_fit_pose_views_robust: launch_fit_pose_views_robust hands UT_LOSS_SQUARED without `inlier` on to fit_views.hip
+int fit_pose_views_robust(ut_handle h, const char* who, int table_kind, void* stream, ut::FitViewsRobustArgs a) {
+  const int rc = fit_views_args(h, who, a, table_kind);
+  if (rc) return rc;
+  return launch_in_views(h, who, a.views, stream, [&](hipStream_t s) -> int {
+    HIPCHK(h, ut::launch_fit_pose_views_robust(a, s)); return UT_OK; });
 }
 }  // namespace
 
@@ -1607,9 +1591,11 @@ int ut_fit_pose_views(ut_handle h, const float* hand_model, int n_models, const 
                       const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
                       const int64_t* mirror, float t_scale, int max_iters, int n, float* joint_angles, int ja_stride,
                       float* wrist_xf, int xf_stride, float* info, float* residual, void* stream) {
-  return fit_pose_views(h, "ut_fit_pose_views", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows, table_kind,
-                        limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
-                        UT_LOSS_SQUARED, 0.f, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, nullptr, stream);
+  return fit_pose_views_robust(h, "ut_fit_pose_views", table_kind, stream,
+                               {{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride,
+                                  mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                                 window, weights, cam_rows, max_views, table, n_rows, camera_kind(table_kind), info, residual, nullptr},
+                                UT_LOSS_SQUARED, 0.f, nullptr});
 }
 
 int ut_fit_pose_views_robust(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
@@ -1618,9 +1604,11 @@ int ut_fit_pose_views_robust(ut_handle h, const float* hand_model, int n_models,
                              int init_xf_stride, const int64_t* mirror, float t_scale, int max_iters, int loss, float loss_scale,
                              int n, float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride, float* info,
                              float* residual, float* inlier, void* stream) {
-  return fit_pose_views(h, "ut_fit_pose_views_robust", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
-                        table_kind, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
-                        loss, loss_scale, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, inlier, stream);
+  return fit_pose_views_robust(h, "ut_fit_pose_views_robust", table_kind, stream,
+                               {{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride,
+                                  mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                                 window, weights, cam_rows, max_views, table, n_rows, camera_kind(table_kind), info, residual, nullptr},
+                                loss, loss_scale, inlier});
 }
 
 int ut_fit_pose_views_scale(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
@@ -1629,10 +1617,17 @@ int ut_fit_pose_views_scale(ut_handle h, const float* hand_model, int n_models, 
                             int init_ja_stride, const float* init_wrist_xf, int init_xf_stride, const int64_t* mirror, float t_scale,
                             int max_iters, int loss, float loss_scale, int n, float* joint_angles, int ja_stride, float* wrist_xf,
                             int xf_stride, float* scale, float* info, float* residual, float* inlier, void* stream) {
-  const ViewsScale sc{init_scale, scale_mode, scale};
-  return fit_pose_views(h, "ut_fit_pose_views_scale", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
-                        table_kind, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale, max_iters,
-                        loss, loss_scale, n, joint_angles, ja_stride, wrist_xf, xf_stride, info, residual, inlier, stream, &sc);
+  const char* who = "ut_fit_pose_views_scale";      // every loss is fit_views_scale.hip's; info is [n,6]
+  ut::FitViewsScaleArgs b{{{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride,
+                             mirror, t_scale, max_iters, n, joint_angles, ja_stride, wrist_xf, xf_stride},
+                            window, weights, cam_rows, max_views, table, n_rows, camera_kind(table_kind), info, residual, nullptr},
+                           loss, loss_scale, inlier},
+                          init_scale, scale_mode, scale};
+  const int rc = fit_views_args(h, who, b.robust, table_kind, FIT_NO_TARGETS, !scale, scale_mode == UT_SCALE_FREE || scale_mode == UT_SCALE_FIXED
+                                ? nullptr : "scale_mode must be UT_SCALE_FREE or UT_SCALE_FIXED");
+  if (rc) return rc;
+  return launch_in_views(h, who, b.robust.views, stream, [&](hipStream_t s) -> int {
+    HIPCHK(h, ut::launch_fit_pose_views_scale(b, s)); return UT_OK; });
 }
 
 static_assert(UT_COV_OK == ut::COV_OK && UT_COV_SINGULAR == ut::COV_SINGULAR && UT_COV_REFUSED == ut::COV_REFUSED &&
@@ -1644,12 +1639,17 @@ int ut_pose_information_views(ut_handle h, const float* hand_model, int n_models
                               int xf_stride, const int64_t* mirror, float t_scale, int loss, float loss_scale, int n,
                               float* pose_info, float* pivot, float* param_sigma, float* landmark_cov, float* info,
                               void* stream) {
-  // the pose is the fit's start, and stands for the fit's outputs in the shared checks: nothing is written through it
-  const ViewsCov cov{angle_sigma, pose_info, pivot, param_sigma, landmark_cov, info};
-  return fit_pose_views(h, "ut_pose_information_views", hand_model, n_models, window, weights, cam_rows, max_views, table, n_rows,
-                        table_kind, nullptr, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale, 1, loss, loss_scale, n,
-                        const_cast<float*>(joint_angles), ja_stride, const_cast<float*>(wrist_xf), xf_stride, nullptr, nullptr,
-                        nullptr, stream, nullptr, &cov);
+  const char* who = "ut_pose_information_views";      // the pose stands where the fits have their start; there are no pose outputs
+  ut::PoseInfoViewsArgs b{{{{hand_model, n_models, nullptr, 0, nullptr, joint_angles, ja_stride, wrist_xf, xf_stride, mirror, t_scale,
+                             0, n, nullptr, 0, nullptr, 0},
+                            window, weights, cam_rows, max_views, table, n_rows, camera_kind(table_kind), nullptr, nullptr, nullptr},
+                           loss, loss_scale, nullptr},
+                          angle_sigma, pose_info, pivot, param_sigma, landmark_cov, info};
+  const int rc = fit_views_args(h, who, b.robust, table_kind, FIT_NO_TARGETS | FIT_POSE_IS_INPUT, false,
+                                pose_info || pivot || param_sigma || landmark_cov || info ? nullptr : "all five outputs are NULL");
+  if (rc) return rc;
+  return launch_in_views(h, who, b.robust.views, stream, [&](hipStream_t s) -> int {
+    HIPCHK(h, ut::launch_pose_information_views(b, s)); return UT_OK; });
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

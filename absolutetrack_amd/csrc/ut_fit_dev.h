@@ -1,4 +1,5 @@
 // The pose fits' solver, written once: fit.hip, fit_scale.hip, fit_info.hip and fit_views.hip each describe a cost and instantiate it.
+// At the end the hand's scale as a 27th parameter, FitScaleParam, which fit_scale.hip and fit_views_scale.hip share.
 //
 // Levenberg-Marquardt on NP parameters (20 angle increments, a wrist rotation about the weighted centroid of the targets, a
 // wrist translation, then whatever the problem adds) and 63 residual rows, Marquardt's diagonal scaling with a floor, Cholesky
@@ -517,5 +518,77 @@ __device__ inline void fit_pose(P& prob, typename P::Lds& S, const FitPoseArgs& 
   fit_store_pose(S, a, i, lane, st);
   prob.report(S, i, lane, st);
 }
+
+// ---- the hand's scale as a 27th parameter, written once: fit_scale.hip and fit_views_scale.hip derive their problems from it
+//
+// Scale s means hand.scaled_hand_model(model, s): the 66 joint and 63 landmark rest coordinates times s in fp32, nothing else.
+// sigma = ln s is ordered last, d landmark / d sigma = landmark - wrist translation (the deriving problem's finish_rows writes
+// that column), the trial scale is clamp(s exp(d sigma), SCALE_MIN, SCALE_MAX), and a small step also needs |d sigma| <=
+// FIT_STEP_TOL.  Every trial writes the region's model again from an unscaled copy of those 129 floats.
+constexpr int FITS_P = 3;         // poses (waves) per workgroup
+constexpr int FITS_SIGMA = 26;    // column of sigma = ln s
+
+struct FitScaleLds {              // one wave's region
+  float hm[321];                  // the pose's packed model at the scale of the last evaluated state
+  float rest[129];                // its joint (66) and landmark (63) rest coordinates as given: hm[66..194] = rest * scale
+  float local[20][12];            // joint transforms of the last evaluated state
+  float prefix[20][12];           // W L0 .. L(j-1) in front of joint 4 f + j
+  float frame[17][12];            // skinning frames
+  float omega[20][3], cw[20][3];  // joint axes and centres in the world (linearisation)
+  float jl[63 * 29];              // J while the normal matrix is formed, then the Cholesky factor L [27][29]
+  float a[28][29];                // lower triangle of [J r]^T [J r]: A = J^T J, row 27 = g = J^T r
+  float ang[20], ang_t[20];       // accepted and trial angles
+  float wrist[12], wrist_t[12];   // accepted and trial wrist frame
+  float p[21][3];                 // landmarks of the last evaluated state
+  float target[21][3], w[21];     // targets (0 where the weight is 0, or without 3-D targets) and scalar weights, 0 = unused
+};
+static_assert(sizeof(FitScaleLds) == 16416 && sizeof(FitScaleLds) * FITS_P <= 65536, "a workgroup's static LDS");
+
+struct FitScaleParam {
+  bool fixed = false;
+  float scale = 1.f, scale_t = 1.f;      // of the accepted and of the trial state
+
+  // The model of the region at scale s: the bits of scaled_hand_model.  Called by the whole wave; the caller syncs.
+  __device__ inline void set_scale(FitScaleLds& S, float s, int lane) {
+    for (int e = lane; e < 129; e += 64) S.hm[66 + e] = S.rest[e] * s;
+  }
+  // The unscaled rest coordinates and the start's scale; the model at that scale.  False when the start's scale lies outside the
+  // bounds: the pose is refused and its scale is 1.
+  __device__ inline bool load_scale(FitScaleLds& S, const float* hand_model, int mrow, const float* init_scale, int scale_mode, int i,
+                                    int lane) {
+    fixed = scale_mode == FITS_MODE_FIXED;
+    for (int e = lane; e < 129; e += 64) S.rest[e] = hand_model[(size_t)mrow * 321 + 66 + e];
+    if (init_scale) scale = init_scale[i];
+    const bool bad_scale = !(scale >= FITS_SCALE_MIN) || !(scale <= FITS_SCALE_MAX);      // a NaN is neither
+    if (bad_scale) scale = 1.f;
+    wave_sync();                                      // S.hm is written by other lanes
+    set_scale(S, scale, lane);
+    return !bad_scale;
+  }
+  __device__ inline bool trial(FitScaleLds& S, int lane, float delta) {
+    // with the sigma column zero the floored diagonal gives d sigma = 0; the fixed scale is kept by construction as well
+    const float ds = fixed ? 0.f : lane_value(delta, FITS_SIGMA);
+    scale_t = fixed ? scale : fminf(fmaxf(scale * expf(ds), FITS_SCALE_MIN), FITS_SCALE_MAX);
+    set_scale(S, scale_t, lane);
+    return fabsf(ds) <= FIT_STEP_TOL;
+  }
+  // The scale information of the accepted state of problem `prob` (the object this is a base of), 0 for a refused pose and a
+  // fixed scale: the last pivot of the Cholesky factorisation of A + SCALE_INFO_LAMBDA D, i.e. the Schur complement of sigma;
+  // FITS_AT_BOUND into `status`.  After an accepted last trial the region holds that state (model at its scale, frames,
+  // landmarks) and the normal matrix is the one before it: linearise once more.  After a rejected one the normal matrix is the
+  // accepted state's already, and nothing else is needed.
+  template <class P>
+  __device__ inline float scale_information(P& prob, FitScaleLds& S, int lane, const FitState& st, int& status) {
+    float scale_info = 0.f;
+    if (!st.refused && !fixed) {
+      if (st.fresh) fit_linearise(prob, S, lane, st);
+      float pivot = 0.f;                              // stays 0 when a pivot is not positive and finite
+      fit_solve<P::NP, P::LD, false>(S, lane, FITS_SCALE_INFO_LAMBDA, fit_diag<P::NP>(S, lane), pivot);
+      scale_info = uniform(pivot);
+      if (scale <= FITS_SCALE_MIN || scale >= FITS_SCALE_MAX) status |= FITS_AT_BOUND;
+    }
+    return scale_info;
+  }
+};
 
 }  // namespace ut

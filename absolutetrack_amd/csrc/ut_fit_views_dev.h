@@ -1,7 +1,6 @@
-// The cost of the pose fits on 2-D keypoints in camera views, written once: fit_views.hip (ut_fit_pose_views, the squared
-// reprojection cost) and fit_views_robust.hip (ut_fit_pose_views_robust, Huber and Geman-McClure) instantiate it in
-// ut_fit_dev.h's fit_pose(), and fit_views_scale.hip (ut_fit_pose_views_scale) derives the same cost on 27 parameters from it.
-// fit_views.hip's header comment describes the reduction to 63 rows, the region and the registers.
+// The cost of the pose fits on 2-D keypoints in camera views, written once: fit_views.hip (ut_fit_pose_views, squared) and
+// fit_views_robust.hip (ut_fit_pose_views_robust, Huber and Geman-McClure) instantiate it in ut_fit_dev.h's fit_pose(), and
+// fit_views_scale.hip derives it on 27 parameters.  fit_views.hip's header comment: the reduction to 63 rows, the region, registers.
 //
 // The loss is a compile-time parameter.  The cost is sum_v sum_l w_vl c^2 rho(d_vl^2 / c^2), d the reprojection distance and c
 // a scale, both in px:
@@ -13,6 +12,8 @@
 // second-order (Triggs) term.  The cost hook returns the robust cost itself, so fit_pose()'s accept / reject, lambda and stop
 // rules act on it unchanged; `worst` stays the largest raw reprojection distance.  With FITV_LOSS_SQUARED every factor is the
 // constant 1 and fit_views.hip compiles to what it compiled to before the loss was a parameter.
+// The four kernels in the views repeat their cam_rows index check (the bad_row loop, the atomicOr) on purpose: a shared __device__
+// helper, with or without the atomicOr, changes the register allocation of all four files, which sit at the register limit.
 #pragma once
 #include "ut_camera.h"
 #include "ut_fit_dev.h"
@@ -53,8 +54,7 @@ __device__ inline double fitv_rho(double d2, double c2, double inv_c2) {
   return d2 / (1.0 + s);
 }
 
-// REGION, PARAMS and STRIDE are the problem's P::Lds, P::NP and P::LD: fit_views_scale.hip derives the same cost on 27 parameters
-// in fit_scale.hip's region from it.  The defaults are what fit_views.hip and fit_views_robust.hip instantiate.
+// REGION, PARAMS, STRIDE: the problem's P::Lds, P::NP, P::LD - fit_views.hip's and fit_views_robust.hip's, or FitScaleLds, 27, 29.
 template <int KIND, int LOSS = FITV_LOSS_SQUARED, class REGION = FitViewsLds, int PARAMS = 26, int STRIDE = 27>
 struct FitViewsCost {
   using Lds = REGION;

@@ -196,6 +196,17 @@ class _FitStaging:
         return t.reshape(self.lead + tail).to(self.src_device)
 
 
+def _views_staging(hand_model: HandModel, window, cam_rows, table, weights, limits):
+    """How the wrappers on detections in V views stage a call: window [...,V,21,2] checked -> (the _FitStaging on its leading
+    dims, V, (window f64 [n,V,21,2], cam_rows i32 [n,V], table f64) on the device, weights [n,V,21] there or None)."""
+    if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
+        raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
+    v = window.shape[-3]
+    s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, limits, "limits")
+    views = (s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32), table.to(s.dev, torch.float64))
+    return s, v, views, s.f32(weights, (v, 21))
+
+
 def fit_landmarks(hand_model: HandModel, landmarks: torch.Tensor, weights: Optional[torch.Tensor] = None, init=None,
                   limits: bool = False, mirror: Optional[torch.Tensor] = None, max_iters: int = 32):
     """The inverse of skin_landmarks: [...,21,3] landmarks -> (joint_angles [...,22], wrist_transforms [...,4,4], info
@@ -263,17 +274,9 @@ def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: t
     used detection.  Leading dims, devices and mirror as for fit_landmarks."""
     if init is None:
         raise ValueError("init = (joint_angles, wrist_transforms) is required: fit_landmarks_views has no cold start")
-    if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
-        raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
-    v = window.shape[-3]
-    s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, limits, "limits")
-    args = (s.blob, s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32), table.to(s.dev, torch.float64),
-            *s.init(init), s.f32(weights, (v, 21)), s.box, s.flags(mirror))
-    if _native.loss_code(loss) == _native.UT_LOSS_SQUARED and not return_inliers:
-        res = _native.fit_pose_views(*args, max_iters=max_iters, residual=with_residual)
-    else:
-        res = _native.fit_pose_views_robust(*args, max_iters=max_iters, loss=loss, loss_scale=loss_scale, residual=with_residual,
-                                            inlier=return_inliers)
+    s, v, views, weights = _views_staging(hand_model, window, cam_rows, table, weights, limits)
+    res = _native.fit_pose_views_any_loss(s.blob, *views, *s.init(init), weights, s.box, s.flags(mirror), max_iters=max_iters, loss=loss,
+                                          loss_scale=loss_scale, residual=with_residual, inlier=return_inliers)
     out = (s.back(res[0], (22,)), s.back(res[1], (4, 4)), s.back(res[2], (4,)))
     return out + tuple(s.back(r, (v, 21)) for r in res[3:])
 
@@ -336,10 +339,7 @@ def pose_uncertainty_views(hand_model: HandModel, joint_angles: torch.Tensor, wr
     +inf.  The covariance is the Gauss-Newton one of the unconstrained linearisation (no second-order term; under a robust loss
     that of the reweighted problem): it means something at a minimum of the cost - at the pose a fit returned.  A hand that
     one camera sees comes back several times less certain along that camera's rays than across them."""
-    if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
-        raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
-    v = window.shape[-3]
-    s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, False)
+    s, _v, views, weights = _views_staging(hand_model, window, cam_rows, table, weights, False)
     if angle_sigma is not None:
         rows = s.blob.shape[0]
         angle_sigma = torch.as_tensor(angle_sigma, dtype=torch.float32)      # one row per model row, as the kernel reads it
@@ -347,10 +347,8 @@ def pose_uncertainty_views(hand_model: HandModel, joint_angles: torch.Tensor, wr
         if angle_sigma.shape[0] != rows:
             raise ValueError("angle_sigma must be [20] with an unbatched hand_model")
         angle_sigma = angle_sigma.to(s.dev).contiguous()
-    outs = _native.pose_information_views(s.blob, s.f32(joint_angles, (22,)), s.f32(wrist_transforms, (4, 4)),
-                                          s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32),
-                                          table.to(s.dev, torch.float64), s.f32(weights, (v, 21)), angle_sigma, s.flags(mirror),
-                                          loss=loss, loss_scale=loss_scale)
+    outs = _native.pose_information_views(s.blob, s.f32(joint_angles, (22,)), s.f32(wrist_transforms, (4, 4)), *views, weights,
+                                          angle_sigma, s.flags(mirror), loss=loss, loss_scale=loss_scale)
     return unpack_uncertainty(*outs, lead=s.lead, device=s.src_device)
 
 
@@ -407,17 +405,27 @@ def calibrate_scale(hand_model: HandModel, landmarks: torch.Tensor, weights: Opt
     if landmarks.dim() < 3:
         raise ValueError(f"landmarks must be [...,N,21,3], got {tuple(landmarks.shape)}")
     s, args = _scale_fit_inputs(hand_model, landmarks, weights, None, None, False, mirror)
+
+    def fixed_pass(ja, xf, pose_scale):
+        return _native.fit_pose_scale(scale_mode=_native.UT_SCALE_FIXED, max_iters=max_iters,
+                                      **dict(args, init_scale=pose_scale, init_angles=ja, init_wrist_xf=xf))
+    return _pooled_calibration(hand_model, s, _native.fit_pose_scale(max_iters=max_iters, **args), fixed_pass, refit, "calibrate_scale")
+
+
+def _pooled_calibration(hand_model: HandModel, s: _FitStaging, free, fixed_pass, refit: bool, who: str) -> ScaleCalibration:
+    """The tail calibrate_scale and calibrate_scale_in_views share: free = (joint_angles, wrist_xf, scale, info) of the free pass
+    over s.n poses, pooled over the last leading dim; with refit, fixed_pass(joint_angles, wrist_xf, pose_scale) runs the fixed
+    pass from them at the pooled scales; `who` names the caller when a group has no usable pose."""
+    ja, xf, scale, info = free
     group_lead, n_per = s.lead[:-1], s.lead[-1]
-    ja, xf, scale, info = _native.fit_pose_scale(max_iters=max_iters, **args)
     group, pose_scale = _native.pool_scale(scale, info, n_per)
     if refit:
-        args.update(init_scale=pose_scale, init_angles=ja, init_wrist_xf=xf)
-        ja, xf, pose_scale, info = _native.fit_pose_scale(scale_mode=_native.UT_SCALE_FIXED, max_iters=max_iters, **args)
+        ja, xf, pose_scale, info = fixed_pass(ja, xf, pose_scale)
     else:
         pose_scale = scale
     stats = group.reshape(group_lead + (4,)).to(s.src_device)
     if bool((stats[..., 3] == 0).any()):
-        raise ValueError("calibrate_scale: a group has no usable pose (none converged away from the scale bounds)")
+        raise ValueError(f"{who}: a group has no usable pose (none converged away from the scale bounds)")
     pooled = stats[..., 0]
     model = None
     if group_lead == () and hand_model.joint_rest_positions.dim() == 2:
@@ -430,15 +438,10 @@ def _views_scale_inputs(hand_model: HandModel, window, cam_rows, table, init, in
     the device: (staging, V, positional arguments, keyword arguments)."""
     if init is None:
         raise ValueError(f"init = (joint_angles, wrist_transforms) is required: {who} has no cold start")
-    if window.dim() < 3 or tuple(window.shape[-2:]) != (21, 2):
-        raise ValueError(f"window must be [...,V,21,2], got {tuple(window.shape)}")
-    v = window.shape[-3]
-    s = _FitStaging(hand_model, tuple(window.shape[:-3]), window.device, limits, "limits")
+    s, v, views, weights = _views_staging(hand_model, window, cam_rows, table, weights, limits)
     if init_scale is not None:
         init_scale = torch.as_tensor(init_scale).expand(s.lead)
-    args = (s.blob, s.f32(window, (v, 21, 2), torch.float64), s.f32(cam_rows, (v,), torch.int32), table.to(s.dev, torch.float64),
-            *s.init(init))
-    return s, v, args, dict(weights=s.f32(weights, (v, 21)), limits=s.box, init_scale=s.f32(init_scale, ()), mirror=s.flags(mirror))
+    return s, v, (s.blob, *views, *s.init(init)), dict(weights=weights, limits=s.box, init_scale=s.f32(init_scale, ()), mirror=s.flags(mirror))
 
 
 def fit_landmarks_views_scale(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, init,
@@ -479,23 +482,11 @@ def calibrate_scale_in_views(hand_model: HandModel, window: torch.Tensor, cam_ro
         raise ValueError(f"window must be [...,N,V,21,2], got {tuple(window.shape)}")
     s, _v, args, kw = _views_scale_inputs(hand_model, window, cam_rows, table, init, init_scale, weights, mirror, None,
                                           "calibrate_scale_in_views")
-    group_lead, n_per = s.lead[:-1], s.lead[-1]
-    common = dict(max_iters=max_iters, loss=loss, loss_scale=loss_scale)
-    ja, xf, scale, info = _native.fit_pose_views_scale(*args, **common, **kw)
-    group, pose_scale = _native.pool_scale(scale, info, n_per)
-    if refit:
-        kw.update(init_scale=pose_scale)
-        ja, xf, pose_scale, info = _native.fit_pose_views_scale(*args[:4], ja, xf, scale_mode=_native.UT_SCALE_FIXED, **common, **kw)
-    else:
-        pose_scale = scale
-    stats = group.reshape(group_lead + (4,)).to(s.src_device)
-    if bool((stats[..., 3] == 0).any()):
-        raise ValueError("calibrate_scale_in_views: a group has no usable pose (none converged away from the scale bounds)")
-    pooled = stats[..., 0]
-    model = None
-    if group_lead == () and hand_model.joint_rest_positions.dim() == 2:
-        model = scaled_hand_model(hand_model, float(pooled))
-    return ScaleCalibration(pooled, stats, model, s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(info, (6,)), s.back(pose_scale, ()))
+    kw.update(max_iters=max_iters, loss=loss, loss_scale=loss_scale)
+
+    def fixed_pass(ja, xf, pose_scale):
+        return _native.fit_pose_views_scale(*args[:4], ja, xf, scale_mode=_native.UT_SCALE_FIXED, **dict(kw, init_scale=pose_scale))
+    return _pooled_calibration(hand_model, s, _native.fit_pose_views_scale(*args, **kw), fixed_pass, refit, "calibrate_scale_in_views")
 
 
 _MESH_FIELDS = ("mesh_vertices", "mesh_triangles", "dense_bone_weights")

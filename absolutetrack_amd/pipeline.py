@@ -249,11 +249,8 @@ def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_p
     (and angle_sigma f32 [1|n,20] or None, the prior of _native.pose_information_views); its hand.PoseUncertainty is the last
     item.  Off, the result is what it was without the keyword."""
     kw = dict(weights=weights, limits=limits, mirror=mirror, t_scale=t_scale, max_iters=max_iters, residual=with_residual, engine=engine, **strided)
-    if _native.loss_code(loss) == _native.UT_LOSS_SQUARED and not with_inliers:
-        res = _native.fit_pose_views(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, **kw)
-    else:
-        res = _native.fit_pose_views_robust(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, loss=loss,
-                                            loss_scale=loss_scale, inlier=with_inliers, **kw)
+    res = _native.fit_pose_views_any_loss(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, loss=loss,
+                                          loss_scale=loss_scale, inlier=with_inliers, **kw)
     if not with_uncertainty:
         return res
     outs = _native.pose_information_views(hand_model, res[0], res[1], window, src_row, cam_params, weights=weights, angle_sigma=angle_sigma,

@@ -66,6 +66,23 @@ def _left_handed(wrist_xform: np.ndarray, hand_idx: int) -> np.ndarray:
     return xf
 
 
+def _mirror_flag(hand_idx: int) -> torch.Tensor:
+    """The `mirror` of one hand for the hand.py wrappers: 1 for the right hand."""
+    return torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0)
+
+
+def _start_tensors(pose: Optional[SingleHandPose]):
+    """A pose as the `init` of the hand.py fits: (joint_angles, wrist_transforms) float32 tensors, None for None."""
+    if pose is None:
+        return None
+    return torch.from_numpy(np.asarray(pose.joint_angles, np.float32)), torch.from_numpy(np.asarray(pose.wrist_xform, np.float32))
+
+
+def _pose_from_fit(ja: torch.Tensor, xf: torch.Tensor, fit_info: torch.Tensor) -> SingleHandPose:
+    """The pose a fit returned: hand_confidence is 1 when it converged, else 0."""
+    return SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(), hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0)
+
+
 def landmarks_from_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, hand_idx: int) -> np.ndarray:
     """World-space landmarks [21,3] of a pose (lib/tracker/perspective_crop.py:40-51)."""
     hit = _landmark_memo.get(hand_model, hand_idx, hand_pose.joint_angles, hand_pose.wrist_xform)
@@ -83,11 +100,7 @@ def hand_pose_from_landmarks(hand_model: HandModel, landmarks: np.ndarray, hand_
     the landmarks.  hand_confidence is 1 when the fit converged and 0 when it stopped at its iteration limit or refused
     the landmarks (not finite)."""
     kp = torch.from_numpy(np.ascontiguousarray(landmarks, np.float32)).reshape(21, 3)
-    start = None if init is None else (torch.from_numpy(np.asarray(init.joint_angles, np.float32)),
-                                       torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
-    ja, xf, info = fit_landmarks(hand_model, kp, init=start, mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
-    return SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(),
-                          hand_confidence=1.0 if int(info[3]) & FIT_CONVERGED else 0.0)
+    return _pose_from_fit(*fit_landmarks(hand_model, kp, init=_start_tensors(init), mirror=_mirror_flag(hand_idx)))
 
 
 def hand_poses_from_keypoints(hand_model: HandModel, keypoints: np.ndarray, valid: np.ndarray
@@ -144,8 +157,7 @@ def mesh_from_hand_pose(hand_model: HandModel, hand_pose: SingleHandPose, hand_i
     landmarks_from_hand_pose.  The hand model is a left hand: right hands get column 0 of the wrist transform negated, on
     the device (the same values as _left_handed gives), so that the normals of both hands point outwards."""
     res = skin_mesh(hand_model, torch.from_numpy(np.asarray(hand_pose.joint_angles)).float(),
-                    torch.from_numpy(np.asarray(hand_pose.wrist_xform)).float(), normals=normals,
-                    mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
+                    torch.from_numpy(np.asarray(hand_pose.wrist_xform)).float(), normals=normals, mirror=_mirror_flag(hand_idx))
     if normals:
         return res[0].cpu().numpy(), res[1].cpu().numpy()
     return res.cpu().numpy()
@@ -203,6 +215,21 @@ def _native_camera_table(cameras: List[CameraModel], who: str) -> np.ndarray:
     return np.stack([geometry.pack_camera_model(c) for c in cameras])
 
 
+def _window_inputs(who: str, cameras: List[CameraModel], window, weights, shape, name: str = "window_keypoints"):
+    """What the functions on detections in the cameras check alike: (the cameras' kernel table, `window` as a contiguous float64
+    array of `shape` - a dimension given by its name is free -, weights as float32 with the window's dims but the last, or None).
+    `name` is how the caller's message calls the window."""
+    table = _native_camera_table(cameras, who)
+    win = np.ascontiguousarray(window, np.float64)
+    if win.ndim != len(shape) or any(not isinstance(e, str) and e != d for e, d in zip(shape, win.shape)):
+        raise ValueError(f"{name} must be [{','.join(map(str, shape))}], got {win.shape}")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float32)
+        if weights.shape != win.shape[:-1]:
+            raise ValueError(f"weights must be {win.shape[:-1]}, got {weights.shape}")
+    return table, win, weights
+
+
 def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weights: Optional[np.ndarray] = None,
                           with_information: bool = False):
     """The inverse of project_landmarks: window coordinates [n_cams,P,2] of P points in every camera -> (world points [P,3]
@@ -213,14 +240,7 @@ def triangulate_landmarks(cameras: List[CameraModel], window: np.ndarray, weight
     is no host implementation.  with_information=True: one ut_triangulate_points_info launch instead, and a third result,
     sqrt_info [P,6] float32 - the lower Cholesky factor (l00, l10, l11, l20, l21, l22) of each point's 3 x 3 information
     matrix, px per mm, all 0 where the point carries none: what hand.fit_landmarks_info reads."""
-    table = _native_camera_table(cameras, "triangulate_landmarks")
-    win = np.ascontiguousarray(window, np.float64)
-    if win.ndim != 3 or win.shape[0] != len(cameras) or win.shape[2] != 2:
-        raise ValueError(f"window must be [{len(cameras)},P,2], got {win.shape}")
-    if weights is not None:
-        weights = np.ascontiguousarray(weights, np.float32)
-        if weights.shape != win.shape[:2]:
-            raise ValueError(f"weights must be {win.shape[:2]}, got {weights.shape}")
+    table, win, weights = _window_inputs("triangulate_landmarks", cameras, window, weights, (len(cameras), "P", 2), "window")
     dev = fk_device()
     rows = torch.arange(len(cameras), dtype=torch.int32, device=dev)[None]
     entry = _native.triangulate_points_info if with_information else _native.triangulate_points
@@ -264,19 +284,11 @@ def hand_pose_uncertainty_in_views(hand_model: HandModel, cameras: List[CameraMo
     are informations (1 / sigma^2 in px^-2 makes the result absolute; None = per px^2 of detection noise), loss / loss_scale those
     of the fit that produced the pose, angle_sigma [20] rad an optional prior on the joint angles.  Cameras as for
     triangulate_landmarks."""
-    table = _native_camera_table(cameras, "hand_pose_uncertainty_in_views")
-    win = np.ascontiguousarray(window_keypoints, np.float64)
-    if win.shape != (len(cameras), 21, 2):
-        raise ValueError(f"window_keypoints must be [{len(cameras)},21,2], got {win.shape}")
-    if weights is not None:
-        weights = np.ascontiguousarray(weights, np.float32)
-        if weights.shape != win.shape[:2]:
-            raise ValueError(f"weights must be {win.shape[:2]}, got {weights.shape}")
+    table, win, weights = _window_inputs("hand_pose_uncertainty_in_views", cameras, window_keypoints, weights, (len(cameras), 21, 2))
     unc = pose_uncertainty_views(
-        hand_model, torch.from_numpy(np.asarray(pose.joint_angles, np.float32)), torch.from_numpy(np.asarray(pose.wrist_xform, np.float32)),
-        torch.from_numpy(win), torch.arange(len(cameras), dtype=torch.int32), torch.from_numpy(table),
+        hand_model, *_start_tensors(pose), torch.from_numpy(win), torch.arange(len(cameras), dtype=torch.int32), torch.from_numpy(table),
         weights=None if weights is None else torch.from_numpy(weights), angle_sigma=angle_sigma, loss=loss, loss_scale=loss_scale,
-        mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
+        mirror=_mirror_flag(hand_idx))
     return type(unc)(*(t.numpy() for t in unc))
 
 
@@ -293,21 +305,13 @@ def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel],
     wrong finger); a fourth item then, inlier [n_cams,21]: psi of every used detection at the returned pose, 1 an inlier, towards
     0 an outlier.  The default "squared" returns the three items it always did.  return_uncertainty=True: a last item more, the
     hand.PoseUncertainty of the returned pose under the same loss, weights and views (hand_pose_uncertainty_in_views)."""
-    table = _native_camera_table(cameras, "refine_hand_pose_in_views")
-    win = np.ascontiguousarray(window_keypoints, np.float64)
-    if win.shape != (len(cameras), 21, 2):
-        raise ValueError(f"window_keypoints must be [{len(cameras)},21,2], got {win.shape}")
-    if weights is not None:
-        weights = np.ascontiguousarray(weights, np.float32)
-        if weights.shape != win.shape[:2]:
-            raise ValueError(f"weights must be {win.shape[:2]}, got {weights.shape}")
-    start = (torch.from_numpy(np.asarray(init.joint_angles, np.float32)), torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
+    table, win, weights = _window_inputs("refine_hand_pose_in_views", cameras, window_keypoints, weights, (len(cameras), 21, 2))
     robust = _native.loss_code(loss) != _native.UT_LOSS_SQUARED
     ja, xf, fit_info, residual, *inlier = fit_landmarks_views(
-        hand_model, torch.from_numpy(win), torch.arange(len(cameras), dtype=torch.int32), torch.from_numpy(table), start,
-        weights=None if weights is None else torch.from_numpy(weights), mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0),
+        hand_model, torch.from_numpy(win), torch.arange(len(cameras), dtype=torch.int32), torch.from_numpy(table), _start_tensors(init),
+        weights=None if weights is None else torch.from_numpy(weights), mirror=_mirror_flag(hand_idx),
         with_residual=True, loss=loss, loss_scale=loss_scale, return_inliers=robust)
-    pose = SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(), hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0)
+    pose = _pose_from_fit(ja, xf, fit_info)
     out = (pose, fit_info.numpy(), residual.numpy()) + tuple(r.numpy() for r in inlier)
     if return_uncertainty:
         out += (hand_pose_uncertainty_in_views(hand_model, cameras, win, hand_idx, pose, weights, loss, loss_scale),)
@@ -323,27 +327,19 @@ def _chain_pose_from_window_keypoints(hand_model, cameras, window_keypoints, han
     if pts.shape[0] != 21:
         raise ValueError(f"window_keypoints must be [{len(cameras)},21,2], got {np.shape(window_keypoints)}")
     if use_information:
-        flip = torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0)
+        flip = _mirror_flag(hand_idx)
         target, used = torch.from_numpy(pts.astype(np.float32)), torch.from_numpy((factor != 0).any(-1).astype(np.float32))
-        start = None if init is None else (torch.from_numpy(np.asarray(init.joint_angles, np.float32)),
-                                           torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
+        start = _start_tensors(init)
         if start is not None:
             start = fit_landmarks(hand_model, target, weights=used, init=start, mirror=flip)[:2]
-        ja, xf, fit_info = fit_landmarks_info(hand_model, target, torch.from_numpy(factor), init=start, mirror=flip)
-        return SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(),
-                              hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0), info
+        return _pose_from_fit(*fit_landmarks_info(hand_model, target, torch.from_numpy(factor), init=start, mirror=flip)), info
     sigma = info[:, 1].astype(np.float64)
     ok = np.isfinite(sigma) & (sigma > 0)
     lw = np.zeros(21, np.float32)
     if ok.any():
         lw[ok] = (sigma[ok].min() / sigma[ok]) ** 2
-    start = None if init is None else (torch.from_numpy(np.asarray(init.joint_angles, np.float32)),
-                                       torch.from_numpy(np.asarray(init.wrist_xform, np.float32)))
-    ja, xf, fit_info = fit_landmarks(hand_model, torch.from_numpy(pts.astype(np.float32)), weights=torch.from_numpy(lw), init=start,
-                                     mirror=torch.tensor(1 if hand_idx == RIGHT_HAND_INDEX else 0))
-    pose = SingleHandPose(joint_angles=ja.numpy(), wrist_xform=xf.numpy(),
-                          hand_confidence=1.0 if int(fit_info[3]) & FIT_CONVERGED else 0.0)
-    return pose, info
+    return _pose_from_fit(*fit_landmarks(hand_model, torch.from_numpy(pts.astype(np.float32)), weights=torch.from_numpy(lw),
+                                         init=_start_tensors(init), mirror=_mirror_flag(hand_idx))), info
 
 
 def calibrate_hand_model_from_keypoints(hand_model: HandModel, keypoints: np.ndarray, valid: np.ndarray,
@@ -382,14 +378,8 @@ def calibrate_hand_model_from_window_keypoints(hand_model: HandModel, cameras: L
     views), which roughly halves the scale's error on the same detections and keeps the frames the 3-D chain cannot use; sigma
     and scatter of the result are then per px.  loss, loss_scale: the passes' in the views, as for refine_hand_pose_in_views; not
     read without refine_in_views.  The cameras must see the hand from two places: one camera cannot see its size."""
-    table = _native_camera_table(cameras, "calibrate_hand_model_from_window_keypoints")
-    win = np.ascontiguousarray(window_keypoints, np.float64)
-    if win.ndim != 4 or win.shape[1:] != (len(cameras), 21, 2):
-        raise ValueError(f"window_keypoints must be [n_frames,{len(cameras)},21,2], got {win.shape}")
-    if weights is not None:
-        weights = np.ascontiguousarray(weights, np.float32)
-        if weights.shape != win.shape[:3]:
-            raise ValueError(f"weights must be {win.shape[:3]}, got {weights.shape}")
+    table, win, weights = _window_inputs("calibrate_hand_model_from_window_keypoints", cameras, window_keypoints, weights,
+                                         ("n_frames", len(cameras), 21, 2))
     dev = fk_device()
     n = win.shape[0]
     rows = torch.arange(len(cameras), dtype=torch.int32, device=dev)[None].expand(n, -1).contiguous()
