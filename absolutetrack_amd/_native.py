@@ -121,6 +121,12 @@ _UNCERTAINTY_PROTOTYPES = {
                                          _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 UNCERTAINTY_EXPORTS = tuple(_UNCERTAINTY_PROTOTYPES)
+# The entry of include/umetrack_hip_smooth.h, in a table of its own like its header (tests/test_smooth_host.py pins it).
+_SMOOTH_PROTOTYPES = {
+    "ut_smooth_pose_sequence": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _vp, _vp, _i32,
+                                       _vp, _i32, _vp, _vp, _vp]),
+}
+SMOOTH_EXPORTS = tuple(_SMOOTH_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -146,7 +152,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
                                       **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES, **_ROBUST_PROTOTYPES,
-                                      **_VIEWS_SCALE_PROTOTYPES, **_UNCERTAINTY_PROTOTYPES}.items():
+                                      **_VIEWS_SCALE_PROTOTYPES, **_UNCERTAINTY_PROTOTYPES, **_SMOOTH_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -856,6 +862,77 @@ def pose_information_views(hand_model: torch.Tensor, joint_angles: torch.Tensor,
               _ptr(table), table.shape[0], kind, _ptr(angle_sigma), _ptr(joint_angles), ja_stride, _ptr(wrist_xf), xf_stride,
               _ptr(mirror), ctypes.c_float(t_scale), code, ctypes.c_float(loss_scale), n, *map(_ptr, outs))
     return outs
+
+
+UT_SMOOTH_OK, UT_SMOOTH_SINGULAR, UT_SMOOTH_REFUSED, UT_SMOOTH_GAP = 1, 2, 4, 8
+UT_SMOOTH_WORK = 408
+
+
+def smooth_pose_sequence(joint_angles: torch.Tensor, wrist_xf: torch.Tensor, pose_info: torch.Tensor, pivot: torch.Tensor,
+                         step_var: torch.Tensor, frame_weight: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+                         centre: Optional[torch.Tensor] = None, t_scale: float = 1.0, *, n_seq: Optional[int] = None,
+                         n_frames: Optional[int] = None, ja_stride: int = 22, xf_stride: int = 16,
+                         out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_out_stride: int = 22, xf_out_stride: int = 16,
+                         param_sigma=False, info=True, workspace: Optional[torch.Tensor] = None, engine: Optional["HipEngine"] = None):
+    """ut_smooth_pose_sequence: the fitted poses of n_seq sequences of n_frames frames (joint_angles [n_seq,T,22], wrist_xf
+    [n_seq,T,4,4]) combined by their information matrices (pose_info [n_seq,T,351] and pivot [n_seq,T,3] of
+    pose_information_views) under a random walk with the variances step_var f32 [1|n_seq,26] per frame step (rad^2, rad^2, target
+    units^2) - include/umetrack_hip_smooth.h states the model.  frame_weight f32 [n_seq,T] >= 0 or None = 1 (0: the frame is a
+    gap), lengths i32 [n_seq] or None, centre f32 [n_seq,3] or None: the body-fixed point the motion model speaks about, in the
+    proper wrist frame and target units.  Returns (joint_angles, wrist_xf, param_sigma [n_seq,T,26] or None, info [n_seq,T,4] or
+    None: sqrt(u^T H' u), sqrt(m^T W m) of the smoothed step, the smallest scaled pivot, status bits UT_SMOOTH_*).  param_sigma /
+    info: True = a fresh tensor, False = left out, or a preallocated contiguous f32 tensor.  out: preallocated (joint_angles,
+    wrist_xf) - they may be the inputs themselves.  With n_seq and n_frames given, the poses are fp32 views read in place (and `out`
+    written) with the strides given in floats.  workspace: a contiguous f32 tensor of at least n_seq * T * UT_SMOOTH_WORK elements,
+    or None = a fresh one.  No device status word: nothing synchronises, the call is capturable."""
+    d = _hip_device(pose_info, "smooth_pose_sequence")
+    if n_seq is None or n_frames is None:
+        if joint_angles.dim() != 3 or joint_angles.shape[2] != 22:
+            raise ValueError(f"joint_angles must be [n_seq,T,22], got {tuple(joint_angles.shape)}")
+        n_seq, n_frames = joint_angles.shape[:2]
+        joint_angles = _need(joint_angles, torch.float32, d, "joint_angles")
+        wrist_xf = _need(wrist_xf, torch.float32, d, "wrist_xf")
+        if tuple(wrist_xf.shape) != (n_seq, n_frames, 4, 4):
+            raise ValueError(f"wrist_xf must be [{n_seq},{n_frames},4,4], got {tuple(wrist_xf.shape)}")
+    elif joint_angles.device != d or wrist_xf.device != d or joint_angles.dtype != torch.float32 or wrist_xf.dtype != torch.float32:
+        raise ValueError(f"strided pose views must be fp32 on {d}")
+    n = n_seq * n_frames
+    if n_frames < 1:
+        raise ValueError("n_frames must be at least 1")
+    pose_info, pivot = _need(pose_info, torch.float32, d, "pose_info"), _need(pivot, torch.float32, d, "pivot")
+    if pose_info.numel() != n * 351 or pivot.numel() != n * 3:
+        raise ValueError(f"pose_info / pivot must hold [{n_seq},{n_frames},351] / [{n_seq},{n_frames},3]")
+    step_var = _need(step_var, torch.float32, d, "step_var").reshape(-1, 26)
+    if step_var.shape[0] not in (1, n_seq) and n_seq:
+        raise ValueError(f"step_var has {step_var.shape[0]} rows for {n_seq} sequences")
+    if frame_weight is not None:
+        frame_weight = _need(frame_weight, torch.float32, d, "frame_weight")
+        if frame_weight.numel() != n:
+            raise ValueError(f"frame_weight must be [{n_seq},{n_frames}]")
+    if lengths is not None:
+        lengths = _need(lengths, torch.int32, d, "lengths")
+        if lengths.numel() != n_seq:
+            raise ValueError(f"lengths must be [{n_seq}]")
+    if centre is not None:
+        centre = _need(centre, torch.float32, d, "centre")
+        if centre.numel() != n_seq * 3:
+            raise ValueError(f"centre must be [{n_seq},3]")
+    if out is None:
+        out = (torch.empty((n_seq, n_frames, 22), dtype=torch.float32, device=d), torch.empty((n_seq, n_frames, 4, 4), dtype=torch.float32, device=d))
+        ja_out_stride, xf_out_stride = 22, 16
+    elif any(o.device != d or o.dtype != torch.float32 for o in out):
+        raise ValueError(f"out must be fp32 on {d}")
+    if workspace is None:
+        workspace = torch.empty((max(n, 1), UT_SMOOTH_WORK), dtype=torch.float32, device=d)
+    elif workspace.device != d or workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() < n * UT_SMOOTH_WORK:
+        raise ValueError(f"workspace must be a contiguous f32 tensor of at least {n * UT_SMOOTH_WORK} elements on {d}")
+    param_sigma = _optional_out(param_sigma, (n_seq, n_frames, 26), d, "param_sigma")
+    info = _optional_out(info, (n_seq, n_frames, 4), d, "info")
+    h = engine._h if engine is not None else None
+    _fit_call("ut_smooth_pose_sequence", d, h, _ptr(joint_angles), ja_stride, _ptr(wrist_xf), xf_stride, _ptr(pose_info), _ptr(pivot),
+              _ptr(frame_weight), _ptr(lengths), _ptr(centre), _ptr(step_var), step_var.shape[0], ctypes.c_float(t_scale), n_seq, n_frames,
+              _ptr(workspace), _ptr(out[0]), ja_out_stride, _ptr(out[1]), xf_out_stride, _ptr(param_sigma), _ptr(info))
+    return out[0], out[1], param_sigma, info
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

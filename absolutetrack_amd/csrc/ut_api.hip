@@ -6,6 +6,7 @@
 #include "../../include/umetrack_hip_info.h"
 #include "../../include/umetrack_hip_robust.h"
 #include "../../include/umetrack_hip_scale.h"
+#include "../../include/umetrack_hip_smooth.h"
 #include "../../include/umetrack_hip_triangulate.h"
 #include "../../include/umetrack_hip_uncertainty.h"
 #include "../../include/umetrack_hip_views.h"
@@ -1650,6 +1651,37 @@ int ut_pose_information_views(ut_handle h, const float* hand_model, int n_models
   if (rc) return rc;
   return launch_in_views(h, who, b.robust.views, stream, [&](hipStream_t s) -> int {
     HIPCHK(h, ut::launch_pose_information_views(b, s)); return UT_OK; });
+}
+
+static_assert(UT_SMOOTH_OK == ut::SMOOTH_OK && UT_SMOOTH_GAP == ut::SMOOTH_GAP && UT_SMOOTH_SINGULAR == ut::SMOOTH_SINGULAR &&
+              UT_SMOOTH_REFUSED == ut::SMOOTH_REFUSED && UT_SMOOTH_REFUSED == UT_FIT_REFUSED && UT_SMOOTH_WORK == ut::SMOOTH_WORK,
+              "umetrack_hip_smooth.h and ut_kernels.h");
+
+int ut_smooth_pose_sequence(ut_handle h, const float* joint_angles, int ja_stride, const float* wrist_xf, int xf_stride,
+                            const float* pose_info, const float* pivot, const float* frame_weight, const int32_t* lengths,
+                            const float* centre, const float* step_var, int n_var, float t_scale, int n_seq, int n_frames,
+                            float* workspace, float* joint_angles_out, int ja_out_stride, float* wrist_xf_out, int xf_out_stride,
+                            float* param_sigma, float* info, void* stream) {
+  // stateless like ut_fit_pose: h may be NULL
+  const char* who = "ut_smooth_pose_sequence";
+  if (!joint_angles || !wrist_xf) return fail_as(h, who, "joint_angles and wrist_xf are required");
+  if (!pose_info || !pivot) return fail_as(h, who, "pose_info and pivot are required");
+  if (!step_var) return fail_as(h, who, "step_var is required");
+  if (!workspace) return fail_as(h, who, "workspace is required");
+  if (!joint_angles_out || !wrist_xf_out) return fail_as(h, who, "joint_angles_out and wrist_xf_out are required");
+  if (ja_stride < 22 || xf_stride < 12 || ja_out_stride < 22 || xf_out_stride < 12)
+    return fail_as(h, who, "a stride is below 22 (angles) / 12 (wrist)");
+  if (n_seq < 0) return fail_as(h, who, "n_seq is negative");
+  if (n_frames < 1) return fail_as(h, who, "n_frames must be at least 1");
+  if (n_var != 1 && n_var != n_seq) return fail_as(h, who, "n_var must be 1 or n_seq");
+  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f)) return fail_as(h, who, "t_scale must be positive and finite");
+  if (n_seq == 0) return UT_OK;
+  const ut::SmoothArgs a{joint_angles, ja_stride, wrist_xf, xf_stride, pose_info, pivot, frame_weight, lengths, centre, step_var, n_var,
+                         t_scale, n_seq, n_frames, workspace, joint_angles_out, ja_out_stride, wrist_xf_out, xf_out_stride,
+                         param_sigma, info};
+  ON_DEVICE_IF(h);
+  HIPCHK(h, ut::launch_smooth_pose_sequence(a, (hipStream_t)stream));
+  return UT_OK;
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

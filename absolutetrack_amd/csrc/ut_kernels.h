@@ -485,6 +485,29 @@ struct PoseInfoViewsArgs {
 };
 hipError_t launch_pose_information_views(const PoseInfoViewsArgs& a, hipStream_t s);
 
+// smooth.hip: fitted poses smoothed over a sequence by their information matrices (ut_smooth_pose_sequence).  Pointers as
+// ut_smooth_pose_sequence documents them; the constants are public as UT_SMOOTH_*.
+enum : int { SMOOTH_OK = 1, SMOOTH_SINGULAR = 2, SMOOTH_REFUSED = FIT_REFUSED, SMOOTH_GAP = 8 };
+constexpr int SMOOTH_WORK = 408;
+struct SmoothArgs {
+  const float* ja; int ja_stride;
+  const float* xf; int xf_stride;
+  const float* pose_info;               // [n_seq * n_frames,351]
+  const float* pivot;                   // [n_seq * n_frames,3]
+  const float* frame_weight;            // [n_seq * n_frames] or null
+  const int32_t* lengths;               // [n_seq] or null
+  const float* centre;                  // [n_seq,3] or null
+  const float* step_var; int n_var;     // [n_var,26]
+  float t_scale;
+  int n_seq, n_frames;
+  float* workspace;                     // [n_seq * n_frames,SMOOTH_WORK]
+  float* ja_out; int ja_out_stride;
+  float* xf_out; int xf_out_stride;
+  float* param_sigma;                   // [n_seq * n_frames,26] or null
+  float* info;                          // [n_seq * n_frames,4] or null
+};
+hipError_t launch_smooth_pose_sequence(const SmoothArgs& a, hipStream_t s);
+
 // Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
 //  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
 //           bone, unused slots weight 0 / bone 0

@@ -352,6 +352,61 @@ def pose_uncertainty_views(hand_model: HandModel, joint_angles: torch.Tensor, wr
     return unpack_uncertainty(*outs, lead=s.lead, device=s.src_device)
 
 
+SMOOTH_OK, SMOOTH_SINGULAR, SMOOTH_REFUSED, SMOOTH_GAP = (_native.UT_SMOOTH_OK, _native.UT_SMOOTH_SINGULAR, _native.UT_SMOOTH_REFUSED,
+                                                            _native.UT_SMOOTH_GAP)
+
+
+def step_sigma_from_rates(angle_rate: float, rotation_rate: float, speed: float, fps: float) -> torch.Tensor:
+    """[26] step_sigma of smooth_poses from what a hand does per second: the joint angles' rate (rad / s), the wrist's turning
+    rate (rad / s) and the hand's speed (landmark units / s), each as a standard deviation, at `fps` frames per second.  A random
+    walk: the sigma of one frame step is the rate over fps."""
+    if not fps > 0:
+        raise ValueError("fps must be positive")
+    return torch.tensor([angle_rate / fps] * 20 + [rotation_rate / fps] * 3 + [speed / fps] * 3, dtype=torch.float32)
+
+
+def smooth_poses(hand_model: HandModel, joint_angles: torch.Tensor, wrist_transforms: torch.Tensor, uncertainty, step_sigma,
+                 frame_weight: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+                 mirror: Optional[torch.Tensor] = None, centre: Optional[torch.Tensor] = None, return_sigma: bool = False):
+    """A sequence of fitted poses smoothed by their information matrices, on the HIP kernel csrc/smooth.hip (no CPU
+    implementation): joint_angles [...,T,22] and wrist_transforms [...,T,4,4] are the fits of T consecutive frames, `uncertainty`
+    their PoseUncertainty (pose_uncertainty_views; leading dims [...,T]) or the pair (pose_info [...,T,26,26] or packed
+    [...,T,351], pivot [...,T,3]).  Every fit is a Gaussian measurement of the true pose, consecutive poses differ by a random
+    walk with the standard deviations step_sigma [26] or [...,26] per frame step (20 angles rad, rotation rad, translation in the
+    landmarks' units: step_sigma_from_rates), and the result is the most probable sequence - one linear solve, first order in
+    the rotation (include/umetrack_hip_smooth.h).  frame_weight [...,T] >= 0 multiplies a frame's information: 0 makes the frame
+    a gap that the motion model fills in, as a refused fit (information 0) is.  lengths [...] i32: frames at or past a
+    sequence's length are copied through.  centre [...,3] or [3]: the body-fixed point whose motion step_sigma's translation
+    describes, in the wrist's frame; default the mean of hand_model.landmark_rest_positions (mirror [...] of 0 / 1: x negated
+    where 1, as the landmarks of a mirrored hand are).  Returns (joint_angles, wrist_transforms, info [...,T,4]: how many of its
+    own sigmas the frame was moved, the smoothed step in step sigmas, the smallest scaled pivot, status SMOOTH_OK (| SMOOTH_GAP) /
+    SMOOTH_SINGULAR (no frame observes some direction: poses unchanged) / SMOOTH_REFUSED) and, with return_sigma=True, param_sigma
+    [...,T,26] of the smoothed poses - its translation is that of `centre`."""
+    if joint_angles.dim() < 2 or joint_angles.shape[-1] != 22:
+        raise ValueError(f"joint_angles must be [...,T,22], got {tuple(joint_angles.shape)}")
+    lead, frames = tuple(joint_angles.shape[:-2]), joint_angles.shape[-2]
+    src = joint_angles.device
+    dev = src if src.type == "cuda" else fk_device()
+    n_seq = int(np.prod(lead)) if lead else 1
+    pose_info, pivot = (uncertainty.pose_info, uncertainty.pivot) if isinstance(uncertainty, PoseUncertainty) else uncertainty
+    if pose_info.shape[-1] == 26 and pose_info.dim() >= 2 and pose_info.shape[-2] == 26:
+        pose_info = pose_info[..., _TRIL[0], _TRIL[1]]
+    put = lambda t, tail, dtype=torch.float32: None if t is None else torch.as_tensor(t).expand(lead + tail).reshape((n_seq,) + tail).to(dev, dtype).contiguous()
+    step_var = torch.as_tensor(step_sigma, dtype=torch.float32)
+    step_var = (step_var * step_var).reshape(1, 26) if step_var.numel() == 26 else put(step_var * step_var, (26,))
+    if centre is None:
+        centre = torch.as_tensor(hand_model.landmark_rest_positions).reshape(-1, 21, 3)[0].to(torch.float64).mean(0).to(torch.float32)
+        centre = centre.expand(lead + (3,)).clone()
+        if mirror is not None:
+            centre[..., 0] = torch.where(torch.as_tensor(mirror).expand(lead) == 1, -centre[..., 0], centre[..., 0])
+    ja, xf, sigma, info = _native.smooth_pose_sequence(
+        put(joint_angles, (frames, 22)), put(wrist_transforms, (frames, 4, 4)), put(pose_info, (frames, 351)), put(pivot, (frames, 3)),
+        step_var.to(dev), put(frame_weight, (frames,)), put(lengths, (), torch.int32), put(centre, (3,)), param_sigma=bool(return_sigma))
+    back = lambda t, tail: t.reshape(lead + (frames,) + tail).to(src)
+    out = (back(ja, (22,)), back(xf, (4, 4)), back(info, (4,)))
+    return out + ((back(sigma, (26,)),) if return_sigma else ())
+
+
 FITS_CONVERGED, FITS_AT_MAX_ITERS, FITS_REFUSED, FITS_AT_BOUND = (_native.UT_FITS_CONVERGED, _native.UT_FITS_AT_MAX_ITERS,
                                                                   _native.UT_FITS_REFUSED, _native.UT_FITS_AT_BOUND)
 

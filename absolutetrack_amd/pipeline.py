@@ -259,6 +259,37 @@ def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_p
     return res + (unpack_uncertainty(*outs),)
 
 
+def smooth_fitted_sequence(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
+                           init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, step_var: torch.Tensor, n_seq: int,
+                           weights: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                           max_iters: int = 32, loss="squared", loss_scale: float = 3.0, angle_sigma: Optional[torch.Tensor] = None,
+                           frame_weight: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+                           centre: Optional[torch.Tensor] = None, with_sigma: bool = False, engine: Optional[_native.HipEngine] = None):
+    """fit_keypoints_in_views, then the fits of every sequence smoothed by their information matrices: THREE launches on the
+    current stream - ut_fit_pose_views (or its robust entry), ut_pose_information_views at the fitted poses with the same loss,
+    weights and views, ut_smooth_pose_sequence on what the two wrote - and nothing between them on the host, so that the chain is
+    capturable with deferred checks.  The n = n_seq * T hand-samples are sequence-major: frame t of sequence s is row s * T + t of
+    window f64 [n,V,21,2], src_row i32 [n,V], init_angles [n,22], init_wrist_xf [n,4,4] (every frame needs a start: the fits of one
+    launch cannot start from each other) and weights / mirror.  step_var f32 [1|n_seq,26], frame_weight [n_seq,T], lengths i32
+    [n_seq], centre f32 [n_seq,3] (None: the wrist's origin - hand.smooth_poses has the landmarks' mean as its default) as for
+    _native.smooth_pose_sequence; a frame whose fit is refused carries no information and is filled in.  Returns (joint_angles
+    [n_seq,T,22], wrist_xf [n_seq,T,4,4], info [n_seq,T,4] of the smoother, param_sigma [n_seq,T,26] or None, the fit's (joint_angles
+    [n,22], wrist_xf [n,4,4], info [n,4]))."""
+    n = window.shape[0]
+    if n_seq < 1 or n % n_seq:
+        raise ValueError(f"{n} hand-samples are not {n_seq} sequences of equal length")
+    fit = _native.fit_pose_views_any_loss(hand_model, window, src_row, cam_params, init_angles, init_wrist_xf, weights=weights, mirror=mirror,
+                                          t_scale=t_scale, max_iters=max_iters, loss=loss, loss_scale=loss_scale, engine=engine)
+    pose_info, pivot = _native.pose_information_views(hand_model, fit[0], fit[1], window, src_row, cam_params, weights=weights,
+                                                      angle_sigma=angle_sigma, mirror=mirror, t_scale=t_scale, loss=loss, loss_scale=loss_scale,
+                                                      param_sigma=False, landmark_cov=False, info=False, engine=engine)[:2]
+    frames = n // n_seq
+    ja, xf, sigma, info = _native.smooth_pose_sequence(fit[0].reshape(n_seq, frames, 22), fit[1].reshape(n_seq, frames, 4, 4), pose_info, pivot,
+                                                       step_var, frame_weight=frame_weight, lengths=lengths, centre=centre, t_scale=t_scale,
+                                                       param_sigma=with_sigma, engine=engine)
+    return ja, xf, info, sigma, fit[:3]
+
+
 def calibrate_scale_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
                              init_angles: torch.Tensor, init_wrist_xf: torch.Tensor, init_scale: Optional[torch.Tensor] = None,
                              group_size: Optional[int] = None, weights: Optional[torch.Tensor] = None,

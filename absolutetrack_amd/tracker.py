@@ -18,7 +18,7 @@ import torch
 from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
-from .hand import FIT_CONVERGED, fit_landmarks, fit_landmarks_info, fit_landmarks_views, pose_uncertainty_views
+from .hand import FIT_CONVERGED, fit_landmarks, fit_landmarks_info, fit_landmarks_views, pose_uncertainty_views, smooth_poses
 from .hand import ScaleCalibration, calibrate_scale, calibrate_scale_in_views
 from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
@@ -290,6 +290,45 @@ def hand_pose_uncertainty_in_views(hand_model: HandModel, cameras: List[CameraMo
         weights=None if weights is None else torch.from_numpy(weights), angle_sigma=angle_sigma, loss=loss, loss_scale=loss_scale,
         mirror=_mirror_flag(hand_idx))
     return type(unc)(*(t.numpy() for t in unc))
+
+
+def smooth_hand_poses_in_views(hand_model: HandModel, cameras: List[List[CameraModel]], window_keypoints: np.ndarray, hand_idx: int,
+                               init: SingleHandPose, step_sigma, weights: Optional[np.ndarray] = None, loss="squared",
+                               loss_scale: float = 3.0, frame_weight: Optional[np.ndarray] = None, centre=None):
+    """One hand through T frames of detections, fitted frame by frame and then smoothed over the sequence: cameras[t] the cameras
+    of frame t (the same number in every frame), window_keypoints [T,n_cams,21,2], weights [T,n_cams,21] informations (1 / sigma^2
+    in px^-2 of each detection, 0 where the camera does not see the landmark; None = all 1, and then step_sigma is in units of the
+    detection noise).  Frame t is fitted by refine_hand_pose_in_views from frame t - 1's fit (frame 0 from `init`), as
+    hand_poses_from_keypoints warm-starts its frames; then ONE ut_pose_information_views launch at the T fits and ONE
+    ut_smooth_pose_sequence launch (hand.smooth_poses: step_sigma [26] per frame step - hand.step_sigma_from_rates -, frame_weight
+    [T], centre).  A frame whose fit is refused carries no information and is filled in from its neighbours.  Returns (the T
+    smoothed SingleHandPoses with the fits' hand_confidence, info [T,4] and param_sigma [T,26] of hand.smooth_poses)."""
+    win = np.ascontiguousarray(window_keypoints, np.float64)
+    frames = len(cameras)
+    if frames == 0 or win.ndim != 4 or win.shape[0] != frames:
+        raise ValueError(f"window_keypoints must be [{frames},n_cams,21,2] for {frames} frames of cameras, got {win.shape}")
+    n_cams = win.shape[1]
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float32)
+    poses, pose = [], init
+    tables = []
+    for t in range(frames):
+        table, _w, _wt = _window_inputs("smooth_hand_poses_in_views", cameras[t], win[t], None if weights is None else weights[t], (n_cams, 21, 2))
+        tables.append(table)
+        pose = refine_hand_pose_in_views(hand_model, cameras[t], win[t], hand_idx, pose, None if weights is None else weights[t], loss=loss,
+                                         loss_scale=loss_scale)[0]
+        poses.append(pose)
+    ja = torch.from_numpy(np.stack([np.asarray(p.joint_angles, np.float32) for p in poses]))
+    xf = torch.from_numpy(np.stack([np.asarray(p.wrist_xform, np.float32) for p in poses]))
+    rows = torch.arange(frames * n_cams, dtype=torch.int32).reshape(frames, n_cams)
+    mirror = _mirror_flag(hand_idx)
+    unc = pose_uncertainty_views(hand_model, ja, xf, torch.from_numpy(win), rows, torch.from_numpy(np.concatenate(tables)),
+                                 weights=None if weights is None else torch.from_numpy(weights), loss=loss, loss_scale=loss_scale,
+                                 mirror=mirror.expand(frames))
+    sja, sxf, info, sigma = smooth_poses(hand_model, ja, xf, unc, step_sigma, mirror=mirror, centre=centre, return_sigma=True,
+                                         frame_weight=None if frame_weight is None else torch.from_numpy(np.ascontiguousarray(frame_weight, np.float32)))
+    out = [SingleHandPose(joint_angles=sja[t].numpy(), wrist_xform=sxf[t].numpy(), hand_confidence=poses[t].hand_confidence) for t in range(frames)]
+    return out, info.numpy(), sigma.numpy()
 
 
 def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray, hand_idx: int,
