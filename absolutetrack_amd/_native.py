@@ -127,6 +127,13 @@ _SMOOTH_PROTOTYPES = {
                                        _vp, _i32, _vp, _vp, _vp]),
 }
 SMOOTH_EXPORTS = tuple(_SMOOTH_PROTOTYPES)
+# The entries of include/umetrack_hip_start.h, in a table of their own like their header (tests/test_start_host.py pins it).
+_START_PROTOTYPES = {
+    "ut_start_pose_views": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _i32,
+                                   _vp, _i32, _vp, _i32, _vp, _vp]),
+    "ut_select_pose": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+}
+START_EXPORTS = tuple(_START_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -152,7 +159,8 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
                                       **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES, **_ROBUST_PROTOTYPES,
-                                      **_VIEWS_SCALE_PROTOTYPES, **_UNCERTAINTY_PROTOTYPES, **_SMOOTH_PROTOTYPES}.items():
+                                      **_VIEWS_SCALE_PROTOTYPES, **_UNCERTAINTY_PROTOTYPES, **_SMOOTH_PROTOTYPES,
+                                      **_START_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -933,6 +941,84 @@ def smooth_pose_sequence(joint_angles: torch.Tensor, wrist_xf: torch.Tensor, pos
               _ptr(frame_weight), _ptr(lengths), _ptr(centre), _ptr(step_var), step_var.shape[0], ctypes.c_float(t_scale), n_seq, n_frames,
               _ptr(workspace), _ptr(out[0]), ja_out_stride, _ptr(out[1]), xf_out_stride, _ptr(param_sigma), _ptr(info))
     return out[0], out[1], param_sigma, info
+
+
+UT_START_MAX_SEEDS = 64
+
+
+def start_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                     bank_angles: torch.Tensor, seeds: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                     limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                     iters: int = 30, *, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22,
+                     xf_stride: int = 16, info: Optional[torch.Tensor] = None, engine: Optional["HipEngine"] = None):
+    """ut_start_pose_views: starts for fit_pose_views from the detections alone - generalised PnP by orthogonal iteration, one start
+    per hand and bank pose, the best of the rotation seeds by the exact reprojection cost.  window, cam_rows, table, weights,
+    hand_model, limits, mirror, t_scale as for fit_pose_views; bank_angles f32 [K,20]; seeds f64 [S,3,3] proper rotations, S <=
+    UT_START_MAX_SEEDS.  Returns (joint_angles [n*K,22], wrist_xf [n*K,4,4], info [n*K,4]: rms px of the start, largest
+    reprojection distance px, the winning seed, status 0 or UT_FIT_REFUSED), row i*K + k the start of hand i from bank pose k -
+    what fit_pose_views takes as its init.  out: preallocated fp32 views written with the strides given in floats.  A cam_rows
+    entry outside [-1, R) raises IndexError and writes nothing for its hand - at once, or from engine.poll_status() when `engine`
+    runs deferred checks (then nothing synchronises and the launch is capturable)."""
+    d, window, cam_rows, table, weights, n, v, kind, _ = _views_inputs("start_pose_views", window, cam_rows, table, weights)
+    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
+    if hand_model.shape[0] not in (1, n) and n:
+        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} hands")
+    bank_angles = _need(bank_angles, torch.float32, d, "bank_angles")
+    if bank_angles.dim() != 2 or bank_angles.shape[1] != 20 or bank_angles.shape[0] < 1:
+        raise ValueError(f"bank_angles must be [K,20] with K >= 1, got {tuple(bank_angles.shape)}")
+    seeds = _need(seeds, torch.float64, d, "seeds")
+    if seeds.numel() % 9 or not 1 <= seeds.numel() // 9 <= UT_START_MAX_SEEDS:
+        raise ValueError(f"seeds must be f64 [S,3,3] with 1 <= S <= {UT_START_MAX_SEEDS}, got {tuple(seeds.shape)}")
+    if not 1 <= int(iters) <= 256:
+        raise ValueError(f"iters must be in 1..256, got {iters}")
+    k = bank_angles.shape[0]
+    if limits is not None:
+        limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
+        if limits.shape[0] != hand_model.shape[0]:
+            raise ValueError(f"limits has {limits.shape[0]} rows for {hand_model.shape[0]} model rows")
+    if mirror is not None:
+        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
+        if mirror.shape[0] != n:
+            raise ValueError("mirror batch mismatch")
+    if out is None:
+        out = (torch.empty(n * k, 22, dtype=torch.float32, device=d), torch.empty(n * k, 4, 4, dtype=torch.float32, device=d))
+        ja_stride, xf_stride = 22, 16
+    elif any(o.device != d or o.dtype != torch.float32 for o in out):
+        raise ValueError(f"out must be fp32 on {d}")
+    info = _out(info, (n * k, 4), torch.float32, d, "info")
+    _fit_call("ut_start_pose_views", d, engine._h if engine is not None else None, _ptr(hand_model), hand_model.shape[0], _ptr(window),
+              _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind, _ptr(limits), _ptr(bank_angles), k, _ptr(seeds),
+              seeds.numel() // 9, _ptr(mirror), ctypes.c_float(t_scale), int(iters), n, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride,
+              _ptr(info))
+    return out[0], out[1], info
+
+
+def select_pose(joint_angles: torch.Tensor, wrist_xf: torch.Tensor, info: torch.Tensor, n_cand: int, *,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, out_info: Optional[torch.Tensor] = None,
+                out_index: Optional[torch.Tensor] = None):
+    """ut_select_pose: of n_cand fitted candidates per hand (joint_angles [n*n_cand,22], wrist_xf [n*n_cand,4,4], info
+    [n*n_cand,4], rows i*n_cand + c) the one with the lowest info[:,0] among those that are not UT_FIT_REFUSED, the lowest index
+    among equals.  Returns (joint_angles [n,22], wrist_xf [n,4,4], info [n,4], index i32 [n]); index -1 and candidate 0 where
+    every candidate is refused.  No status word: nothing synchronises, the call is capturable."""
+    d = _hip_device(info, "select_pose")
+    joint_angles = _need(joint_angles, torch.float32, d, "joint_angles").reshape(-1, 22)
+    wrist_xf = _need(wrist_xf, torch.float32, d, "wrist_xf").reshape(-1, 16)
+    info = _need(info, torch.float32, d, "info").reshape(-1, 4)
+    n_cand = int(n_cand)
+    rows = info.shape[0]
+    if n_cand < 1 or rows % n_cand or joint_angles.shape[0] != rows or wrist_xf.shape[0] != rows:
+        raise ValueError(f"{rows} info rows, {joint_angles.shape[0]} / {wrist_xf.shape[0]} poses and n_cand = {n_cand} do not go together")
+    n = rows // n_cand
+    ja = _out(None if out is None else out[0], (n, 22), torch.float32, d, "out[0]")
+    xf = _out(None if out is None else out[1], (n, 4, 4), torch.float32, d, "out[1]")
+    out_info = _out(out_info, (n, 4), torch.float32, d, "out_info")
+    out_index = _out(out_index, (n,), torch.int32, d, "out_index")
+    lib = load_library()
+    with torch.cuda.device(d):
+        rc = lib.ut_select_pose(_ptr(joint_angles), 22, _ptr(wrist_xf), 16, _ptr(info), n, n_cand, _ptr(ja), 22, _ptr(xf), 16,
+                                _ptr(out_info), _ptr(out_index), _stream(d))
+    _check_rc(lib, None, rc, "ut_select_pose", "points")
+    return ja, xf, out_info, out_index
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

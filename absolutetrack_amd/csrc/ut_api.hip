@@ -7,6 +7,7 @@
 #include "../../include/umetrack_hip_robust.h"
 #include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_smooth.h"
+#include "../../include/umetrack_hip_start.h"
 #include "../../include/umetrack_hip_triangulate.h"
 #include "../../include/umetrack_hip_uncertainty.h"
 #include "../../include/umetrack_hip_views.h"
@@ -1681,6 +1682,48 @@ int ut_smooth_pose_sequence(ut_handle h, const float* joint_angles, int ja_strid
                          param_sigma, info};
   ON_DEVICE_IF(h);
   HIPCHK(h, ut::launch_smooth_pose_sequence(a, (hipStream_t)stream));
+  return UT_OK;
+}
+
+static_assert(UT_START_MAX_SEEDS == 64, "one lane per seed");
+
+int ut_start_pose_views(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
+                        const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind,
+                        const float* limits, const float* bank_angles, int n_bank, const double* seeds, int n_seeds,
+                        const int64_t* mirror, float t_scale, int iters, int n,
+                        float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride, float* info, void* stream) {
+  const char* who = "ut_start_pose_views";      // there is no start to require and no max_iters: the checks of the fits, restated
+  if (!hand_model || !window || !cam_rows || !table || !bank_angles || !seeds || !joint_angles || !wrist_xf)
+    return fail_as(h, who, "null argument");
+  if (table_kind != UT_CAMERA_FISHEYE62 && table_kind != UT_CAMERA_PINHOLE)
+    return fail_as(h, who, "table_kind must be UT_CAMERA_FISHEYE62 or UT_CAMERA_PINHOLE");
+  if (max_views < 1 || max_views > UT_TRI_MAX_VIEWS) return fail_as(h, who, "max_views must be in 1..UT_TRI_MAX_VIEWS (8)");
+  if (n < 0 || n_rows < 1 || (n_models != 1 && n_models != n)) return fail_as(h, who, "bad argument");
+  if (n_bank < 1 || (long long)n * n_bank > 0x7fffffffLL) return fail_as(h, who, "n_bank must be at least 1 and n * n_bank fit an int");
+  if (n_seeds < 1 || n_seeds > UT_START_MAX_SEEDS) return fail_as(h, who, "n_seeds must be in 1..UT_START_MAX_SEEDS (64)");
+  if (iters < 1 || iters > 256) return fail_as(h, who, "iters must be in 1..256");
+  if (ja_stride < 22 || xf_stride < 12) return fail_as(h, who, "a stride is below 22 (angles) / 12 (wrist)");
+  if (!(t_scale > 0.f) || !(t_scale <= 3.0e38f)) return fail_as(h, who, "t_scale must be positive and finite");
+  ut::StartViewsArgs a{{{hand_model, n_models, nullptr, 0, limits, nullptr, 0, nullptr, 0, mirror, t_scale, 0, n, joint_angles, ja_stride,
+                         wrist_xf, xf_stride},
+                        window, weights, cam_rows, max_views, table, n_rows, camera_kind(table_kind), info, nullptr, nullptr},
+                       bank_angles, n_bank, seeds, n_seeds, iters};
+  return launch_in_views(h, who, a.views, stream, [&](hipStream_t s) -> int {
+    HIPCHK(h, ut::launch_start_pose_views(a, s)); return UT_OK; });
+}
+
+int ut_select_pose(const float* joint_angles, int ja_stride, const float* wrist_xf, int xf_stride, const float* info,
+                   int n, int n_cand, float* out_angles, int out_ja_stride, float* out_wrist_xf, int out_xf_stride,
+                   float* out_info, int32_t* out_index, void* stream) {
+  const char* who = "ut_select_pose";      // no handle: the device is the caller's current one, as for ut_fit_pose with h == NULL
+  if (!joint_angles || !wrist_xf || !info || !out_angles || !out_wrist_xf) return fail_as(nullptr, who, "null argument");
+  if (n < 0 || n_cand < 1 || (long long)n * n_cand > 0x7fffffffLL) return fail_as(nullptr, who, "bad argument");
+  if (ja_stride < 22 || xf_stride < 12 || out_ja_stride < 22 || out_xf_stride < 12)
+    return fail_as(nullptr, who, "a stride is below 22 (angles) / 12 (wrist)");
+  if (n == 0) return UT_OK;
+  const ut::SelectPoseArgs a{joint_angles, ja_stride, wrist_xf, xf_stride, info, n, n_cand, out_angles, out_ja_stride, out_wrist_xf,
+                             out_xf_stride, out_info, out_index};
+  HIPCHK(nullptr, ut::launch_select_pose(a, (hipStream_t)stream));
   return UT_OK;
 }
 

@@ -508,6 +508,28 @@ struct SmoothArgs {
 };
 hipError_t launch_smooth_pose_sequence(const SmoothArgs& a, hipStream_t s);
 
+// start_views.hip: starts for the fits in the views from the detections alone (ut_start_pose_views), and the selection among fitted
+// candidates (ut_select_pose).  Of views.pose the model, limits, mirror, t_scale, n and the outputs (n * n_bank rows) are read;
+// views.info is [n * n_bank,4]; views.residual is not read.  Pointers as umetrack_hip_start.h documents them.
+struct StartViewsArgs {
+  FitViewsArgs views;
+  const float* bank; int n_bank;        // [n_bank,20]
+  const double* seeds; int n_seeds;     // [n_seeds,9]
+  int iters;
+};
+hipError_t launch_start_pose_views(const StartViewsArgs& a, hipStream_t s);
+struct SelectPoseArgs {
+  const float* ja; int ja_stride;
+  const float* xf; int xf_stride;
+  const float* info;                    // [n * n_cand,4]
+  int n, n_cand;
+  float* out_ja; int out_ja_stride;
+  float* out_xf; int out_xf_stride;
+  float* out_info;                      // [n,4] or null
+  int32_t* out_index;                   // [n] or null
+};
+hipError_t launch_select_pose(const SelectPoseArgs& a, hipStream_t s);
+
 // Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
 //  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
 //           bone, unused slots weight 0 / bone 0

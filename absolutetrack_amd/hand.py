@@ -281,6 +281,79 @@ def fit_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: t
     return out + tuple(s.back(r, (v, 21)) for r in res[3:])
 
 
+START_ITERS = 30      # rounds of the orthogonal iteration in cold_start_views
+
+
+def start_pose_bank(hand_model: HandModel, fractions=(0.25, 0.5, 0.75)) -> torch.Tensor:
+    """The finger poses cold_start_views tries, f32 [K,20]: the zero pose, then lo + f (hi - lo) of hand_model.joint_limits for
+    every f in `fractions` (without joint_limits: the zero pose alone).  An unbatched skeleton, or the first of a batch."""
+    bank = [torch.zeros(20, dtype=torch.float32)]
+    if hand_model.joint_limits is not None and len(fractions):
+        box = hand_model.joint_limits.reshape(-1, hand_model.joint_limits.shape[-2], 2)[0, :20].to("cpu", torch.float32)
+        bank += [box[:, 0] + float(f) * (box[:, 1] - box[:, 0]) for f in fractions]
+    return torch.stack(bank)
+
+
+def start_rotation_seeds() -> torch.Tensor:
+    """The 24 proper signed permutation matrices, f64 [24,3,3]: the rotations of the cube, in the order of the permutations
+    (0,1,2), (0,2,1), ... and, within one, of the signs (+,+), (+,-), (-,+), (-,-) of the first two rows - the third follows
+    from det = +1.  The identity is seed 0."""
+    seeds = []
+    for perm in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+        parity = 1.0 if perm in ((0, 1, 2), (1, 2, 0), (2, 0, 1)) else -1.0
+        for s0 in (1.0, -1.0):
+            for s1 in (1.0, -1.0):
+                q = np.zeros((3, 3))
+                q[0, perm[0]], q[1, perm[1]], q[2, perm[2]] = s0, s1, parity * s0 * s1
+                seeds.append(q)
+    return torch.from_numpy(np.stack(seeds))
+
+
+def cold_start_views(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                     weights: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, limits=None, bank=None,
+                     seeds=None, iters: int = START_ITERS):
+    """Starts for fit_landmarks_views from the detections alone, one launch of csrc/start_views.hip (no CPU implementation):
+    per hand one start from each of the K finger poses of `bank` (default start_pose_bank(hand_model)), the hand moved rigidly
+    onto the detections' rays from each of `seeds` (default start_rotation_seeds()) and the best seed kept by its reprojection
+    cost.  window, cam_rows, table, weights, mirror, limits as for fit_landmarks_views.  Returns (joint_angles [...,K,22],
+    wrist_transforms [...,K,4,4], info [...,K,4]: rms px, largest reprojection distance px, winning seed, status 0 or
+    FIT_REFUSED)."""
+    s, _v, views, weights = _views_staging(hand_model, window, cam_rows, table, weights, limits)
+    bank = (start_pose_bank(hand_model) if bank is None else bank).to(s.dev, torch.float32)
+    seeds = (start_rotation_seeds() if seeds is None else seeds).to(s.dev, torch.float64)
+    k = bank.shape[0]
+    ja, xf, info = _native.start_pose_views(s.blob, *views, bank, seeds, weights, s.box, s.flags(mirror), iters=iters)
+    return s.back(ja, (k, 22)), s.back(xf, (k, 4, 4)), s.back(info, (k, 4))
+
+
+def fit_landmarks_views_cold(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor,
+                             weights: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, limits=None,
+                             max_iters: int = 32, loss="squared", loss_scale: float = 3.0, bank=None, seeds=None,
+                             iters: int = START_ITERS):
+    """fit_landmarks_views without an init: cold_start_views, then the fit from each of its K starts per hand (any `loss`), then
+    the candidate with the lowest info[...,0] among those not refused (_native.select_pose) - three launches.  Returns
+    (joint_angles [...,22], wrist_transforms [...,4,4], info [...,4]) as fit_landmarks_views does, plus the chosen candidate's
+    index [...] (i32; -1 where every candidate was refused: the pose is then the first candidate's)."""
+    s, _v, views, weights = _views_staging(hand_model, window, cam_rows, table, weights, limits)
+    bank = (start_pose_bank(hand_model) if bank is None else bank).to(s.dev, torch.float32)
+    seeds = (start_rotation_seeds() if seeds is None else seeds).to(s.dev, torch.float64)
+    res = _cold_chain(s.blob, views, weights, s.box, s.flags(mirror), bank, seeds, iters, max_iters, loss, loss_scale)
+    return s.back(res[0], (22,)), s.back(res[1], (4, 4)), s.back(res[2], (4,)), s.back(res[3], ())
+
+
+def _cold_chain(blob, views, weights, box, mirror, bank, seeds, iters, max_iters, loss, loss_scale, t_scale: float = 1.0, engine=None):
+    """start_pose_views -> fit_pose_views[_robust] on the n K starts -> select_pose, everything on the device: (joint_angles [n,22],
+    wrist_xf [n,4,4], info [n,4], index i32 [n])."""
+    k = bank.shape[0]
+    window, cam_rows, table = views
+    ja0, xf0, _ = _native.start_pose_views(blob, window, cam_rows, table, bank, seeds, weights, box, mirror, t_scale, iters, engine=engine)
+    rep = (lambda t: t) if k == 1 else (lambda t: None if t is None else t.repeat_interleave(k, 0))
+    many = (lambda t: t if t is None or t.shape[0] == 1 else rep(t))      # one model row stands for every pose
+    ja, xf, info = _native.fit_pose_views_any_loss(many(blob), rep(window), rep(cam_rows), table, ja0, xf0, rep(weights), many(box),
+                                                   rep(mirror), t_scale, max_iters, loss, loss_scale, engine=engine)[:3]
+    return _native.select_pose(ja, xf, info, k)
+
+
 COV_OK, COV_SINGULAR, COV_REFUSED = _native.UT_COV_OK, _native.UT_COV_SINGULAR, _native.UT_COV_REFUSED
 
 

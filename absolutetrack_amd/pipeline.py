@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native, arch, geometry
-from .hand import HandModel, device_blob, device_mesh, unpack_uncertainty
+from .hand import START_ITERS, HandModel, _cold_chain, device_blob, device_mesh, unpack_uncertainty
 from .tracker import (HandTrackerOpts, MAX_VIEW_NUM, SingleHandPose, gen_crop_cameras_from_pose,
                       network_camera_inputs)
 
@@ -257,6 +257,21 @@ def fit_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_p
                                           mirror=mirror, t_scale=t_scale, loss=loss, loss_scale=loss_scale, engine=engine,
                                           **{k: strided[k] for k in ("n", "ja_stride", "xf_stride") if k in strided})
     return res + (unpack_uncertainty(*outs),)
+
+
+def fit_keypoints_in_views_cold(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
+                                bank_angles: torch.Tensor, seeds: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                                mirror: Optional[torch.Tensor] = None, limits: Optional[torch.Tensor] = None, t_scale: float = 1.0,
+                                max_iters: int = 32, loss="squared", loss_scale: float = 3.0, iters: int = START_ITERS,
+                                engine: Optional[_native.HipEngine] = None):
+    """fit_keypoints_in_views without a start: THREE launches on the current stream - ut_start_pose_views (one start per hand-sample
+    and row of bank_angles f32 [K,20], the best of seeds f64 [S,3,3] each; hand.start_pose_bank / hand.start_rotation_seeds),
+    ut_fit_pose_views (or its robust entry) on the n K starts, ut_select_pose - and between them only device copies that repeat
+    every hand-sample's detections K times, so that the chain is capturable with deferred checks.  Arguments as for
+    fit_keypoints_in_views.  Returns (joint_angles [n,22], wrist_xf [n,4,4], info f32 [n,4] of the chosen fit, index i32 [n]: the
+    chosen bank row, -1 where every candidate was refused)."""
+    return _cold_chain(hand_model, (window, src_row, cam_params), weights, limits, mirror, bank_angles, seeds, iters, max_iters, loss,
+                       loss_scale, t_scale, engine)
 
 
 def smooth_fitted_sequence(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,
