@@ -134,6 +134,12 @@ _START_PROTOTYPES = {
     "ut_select_pose": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
 }
 START_EXPORTS = tuple(_START_PROTOTYPES)
+# The entry of include/umetrack_hip_track.h, in a table of its own like its header (tests/test_track_host.py pins it).
+_TRACK_PROTOTYPES = {
+    "ut_track_pose_views": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp,
+                                   _vp, _f64, _f64, _vp, _vp, _f32, _i32, _i32, _f32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+}
+TRACK_EXPORTS = tuple(_TRACK_PROTOTYPES)
 
 UT_MODE_KNOWN, UT_MODE_UNKNOWN = 0, 1
 UT_REMAP_CV2_FIXED, UT_REMAP_FLOAT = 0, 1
@@ -160,7 +166,7 @@ def load_library() -> ctypes.CDLL:
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_TRIANGULATE_PROTOTYPES, **_SCALE_PROTOTYPES,
                                       **_INFO_PROTOTYPES, **_VIEWS_PROTOTYPES, **_ROBUST_PROTOTYPES,
                                       **_VIEWS_SCALE_PROTOTYPES, **_UNCERTAINTY_PROTOTYPES, **_SMOOTH_PROTOTYPES,
-                                      **_START_PROTOTYPES}.items():
+                                      **_START_PROTOTYPES, **_TRACK_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1019,6 +1025,92 @@ def select_pose(joint_angles: torch.Tensor, wrist_xf: torch.Tensor, info: torch.
                                 _ptr(out_info), _ptr(out_index), _stream(d))
     _check_rc(lib, None, rc, "ut_select_pose", "points")
     return ja, xf, out_info, out_index
+
+
+UT_TRACK_WARM, UT_TRACK_COLD, UT_TRACK_NONE = 0, 1, 2
+
+
+def track_pose_views(hand_model: torch.Tensor, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, n_frames: int,
+                     init_angles: Optional[torch.Tensor] = None, init_wrist_xf: Optional[torch.Tensor] = None, cold=None,
+                     weights: Optional[torch.Tensor] = None, limits: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None,
+                     lengths: Optional[torch.Tensor] = None, t_scale: float = 1.0, max_iters: int = 32, loss="squared",
+                     loss_scale: float = 3.0, recover_ratio: float = 1.5, recover_floor: float = 0.01, *, init_ja_stride: int = 22,
+                     init_xf_stride: int = 16, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ja_stride: int = 22,
+                     xf_stride: int = 16, info: Optional[torch.Tensor] = None, chosen: Optional[torch.Tensor] = None,
+                     engine: Optional["HipEngine"] = None):
+    """ut_track_pose_views: n_seq sequences of n_frames frames of detections followed frame by frame in ONE launch - the warm fit of
+    fit_pose_views_robust from the previous frame's choice, the cold row taken where the warm fit is refused or its rms exceeds
+    recover_ratio x the cold rms + recover_floor (include/umetrack_hip_track.h states the rule; the result is that chain of
+    launches bit for bit).  window f64 [n_seq * n_frames,V,21,2], cam_rows, weights, mirror and hand_model / limits rows: frame t of
+    sequence s is row s * n_frames + t, everything else as for fit_pose_views_robust.  init_angles [n_seq,22] / init_wrist_xf
+    [n_seq,4,4]: the start of each sequence's frame 0, or None: the first usable cold row starts it.  cold = (joint_angles [n,22],
+    wrist_xf [n,4,4], info [n,4], index i32 [n]), what select_pose returns at the end of the cold chain on the same rows, or None:
+    no recovery.  lengths i32 [n_seq] or None.  Returns (joint_angles [n,22], wrist_xf [n,4,4], info [n,4], chosen i32 [n]:
+    UT_TRACK_WARM / UT_TRACK_COLD / UT_TRACK_NONE, -1 at or past a sequence's length, where nothing else is written but an info row
+    of 0).  out: preallocated fp32 views written with the strides given in floats, the init pair read with init_*_stride when they
+    are not the packed shapes.  A cam_rows entry outside [-1, R) inside a sequence's length raises IndexError and writes nothing
+    for that sequence - at once, or from engine.poll_status() when `engine` runs deferred checks (then nothing synchronises and the
+    launch is capturable)."""
+    d, window, cam_rows, table, weights, n, v, kind, (code, loss_scale) = _views_inputs(
+        "track_pose_views", window, cam_rows, table, weights, (loss, loss_scale))
+    n_frames = int(n_frames)
+    if n_frames < 1 or n % n_frames:
+        raise ValueError(f"{n} rows of windows are not sequences of {n_frames} frames")
+    n_seq = n // n_frames
+    hand_model = _need(hand_model, torch.float32, d, "hand_model").reshape(-1, 321)
+    if hand_model.shape[0] not in (1, n) and n:
+        raise ValueError(f"hand_model has {hand_model.shape[0]} rows for {n} frames")
+    if (init_angles is None) != (init_wrist_xf is None):
+        raise ValueError("init_angles and init_wrist_xf go together")
+    if init_angles is None and cold is None:
+        raise ValueError("an init or the cold chain's results are needed: there is nothing to start from")
+    if init_angles is not None:
+        if (init_ja_stride, init_xf_stride) == (22, 16):
+            init_angles = _need(init_angles, torch.float32, d, "init_angles").reshape(-1, 22)
+            init_wrist_xf = _need(init_wrist_xf, torch.float32, d, "init_wrist_xf").reshape(-1, 16)
+            if init_angles.shape[0] != n_seq or init_wrist_xf.shape[0] != n_seq:
+                raise ValueError(f"init_angles / init_wrist_xf must hold one row per sequence ({n_seq})")
+        elif any(t.device != d or t.dtype != torch.float32 for t in (init_angles, init_wrist_xf)):
+            raise ValueError(f"strided init views must be fp32 on {d}")
+    if cold is not None:
+        cja, cxf, cinfo, cindex = cold
+        cja, cxf = _need(cja, torch.float32, d, "cold[0]").reshape(-1, 22), _need(cxf, torch.float32, d, "cold[1]").reshape(-1, 16)
+        cinfo, cindex = _need(cinfo, torch.float32, d, "cold[2]").reshape(-1, 4), _need(cindex, torch.int32, d, "cold[3]").reshape(-1)
+        if any(t.shape[0] != n for t in (cja, cxf, cinfo, cindex)):
+            raise ValueError(f"the cold results must hold one row per frame ({n})")
+        cold = (cja, cxf, cinfo, cindex)
+    else:
+        cold = (None, None, None, None)
+    if not (np.isfinite(recover_ratio) and recover_ratio >= 1.0):
+        raise ValueError(f"recover_ratio must be finite and at least 1, got {recover_ratio}")
+    if not (np.isfinite(recover_floor) and recover_floor >= 0.0):
+        raise ValueError(f"recover_floor must be finite and not negative, got {recover_floor}")
+    if limits is not None:
+        limits = _need(limits, torch.float32, d, "limits").reshape(-1, 20, 2)
+        if limits.shape[0] != hand_model.shape[0]:
+            raise ValueError(f"limits has {limits.shape[0]} rows for {hand_model.shape[0]} model rows")
+    if mirror is not None:
+        mirror = _need(mirror, torch.int64, d, "mirror").reshape(-1)
+        if mirror.shape[0] != n:
+            raise ValueError("mirror batch mismatch")
+    if lengths is not None:
+        lengths = _need(lengths, torch.int32, d, "lengths").reshape(-1)
+        if lengths.shape[0] != n_seq:
+            raise ValueError(f"lengths must be [{n_seq}]")
+    if out is None:
+        out = (torch.empty(n, 22, dtype=torch.float32, device=d), torch.empty(n, 4, 4, dtype=torch.float32, device=d))
+        ja_stride, xf_stride = 22, 16
+    elif any(o.device != d or o.dtype != torch.float32 for o in out):
+        raise ValueError(f"out must be fp32 on {d}")
+    info = _out(info, (n, 4), torch.float32, d, "info")
+    chosen = _out(chosen, (n,), torch.int32, d, "chosen")
+    _fit_call("ut_track_pose_views", d, engine._h if engine is not None else None, _ptr(hand_model), hand_model.shape[0], _ptr(window),
+              _ptr(weights), _ptr(cam_rows), v, _ptr(table), table.shape[0], kind, _ptr(limits), _ptr(init_angles), init_ja_stride,
+              _ptr(init_wrist_xf), init_xf_stride, _ptr(cold[0]), 22, _ptr(cold[1]), 16, _ptr(cold[2]), _ptr(cold[3]),
+              ctypes.c_double(recover_ratio), ctypes.c_double(recover_floor), _ptr(lengths), _ptr(mirror), ctypes.c_float(t_scale),
+              int(max_iters), code, ctypes.c_float(loss_scale), n_seq, n_frames, _ptr(out[0]), ja_stride, _ptr(out[1]), xf_stride,
+              _ptr(info), _ptr(chosen))
+    return out[0], out[1], info, chosen
 
 
 def render_mesh(mesh: Mesh, vertices: torch.Tensor, crop_params: torch.Tensor, sample_range: torch.Tensor,

@@ -12,14 +12,14 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 OUT = os.path.join(HERE, "libumetrack_hip.so")
 SOURCES = ["ut_api.hip", "ut_weights.cpp", "conv_igemm.hip", "conv_pw.hip", "conv_patch.hip", "conv_block32.hip", "conv_split.hip", "conv_w4.hip", "conv_c64k.hip",
-           "conv_c32s2.hip", "stem.hip", "head.hip", "fk.hip", "fit.hip", "fit_scale.hip", "fit_info.hip", "fit_views.hip", "fit_views_robust.hip", "fit_views_scale.hip", "pose_info_views.hip", "smooth.hip", "start_views.hip", "mesh.hip", "render.hip", "triangulate.hip", "warp.hip", "cropgen.hip", "homography.hip", "metrics.hip"]
+           "conv_c32s2.hip", "stem.hip", "head.hip", "fk.hip", "fit.hip", "fit_scale.hip", "fit_info.hip", "fit_views.hip", "fit_views_robust.hip", "fit_views_scale.hip", "pose_info_views.hip", "smooth.hip", "start_views.hip", "track_views.hip", "mesh.hip", "render.hip", "triangulate.hip", "warp.hip", "cropgen.hip", "homography.hip", "metrics.hip"]
 HEADERS = ["ut_kernels.h", "ut_weights.h", "ut_split_pack.h", "ut_conv_dev.h", "ut_math.h", "ut_fk.h", "ut_fit_dev.h", "ut_fit_views_dev.h", "ut_camera.h", os.path.join("..", "..", "include", "umetrack_hip.h"),
            os.path.join("..", "..", "include", "umetrack_hip_fit.h"), os.path.join("..", "..", "include", "umetrack_hip_triangulate.h"),
            os.path.join("..", "..", "include", "umetrack_hip_scale.h"), os.path.join("..", "..", "include", "umetrack_hip_info.h"),
            os.path.join("..", "..", "include", "umetrack_hip_views.h"), os.path.join("..", "..", "include", "umetrack_hip_robust.h"),
            os.path.join("..", "..", "include", "umetrack_hip_views_scale.h"),
            os.path.join("..", "..", "include", "umetrack_hip_uncertainty.h"), os.path.join("..", "..", "include", "umetrack_hip_smooth.h"),
-           os.path.join("..", "..", "include", "umetrack_hip_start.h")]
+           os.path.join("..", "..", "include", "umetrack_hip_start.h"), os.path.join("..", "..", "include", "umetrack_hip_track.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -8,6 +8,7 @@
 #include "../../include/umetrack_hip_scale.h"
 #include "../../include/umetrack_hip_smooth.h"
 #include "../../include/umetrack_hip_start.h"
+#include "../../include/umetrack_hip_track.h"
 #include "../../include/umetrack_hip_triangulate.h"
 #include "../../include/umetrack_hip_uncertainty.h"
 #include "../../include/umetrack_hip_views.h"
@@ -1220,14 +1221,15 @@ int fail_as(ut_handle h, const char* who, const char* what) {
 // The argument checks the pose fits share, on the arguments as the kernels get them; `who` names the entry in the message.
 // FIT_NO_TARGETS: the fits in the views, which have no 3-D targets and need their start.  FIT_POSE_IS_INPUT: ut_pose_information_views,
 // whose pose stands where the fits have their start - it is checked as their outputs are; a.ja / a.xf and a.max_iters are not read.
-enum : int { FIT_NO_TARGETS = 1, FIT_POSE_IS_INPUT = 2 };
+// FIT_START_OPTIONAL: ut_track_pose_views, whose sequences may start from the cold rows instead - the entry checks that one of them is there.
+enum : int { FIT_NO_TARGETS = 1, FIT_POSE_IS_INPUT = 2, FIT_START_OPTIONAL = 4 };
 int fit_pose_args(ut_handle h, const char* who, const ut::FitPoseArgs& a, int flags = 0) {
   const bool with_targets = !(flags & FIT_NO_TARGETS), fitted = !(flags & FIT_POSE_IS_INPUT);
   const float *ja = fitted ? a.ja : a.init_ja, *xf = fitted ? a.xf : a.init_xf;
   const int ja_stride = fitted ? a.ja_stride : a.init_ja_stride, xf_stride = fitted ? a.xf_stride : a.init_xf_stride;
   if (!a.hand_model || (with_targets && !a.targets) || !ja || !xf || a.n < 0 || (a.n_models != 1 && a.n_models != a.n))
     return fail_as(h, who, "bad argument");
-  if (!with_targets && (!a.init_ja || !a.init_xf))
+  if (!with_targets && !(flags & FIT_START_OPTIONAL) && (!a.init_ja || !a.init_xf))
     return fail_as(h, who, "init_angles and init_wrist_xf are required: there is no cold start");
   if ((a.init_ja == nullptr) != (a.init_xf == nullptr))
     return fail_as(h, who, "init_angles and init_wrist_xf must both be given or both be NULL");
@@ -1725,6 +1727,41 @@ int ut_select_pose(const float* joint_angles, int ja_stride, const float* wrist_
                              out_xf_stride, out_info, out_index};
   HIPCHK(nullptr, ut::launch_select_pose(a, (hipStream_t)stream));
   return UT_OK;
+}
+
+static_assert(UT_TRACK_WARM == ut::TRACK_WARM && UT_TRACK_COLD == ut::TRACK_COLD && UT_TRACK_NONE == ut::TRACK_NONE,
+              "umetrack_hip_track.h and ut_kernels.h");
+
+int ut_track_pose_views(ut_handle h, const float* hand_model, int n_models, const double* window, const float* weights,
+                        const int32_t* cam_rows, int max_views, const double* table, int n_rows, int table_kind,
+                        const float* limits,
+                        const float* init_angles, int init_ja_stride, const float* init_wrist_xf, int init_xf_stride,
+                        const float* cold_angles, int cold_ja_stride, const float* cold_wrist_xf, int cold_xf_stride,
+                        const float* cold_info, const int32_t* cold_index, double recover_ratio, double recover_floor,
+                        const int32_t* lengths, const int64_t* mirror, float t_scale, int max_iters, int loss, float loss_scale,
+                        int n_seq, int n_frames, float* joint_angles, int ja_stride, float* wrist_xf, int xf_stride,
+                        float* info, int32_t* chosen, void* stream) {
+  const char* who = "ut_track_pose_views";      // the checks of the fits on n = n_seq * n_frames rows; its own come second and third
+  const bool rows_ok = n_seq >= 0 && n_frames >= 1 && (long long)n_seq * n_frames <= 0x7fffffffLL;
+  const int n_cold = (cold_angles != nullptr) + (cold_wrist_xf != nullptr) + (cold_info != nullptr) + (cold_index != nullptr);
+  const char* own = nullptr;
+  if (!rows_ok) own = "n_seq must not be negative, n_frames at least 1, and n_seq * n_frames fit an int";
+  else if ((init_angles == nullptr) != (init_wrist_xf == nullptr)) own = "init_angles and init_wrist_xf must both be given or both be NULL";
+  else if (n_cold != 0 && n_cold != 4) own = "cold_angles, cold_wrist_xf, cold_info and cold_index must all be given or all be NULL";
+  else if (!init_angles && !n_cold) own = "neither an init nor cold arrays: there is nothing to start from";
+  else if (n_cold && (cold_ja_stride < 22 || cold_xf_stride < 12)) own = "a stride is below 22 (angles) / 12 (wrist)";
+  else if (!(recover_ratio >= 1.0) || !(recover_ratio <= 1.7e308)) own = "recover_ratio must be finite and at least 1";
+  else if (!(recover_floor >= 0.0) || !(recover_floor <= 1.7e308)) own = "recover_floor must be finite and not negative";
+  ut::TrackViewsArgs a{{{{hand_model, n_models, nullptr, 0, limits, init_angles, init_ja_stride, init_wrist_xf, init_xf_stride, mirror, t_scale,
+                          max_iters, rows_ok ? n_seq * n_frames : 0, joint_angles, ja_stride, wrist_xf, xf_stride},
+                         window, weights, cam_rows, max_views, table, n_rows, camera_kind(table_kind), info, nullptr, nullptr},
+                        loss, loss_scale, nullptr},
+                       cold_angles, cold_ja_stride, cold_wrist_xf, cold_xf_stride, cold_info, cold_index, recover_ratio, recover_floor,
+                       lengths, n_seq, n_frames, chosen};
+  const int rc = fit_views_args(h, who, a.robust, table_kind, FIT_NO_TARGETS | FIT_START_OPTIONAL, !info || !chosen, own);
+  if (rc) return rc;
+  return launch_in_views(h, who, a.robust.views, stream, [&](hipStream_t s) -> int {
+    HIPCHK(h, ut::launch_track_pose_views(a, s)); return UT_OK; });
 }
 
 static_assert(UT_RENDER_MAX_VERTICES == ut::RENDER_MAX_VERTICES && UT_RENDER_MAX_VERTICES <= UT_MESH_MAX_VERTICES, "vertex cap");

@@ -530,6 +530,24 @@ struct SelectPoseArgs {
 };
 hipError_t launch_select_pose(const SelectPoseArgs& a, hipStream_t s);
 
+// track_views.hip: sequences of detections followed frame by frame in one launch (ut_track_pose_views), one wave per sequence.  The
+// tracker's fields stand behind FitViewsRobustArgs as the loss's stand behind FitViewsArgs.  robust.views.pose: n = n_seq * n_frames,
+// init_ja / init_xf the sequences' starts [n_seq] or null; robust.views.info is required; residual and inlier are not written.
+// Pointers as umetrack_hip_track.h documents them; the constants are public as UT_TRACK_*.
+enum : int { TRACK_WARM = 0, TRACK_COLD = 1, TRACK_NONE = 2 };
+struct TrackViewsArgs {
+  FitViewsRobustArgs robust;
+  const float* cold_ja; int cold_ja_stride;   // [n_seq * n_frames] rows, or all four cold pointers null: no recovery
+  const float* cold_xf; int cold_xf_stride;
+  const float* cold_info;               // [n_seq * n_frames,4]
+  const int32_t* cold_index;            // [n_seq * n_frames], < 0: the cold row is refused
+  double recover_ratio, recover_floor;
+  const int32_t* lengths;               // [n_seq] or null
+  int n_seq, n_frames;
+  int32_t* chosen;                      // [n_seq * n_frames]
+};
+hipError_t launch_track_pose_views(const TrackViewsArgs& a, hipStream_t s);
+
 // Linear blend skinning of a packed mesh (mesh.hip), one workgroup per pose; pose arguments as for launch_fk.
 //  verts    float4 [nv][2]: (x, y, z, bits: bone index of slot k in byte k) | the four slot weights, slots sorted by ascending
 //           bone, unused slots weight 0 / bone 0

@@ -341,6 +341,51 @@ def fit_landmarks_views_cold(hand_model: HandModel, window: torch.Tensor, cam_ro
     return s.back(res[0], (22,)), s.back(res[1], (4, 4)), s.back(res[2], (4,)), s.back(res[3], ())
 
 
+TRACK_WARM, TRACK_COLD, TRACK_NONE = _native.UT_TRACK_WARM, _native.UT_TRACK_COLD, _native.UT_TRACK_NONE
+RECOVER_RATIO = 1.5       # DESIGN.md, "Start of a pose fit in the views": warm rms / cold rms is 1.00 on the hand, 2.7 (median) once lost
+RECOVER_FLOOR_PX = 0.01
+
+
+def track_landmarks_views(hand_model: HandModel, window: torch.Tensor, cam_rows: torch.Tensor, table: torch.Tensor, init=None, cold=None,
+                          weights: Optional[torch.Tensor] = None, mirror: Optional[torch.Tensor] = None, limits=None,
+                          lengths: Optional[torch.Tensor] = None, max_iters: int = 32, loss="squared", loss_scale: float = 3.0,
+                          recover_ratio: float = RECOVER_RATIO, recover_floor: float = RECOVER_FLOOR_PX):
+    """fit_landmarks_views through sequences of detections, on the HIP kernel csrc/track_views.hip (no CPU implementation): window
+    f64 [...,T,V,21,2] holds T consecutive frames per sequence, cam_rows i32 [...,T,V], weights [...,T,V,21]; table, limits, loss and
+    loss_scale as for fit_landmarks_views.  ONE launch follows every sequence through its frames: frame t is fitted from frame t - 1's
+    result (frame 0 from init = (joint_angles [...,22], wrist_transforms [...,4,4]), one start per sequence) and keeps that warm fit
+    unless it is refused or its rms exceeds recover_ratio x the cold rms + recover_floor px - then the cold result of the frame is
+    taken, if it is not refused itself, and the next frame starts from it.  cold = (joint_angles [...,T,22], wrist_transforms
+    [...,T,4,4], info [...,T,4], index [...,T]): what fit_landmarks_views_cold returns on the same window, or None: no recovery.
+    init None: a sequence starts at its first usable cold result.  One of init and cold is needed.  mirror [...] or [...,T] of 0 /
+    1; lengths i32 [...]: frames at or past a sequence's length are not fitted.  Returns (joint_angles [...,T,22], wrist_transforms
+    [...,T,4,4], info [...,T,4] of the chosen fits, chosen i32 [...,T]: TRACK_WARM, TRACK_COLD - a recovery, or the first cold
+    result of a sequence without an init -, TRACK_NONE - no start yet and a refused cold result, which the row then holds - and -1
+    at or past the length).  The result is the per-frame chain of fit_landmarks_views bit for bit (include/umetrack_hip_track.h)."""
+    if window.dim() < 4:
+        raise ValueError(f"window must be [...,T,V,21,2], got {tuple(window.shape)}")
+    s, _v, views, weights = _views_staging(hand_model, window, cam_rows, table, weights, limits)
+    frames, seq_lead = s.lead[-1], s.lead[:-1]
+    if frames < 1:
+        raise ValueError("a sequence needs at least one frame")
+    n_seq = s.n // frames
+    if init is None and cold is None:
+        raise ValueError("init or cold is needed: there is nothing to start from")
+    if mirror is not None:
+        mirror = torch.as_tensor(mirror)
+        if tuple(mirror.shape) == seq_lead:
+            mirror = mirror[..., None].expand(s.lead)
+    start = (None, None) if init is None else (init[0].reshape(n_seq, 22).to(s.dev, torch.float32), init[1].reshape(n_seq, 4, 4).to(s.dev, torch.float32))
+    if cold is not None:
+        cold = (s.f32(cold[0], (22,)), s.f32(cold[1], (4, 4)), s.f32(cold[2], (4,)), s.f32(cold[3], (), torch.int32))
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).reshape(n_seq).to(s.dev, torch.int32)
+    ja, xf, info, chosen = _native.track_pose_views(s.blob, *views, frames, start[0], start[1], cold, weights, s.box, s.flags(mirror), lengths,
+                                                    max_iters=max_iters, loss=loss, loss_scale=loss_scale, recover_ratio=recover_ratio,
+                                                    recover_floor=recover_floor)
+    return s.back(ja, (22,)), s.back(xf, (4, 4)), s.back(info, (4,)), s.back(chosen, ())
+
+
 def _cold_chain(blob, views, weights, box, mirror, bank, seeds, iters, max_iters, loss, loss_scale, t_scale: float = 1.0, engine=None):
     """start_pose_views -> fit_pose_views[_robust] on the n K starts -> select_pose, everything on the device: (joint_angles [n,22],
     wrist_xf [n,4,4], info [n,4], index i32 [n])."""

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native, arch, geometry
-from .hand import START_ITERS, HandModel, _cold_chain, device_blob, device_mesh, unpack_uncertainty
+from .hand import RECOVER_FLOOR_PX, RECOVER_RATIO, START_ITERS, HandModel, _cold_chain, device_blob, device_mesh, unpack_uncertainty
 from .tracker import (HandTrackerOpts, MAX_VIEW_NUM, SingleHandPose, gen_crop_cameras_from_pose,
                       network_camera_inputs)
 
@@ -303,6 +303,49 @@ def smooth_fitted_sequence(hand_model: torch.Tensor, window: torch.Tensor, cam_p
                                                        step_var, frame_weight=frame_weight, lengths=lengths, centre=centre, t_scale=t_scale,
                                                        param_sigma=with_sigma, engine=engine)
     return ja, xf, info, sigma, fit[:3]
+
+
+def track_keypoints_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor, n_seq: int,
+                             bank_angles: torch.Tensor, seeds: torch.Tensor, init_angles: Optional[torch.Tensor] = None,
+                             init_wrist_xf: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                             mirror: Optional[torch.Tensor] = None, limits: Optional[torch.Tensor] = None,
+                             lengths: Optional[torch.Tensor] = None, t_scale: float = 1.0, max_iters: int = 32, loss="squared",
+                             loss_scale: float = 3.0, iters: int = START_ITERS, recover_ratio: float = RECOVER_RATIO,
+                             recover_floor: float = RECOVER_FLOOR_PX, smooth: bool = False, step_var: Optional[torch.Tensor] = None,
+                             angle_sigma: Optional[torch.Tensor] = None, frame_weight: Optional[torch.Tensor] = None,
+                             centre: Optional[torch.Tensor] = None, with_sigma: bool = False,
+                             engine: Optional[_native.HipEngine] = None):
+    """n_seq sequences from detections to poses, batched tracker.track_hand_poses_in_views: the cold chain of
+    fit_keypoints_in_views_cold on all n = n_seq * T hand-samples (three launches), then ONE ut_track_pose_views launch that follows
+    every sequence through its frames - the warm fit from the previous frame's choice, the cold result where the warm fit is lost
+    (_native.track_pose_views states the rule).  The hand-samples are sequence-major as for smooth_fitted_sequence; init_angles
+    [n_seq,22] / init_wrist_xf [n_seq,4,4]: each sequence's start, or None: its first usable cold result.  smooth=True: two launches
+    more, ut_pose_information_views at the tracked poses and ut_smooth_pose_sequence with step_var (required then), angle_sigma,
+    frame_weight, centre and with_sigma as for smooth_fitted_sequence.  Four or six launches on the current stream and between them
+    only the cold chain's device copies, so that the chain is capturable with deferred checks.  Returns (joint_angles [n,22],
+    wrist_xf [n,4,4], info f32 [n,4] of the chosen fits, chosen i32 [n]: _native.UT_TRACK_*, the cold chain's four results) and,
+    with smooth=True, the smoother's (joint_angles [n_seq,T,22], wrist_xf [n_seq,T,4,4], info [n_seq,T,4], param_sigma or None) as a
+    sixth item."""
+    n = window.shape[0]
+    if n_seq < 1 or n % n_seq:
+        raise ValueError(f"{n} hand-samples are not {n_seq} sequences of equal length")
+    if smooth and step_var is None:
+        raise ValueError("smooth=True needs step_var")
+    frames = n // n_seq
+    cold = _cold_chain(hand_model, (window, src_row, cam_params), weights, limits, mirror, bank_angles, seeds, iters, max_iters, loss,
+                       loss_scale, t_scale, engine)
+    ja, xf, info, chosen = _native.track_pose_views(hand_model, window, src_row, cam_params, frames, init_angles, init_wrist_xf, cold, weights,
+                                                    limits, mirror, lengths, t_scale, max_iters, loss, loss_scale, recover_ratio,
+                                                    recover_floor, engine=engine)
+    if not smooth:
+        return ja, xf, info, chosen, cold
+    pose_info, pivot = _native.pose_information_views(hand_model, ja, xf, window, src_row, cam_params, weights=weights, angle_sigma=angle_sigma,
+                                                      mirror=mirror, t_scale=t_scale, loss=loss, loss_scale=loss_scale, param_sigma=False,
+                                                      landmark_cov=False, info=False, engine=engine)[:2]
+    sja, sxf, sigma, sinfo = _native.smooth_pose_sequence(ja.reshape(n_seq, frames, 22), xf.reshape(n_seq, frames, 4, 4), pose_info, pivot,
+                                                          step_var, frame_weight=frame_weight, lengths=lengths, centre=centre,
+                                                          t_scale=t_scale, param_sigma=with_sigma, engine=engine)
+    return ja, xf, info, chosen, cold, (sja, sxf, sinfo, sigma)
 
 
 def calibrate_scale_in_views(hand_model: torch.Tensor, window: torch.Tensor, cam_params: torch.Tensor, src_row: torch.Tensor,

@@ -19,6 +19,7 @@ from . import _native, geometry
 from .geometry import CameraModel, PinholePlaneCameraModel
 from .hand import NUM_HANDS, NUM_JOINTS_PER_HAND, RIGHT_HAND_INDEX, HandModel, scaled_hand_model, skin_landmarks, skin_mesh
 from .hand import FIT_CONVERGED, fit_landmarks, fit_landmarks_info, fit_landmarks_views, fit_landmarks_views_cold, pose_uncertainty_views, smooth_poses
+from .hand import RECOVER_FLOOR_PX, RECOVER_RATIO, TRACK_COLD, track_landmarks_views
 from .hand import ScaleCalibration, calibrate_scale, calibrate_scale_in_views
 from .hand import device_blob, fk_device, render_mesh as _render_mesh
 from .model import InputFrameData, InputFrameDesc, InputSkeletonData, RegressorOutput
@@ -310,16 +311,10 @@ def smooth_hand_poses_in_views(hand_model: HandModel, cameras: List[List[CameraM
     n_cams = win.shape[1]
     if weights is not None:
         weights = np.ascontiguousarray(weights, np.float32)
-    poses, pose = [], init
-    tables = []
-    for t in range(frames):
-        table, _w, _wt = _window_inputs("smooth_hand_poses_in_views", cameras[t], win[t], None if weights is None else weights[t], (n_cams, 21, 2))
-        tables.append(table)
-        pose = refine_hand_pose_in_views(hand_model, cameras[t], win[t], hand_idx, pose, None if weights is None else weights[t], loss=loss,
-                                         loss_scale=loss_scale)[0]
-        poses.append(pose)
-    ja = torch.from_numpy(np.stack([np.asarray(p.joint_angles, np.float32) for p in poses]))
-    xf = torch.from_numpy(np.stack([np.asarray(p.wrist_xform, np.float32) for p in poses]))
+    tables = [_window_inputs("smooth_hand_poses_in_views", cameras[t], win[t], None if weights is None else weights[t], (n_cams, 21, 2))[0]
+              for t in range(frames)]
+    ja, xf, fit_info = _track_one_sequence(hand_model, win, tables, hand_idx, init, None, weights, loss, loss_scale, RECOVER_RATIO)[:3]
+    poses = [_pose_from_fit(ja[t], xf[t], fit_info[t]) for t in range(frames)]
     rows = torch.arange(frames * n_cams, dtype=torch.int32).reshape(frames, n_cams)
     mirror = _mirror_flag(hand_idx)
     unc = pose_uncertainty_views(hand_model, ja, xf, torch.from_numpy(win), rows, torch.from_numpy(np.concatenate(tables)),
@@ -357,10 +352,6 @@ def refine_hand_pose_in_views(hand_model: HandModel, cameras: List[CameraModel],
     return out
 
 
-RECOVER_RATIO = 1.5       # DESIGN.md, "Start of a pose fit in the views": warm rms / cold rms is 1.00 on the hand, 2.7 (median) once lost
-RECOVER_FLOOR_PX = 0.01
-
-
 def hand_pose_from_window_keypoints_cold(hand_model: HandModel, cameras: List[CameraModel], window_keypoints: np.ndarray,
                                          hand_idx: int, weights: Optional[np.ndarray] = None, loss="squared", loss_scale: float = 3.0):
     """From 2-D detections to a pose with no start at all, one camera being enough: window_keypoints [n_cams,21,2] of one hand in
@@ -381,17 +372,19 @@ def track_hand_poses_in_views(hand_model: HandModel, cameras: List[List[CameraMo
                               weights: Optional[np.ndarray] = None, loss="squared", loss_scale: float = 3.0):
     """One hand through T frames of detections with a way back after a loss: cameras[t] the cameras of frame t (the same number in
     every frame), window_keypoints [T,n_cams,21,2], weights [T,n_cams,21] or None.  The cold chain of
-    hand_pose_from_window_keypoints_cold runs for all T frames as ONE batch (three launches).  Then frame by frame the warm fit of
-    refine_hand_pose_in_views from the previous frame's choice - frame 0 from `init`, or the cold result when init is None.  A
-    frame keeps its warm fit unless that is refused or its rms exceeds recover_ratio x the cold rms + RECOVER_FLOOR_PX: then the
-    cold result is taken (if it is not refused itself), and the next frame starts from it.  Returns (the T SingleHandPoses, info
-    [T,4] of the chosen fits, recovered [T] bool: the frames that took the cold result)."""
+    hand_pose_from_window_keypoints_cold runs for all T frames as ONE batch (three launches).  Then, in ONE ut_track_pose_views launch
+    (hand.track_landmarks_views), frame by frame the warm fit of refine_hand_pose_in_views from the previous frame's choice - frame
+    0 from `init`, or the cold result when init is None.  A frame keeps its warm fit unless that is refused or its rms exceeds
+    recover_ratio x the cold rms + RECOVER_FLOOR_PX: then the cold result is taken (if it is not refused itself), and the next frame
+    starts from it.  recover_ratio must be finite and at least 1 (the C entry takes no infinity: a ratio such as 1e30 recovers on a
+    refused fit alone).  Returns (the T SingleHandPoses, info [T,4] of the chosen fits, recovered [T] bool: the frames that took the
+    cold result)."""
     win = np.ascontiguousarray(window_keypoints, np.float64)
     frames = len(cameras)
     if frames == 0 or win.ndim != 4 or win.shape[0] != frames:
         raise ValueError(f"window_keypoints must be [{frames},n_cams,21,2] for {frames} frames of cameras, got {win.shape}")
-    if not recover_ratio >= 1.0:
-        raise ValueError(f"recover_ratio must be at least 1, got {recover_ratio}")
+    if not 1.0 <= recover_ratio < float("inf"):
+        raise ValueError(f"recover_ratio must be at least 1 and finite, got {recover_ratio}")
     n_cams = win.shape[1]
     if weights is not None:
         weights = np.ascontiguousarray(weights, np.float32)
@@ -402,27 +395,19 @@ def track_hand_poses_in_views(hand_model: HandModel, cameras: List[List[CameraMo
         hand_model, torch.from_numpy(win), rows, torch.from_numpy(np.concatenate(tables)),
         weights=None if weights is None else torch.from_numpy(weights), mirror=_mirror_flag(hand_idx).expand(frames), loss=loss,
         loss_scale=loss_scale)
-    poses, infos, recovered = [], np.zeros((frames, 4), np.float32), np.zeros(frames, bool)
-    pose = init
-    for t in range(frames):
-        cold_ok = int(cindex[t]) >= 0
-        take_cold = pose is None and cold_ok
-        if pose is not None:
-            warm, warm_info = refine_hand_pose_in_views(hand_model, cameras[t], win[t], hand_idx, pose, None if weights is None else weights[t],
-                                                        loss=loss, loss_scale=loss_scale)[:2]
-            lost = bool(int(warm_info[3]) & _native.UT_FIT_REFUSED) or float(warm_info[0]) > recover_ratio * float(cinfo[t, 0]) + RECOVER_FLOOR_PX
-            take_cold = lost and cold_ok
-            if not take_cold:
-                pose, infos[t] = warm, warm_info
-        if take_cold:
-            pose, infos[t] = _pose_from_fit(cja[t], cxf[t], cinfo[t]), cinfo[t].numpy()
-        elif pose is None:                                 # no init and a refused cold chain: nothing to start from yet
-            poses.append(_pose_from_fit(cja[t], cxf[t], cinfo[t]))
-            infos[t] = cinfo[t].numpy()
-            continue
-        recovered[t] = take_cold
-        poses.append(pose)
-    return poses, infos, recovered
+    ja, xf, info, chosen = _track_one_sequence(hand_model, win, tables, hand_idx, init, (cja, cxf, cinfo, cindex), weights, loss, loss_scale,
+                                               recover_ratio)
+    return [_pose_from_fit(ja[t], xf[t], info[t]) for t in range(frames)], info.numpy(), (chosen == TRACK_COLD).numpy()
+
+
+def _track_one_sequence(hand_model, win, tables, hand_idx, init, cold, weights, loss, loss_scale, recover_ratio):
+    """hand.track_landmarks_views on one hand's T frames: win [T,n_cams,21,2], tables the T frames' camera tables, init a
+    SingleHandPose or None, cold the four results of fit_landmarks_views_cold on the same rows or None."""
+    frames, n_cams = win.shape[:2]
+    rows = torch.arange(frames * n_cams, dtype=torch.int32).reshape(frames, n_cams)
+    return track_landmarks_views(hand_model, torch.from_numpy(win), rows, torch.from_numpy(np.concatenate(tables)), _start_tensors(init), cold,
+                                 weights=None if weights is None else torch.from_numpy(weights), mirror=_mirror_flag(hand_idx), loss=loss,
+                                 loss_scale=loss_scale, recover_ratio=recover_ratio, recover_floor=RECOVER_FLOOR_PX)
 
 
 def _chain_pose_from_window_keypoints(hand_model, cameras, window_keypoints, hand_idx, weights, init, use_information):
